@@ -44,7 +44,20 @@ class Clock(object):
         t0 = time.perf_counter()
         last = runner.run(first + warmup, count)
         self.fence()
-        return self.max_over_ranks(time.perf_counter() - t0), last
+        dt = time.perf_counter() - t0
+        runner.last_loss = last                              # (what the runner's outputs() reports as the last step's loss)
+        return self.max_over_ranks(dt), last
+
+
+def measure_steps(clock, runner, warmup, steps, rows_global):
+    """A plain run's protocol: `warmup` untimed steps, then exactly `steps` steps in ONE timed region (every graph the region
+    replays is captured before the clock starts); ms_per_step = the region / steps.  The runner has run warmup + steps steps
+    when it returns, whatever the clock said, so the same arguments leave the same state behind."""
+    dt, last = clock.timed(runner, 0, warmup, steps)
+    per = dt / steps
+    return {"ms_per_step": per * 1e3, "value": rows_global / per, "min_ms_per_step": per * 1e3, "max_ms_per_step": per * 1e3,
+            "repeats": 1, "segments_per_repeat": 1, "timed_steps_per_repeat": steps, "final_loss": float(last),
+            "single_window": True}
 
 
 def measure(clock, runner, warmup, steps, repeats, min_ms, rows_global):

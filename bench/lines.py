@@ -150,8 +150,10 @@ def make_line(args, widths, rows, kind, world, warmup, steps, res, runner, trans
         "ms_per_step": round(res["ms_per_step"], 5), "higher_is_better": True, "scaling": scaling,
         "vs_baseline": None, "dtype": "bf16 (fp32 accumulate, fp32 master weights)" if args.workload == "E" else "f32",
         "data": "synthetic",
-        "timing": {"statistic": "median of %d repeats of [%d warm-up steps + %d timed steps] (max over ranks each)"
-                                % (res["repeats"], warmup, res["timed_steps_per_repeat"]),
+        "timing": {"statistic": ("one timed region of %d steps after %d warm-up steps (max over ranks)" % (steps, warmup)
+                                 if res.get("single_window") else
+                                 "median of %d repeats of [%d warm-up steps + %d timed steps] (max over ranks each)"
+                                 % (res["repeats"], warmup, res["timed_steps_per_repeat"])),
                    "min_ms_per_step": round(res["min_ms_per_step"], 5), "max_ms_per_step": round(res["max_ms_per_step"], 5),
                    "segments_per_repeat": res["segments_per_repeat"], "timed_ms_per_repeat": round(res["ms_per_step"] * res["timed_steps_per_repeat"], 2)},
         "config": {"workload": "%s: Dense/ReLU MLP %s, %d rows per GPU (global batch %d), whole-batch "

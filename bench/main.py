@@ -13,12 +13,13 @@ import numpy as np
 
 from .common import GLOBAL_BATCH_D, PEAK_FP32_MFMA_TFLOPS, WIDTHS_A, WIDTHS_C, WIDTHS_E, _lib, tn    # noqa: F401
 from .common import brief
-from .clock import Clock, measure
+from .clock import Clock, measure, measure_steps
 from .runners import FusedRun, OpsRun, fixture_check, timed_rows_check
 from .roofline import attach_gemm_traffic, box_object, dw_adam_roofline_in_step, latency_roofline, time_gemms, time_gemms_bf16
 from .cpu import cpu_baseline
 from .lines import config_e_object, epoch_loop_object, make_line
 from .multi_gpu import collective_latency_table, collective_selftest, rccl_version_string, self_launch, topology_object
+from .outputs import write_outputs
 
 
 HOST_POOL = {}                                             # what fit_blas_pool_to_cpu_quota() found / did (main())
@@ -100,10 +101,34 @@ def dp_world1_objects(line, args, widths, kind, warmup, steps, solo, use_graph):
             comm1.close()
 
 
+def dp_world1_batch_sizes(line, args, widths, kind, warmup, steps, solo, use_graph, comm, transports):
+    """N = 1 with a forced communicator: the data-parallel step (both collectives issued) at the per-rank batches of the strong
+    curve and of weak_scaling_1024, and the reference's own example net at 128 / 1024 rows."""
+    dp_sizes = {}
+    for rows_b in (256, 512, 1024):                      # the per-rank batches of the strong curve and of weak_scaling_1024
+        rb_run = FusedRun(widths, rows_b, kind, 32, 0, 1, comm, True, use_graph=use_graph)
+        dp_sizes[str(rows_b)] = brief(measure(solo, rb_run, warmup, steps, 3, args.min_ms, rows_b),
+                                      graph_captured=rb_run.chunk is not None)
+        del rb_run
+    ex_widths = [784, 200, 100, 70, 30, 10]
+    ex_dp = {}
+    for rows_b in (128, 1024):
+        rb_run = FusedRun(ex_widths, rows_b, kind, 32, 0, 1, comm, True, use_graph=use_graph)
+        ex_dp[str(rows_b)] = brief(measure(solo, rb_run, warmup, steps, 3, args.min_ms, rows_b),
+                                   graph_captured=rb_run.chunk is not None)
+        del rb_run
+    if line is not None:
+        line["dp_world1_batch_sizes"] = dict(dp_sizes, note="the data-parallel step (both collectives issued, world 1) at the "
+                                             "per-rank batches of the strong curve (256 / 512) and of weak_scaling_1024; transport: %s"
+                                             % (transports["used"] if transports else "rccl"))
+        line.setdefault("reference_example_net", {"widths": "-".join(map(str, ex_widths))})["dp_world1"] = ex_dp
+
+
 def data_parallel_primary(args, comm, clock, runner, widths, rows, kind, world, rank, warmup, steps, force_dp, emit, all_ranks,
-                          p2p_alive, replicas_identical):
+                          p2p_alive, replicas_identical, timer):
     """The primary measurement of a data-parallel line: the same runner timed on RCCL first (north_star's named transport), on the
-    xGMI peer-to-peer path second; both are reported, and `value` follows a RULE, not a best-of-two.  Returns (result, transports)."""
+    xGMI peer-to-peer path second; both are reported, and `value` follows a RULE, not a best-of-two.  `timer(runner)` is the
+    run's timing protocol.  Returns (result, transports)."""
     # Data-parallel run.  RCCL first (north_star's named transport), the xGMI peer-to-peer path second; both are
     # reported.  The latency path carries f32 sums up to its mapped capacity: config A's 0.94 MB arena, not C's
     # 134 MB or E's 1 GB — those go to RCCL whatever the transport's state.
@@ -116,7 +141,7 @@ def data_parallel_primary(args, comm, clock, runner, widths, rows, kind, world, 
         if have_p2p:
             comm.set_p2p(False)
             runner.capture()
-        res_rccl = measure(clock, runner, warmup, steps, args.repeats, args.min_ms, rows * world)
+        res_rccl = timer(runner)
         transports["rccl"] = brief(res_rccl, replicas_identical=replicas_identical(runner),
                                    graph_captured=runner.chunk is not None)
     primary, used = res_rccl, "rccl"
@@ -143,7 +168,7 @@ def data_parallel_primary(args, comm, clock, runner, widths, rows, kind, world, 
         comm.set_p2p(True)
         try:
             runner.capture()
-            res_p2p = measure(clock, runner, warmup, steps, args.repeats, args.min_ms, rows * world)
+            res_p2p = timer(runner)
         except Exception as exc:                              # noqa: BLE001 - a peer timeout raises on every rank (comm.check votes)
             sys.stderr.write("bench: the peer-to-peer leg raised: %s\n" % exc)
             res_p2p = None
@@ -273,10 +298,18 @@ def main():
     ap.add_argument("--rows", type=int, default=None, help="rows per GPU for workload A (default 128; N>1: 1024/N)")
     ap.add_argument("--scaling", default="weak", choices=["strong", "weak"],
                     help="N>1, workload A: which curve `value` is on (the other one is reported beside it)")
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--min-ms", type=float, default=50.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary objects (config_C, paths, ...)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: `value` on the median-of-repeats protocol, the parity checks against "
+                         "the reference's fixtures, scaling curves, rooflines, other configurations and paths, the epoch loop, the CPU "
+                         "baseline, the box probe, the multi-GPU diagnostics (default: set up, warm up, time exactly --steps steps, print "
+                         "the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last one (the loss, every layer's weight and "
+                         "bias) as DIR/<name>.npy, float32, at most 64 MB in all (a larger array as a fixed, seeded sample)")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: timed repeats of the median-of-repeats protocol")
+    ap.add_argument("--min-ms", type=float, default=50.0, help="--full: least time one timed repeat brackets")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the secondary objects (config_C, paths, ...)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--epoch-loop-only", action="store_true", help="N = 1: print just the epoch_loop object")
     args = ap.parse_args()
@@ -354,6 +387,9 @@ def main():
         steps = args.steps if args.steps is not None else 20
         warmup = args.warmup if args.warmup is not None else 3
         n_batches = 2
+    if steps < 1 or warmup < 0:
+        raise SystemExit("bench: --steps must be at least 1 and --warmup at least 0")
+    extras = args.full and not args.no_extras
 
     # ---------------------------------------------------------------- primary measurement
     transports = None
@@ -386,19 +422,32 @@ def main():
         st = comm.p2p_status() if comm is not None and hasattr(comm, "p2p_status") else None
         return all_ranks(bool(st and st["enabled"] and not st["dead"]))
 
-    selftest_before = None
-    if comm is not None and args.path == "fused":
+    selftest_before = window = None
+    if comm is not None and args.path == "fused" and args.full:
         selftest_before = collective_selftest(comm, world, rank, all_ranks)
+    if args.full:
+        timer = lambda r: measure(clock, r, warmup, steps, args.repeats, args.min_ms, rows * world)    # noqa: E731
+    else:
+        timer = lambda r: measure_steps(clock, r, warmup, steps, rows * world)                          # noqa: E731
     if comm is not None and args.path == "fused" and isinstance(runner, FusedRun):
         res, transports = data_parallel_primary(args, comm, clock, runner, widths, rows, kind, world, rank, warmup, steps, force_dp, emit,
-                                                all_ranks, p2p_alive, replicas_identical)
+                                                all_ranks, p2p_alive, replicas_identical, timer)
     else:
-        res = measure(clock, runner, warmup, steps, args.repeats, args.min_ms, rows * world)
+        # exactly `steps` timed steps after `warmup` in every run, so that the outputs below are the same with and without --full;
+        # --full then times the same runner again on the median-of-repeats protocol for the line's `value`
+        res = window = measure_steps(clock, runner, warmup, steps, rows * world)
+    if args.dump_outputs:
+        named = runner.outputs()                           # on every rank: making sharded bf16 masters whole is a collective
+        if rank == 0:
+            write_outputs(args.dump_outputs, named)
+        del named
+    if window is not None and args.full:
+        res = timer(runner)
 
     if comm is not None and transports is not None:
         comm.set_p2p(transports["used"] == "xgmi-p2p")       # everything below runs on the primary transport
     check = check_timed = None
-    if args.path == "fused" and args.workload == "A":
+    if args.full and args.path == "fused" and args.workload == "A":
         # the reference's fixtures exist at global batches 128 and 1024: a weak-scaling line at N = 2 / 4 (global batch 256 /
         # 512) checks the same trainer + transport at config D's split instead (1024 / N rows per rank, the step form its
         # strong_scaling point times)
@@ -411,7 +460,7 @@ def main():
             check["rows_per_rank"], check["global_batch"] = rows_chk, rows_chk * world
             check["step_form"] = ("single-GPU 2L - 2 launch step" if comm is None else
                                   "merged 2L - 2 launch data-parallel step, %d block(s) of <= 128 rows per rank" % ((rows_chk + 127) // 128))
-        if comm is not None and not args.no_extras:
+        if comm is not None and extras:
             # ... and the step form actually TIMED (its own rows per rank), against the single-GPU trainer on the whole batch
             check_timed = timed_rows_check(widths, rows, kind, rank, world, comm, force_dp, use_graph, torch)
             ok_t = all_ranks(check_timed["ok"] if check_timed is not None else True)
@@ -420,6 +469,9 @@ def main():
     if rank == 0:
         line = make_line(args, widths, rows, kind, world, warmup, steps, res, runner, transports, force_dp)
         line["host_blas_pool"] = dict(HOST_POOL)          # (rank 0's; every rank takes its share of half the CPU quota)
+        if window is not None and args.full:
+            line["timing"]["first_window"] = {"warmup": warmup, "timed_steps": steps, "ms_per_step": round(window["ms_per_step"], 5),
+                                              "note": "the protocol of a run without --full, on the same runner before the repeats"}
         if check is not None:
             line["parity_vs_reference_fixture"] = check
             if not check["ok"]:
@@ -430,12 +482,12 @@ def main():
                 exit_code = line["exit_code"] = 4
 
     # ---------------------------------------------------------------- scaling curves (workload A)
-    if args.workload == "A" and args.path == "fused" and not args.no_extras and args.rows is None:
+    if args.workload == "A" and args.path == "fused" and extras and args.rows is None:
         scaling_curves(line, args, comm, clock, solo, res, widths, rows, kind, world, rank, warmup, steps, use_graph, transports,
                        replicas_identical)
 
     # ---------------------------------------------------------------- what the communicator ran on (every line with one)
-    if comm is not None and args.path == "fused" and not args.no_extras:
+    if comm is not None and args.path == "fused" and extras:
         after = collective_selftest(comm, world, rank, all_ranks)
         table = collective_latency_table(comm, clock)
         if line is not None:
@@ -452,25 +504,8 @@ def main():
             comm.set_p2p(transports["used"] == "xgmi-p2p")
 
     # ---------------------------------------------------------------- forced communicator at world 1: the step forms of N > 1
-    if comm is not None and world == 1 and args.workload == "A" and args.path == "fused" and not args.no_extras and args.rows is None:
-        dp_sizes = {}
-        for rows_b in (256, 512, 1024):                      # the per-rank batches of the strong curve and of weak_scaling_1024
-            rb_run = FusedRun(widths, rows_b, kind, 32, 0, 1, comm, True, use_graph=use_graph)
-            dp_sizes[str(rows_b)] = brief(measure(solo, rb_run, warmup, steps, 3, args.min_ms, rows_b),
-                                          graph_captured=rb_run.chunk is not None)
-            del rb_run
-        ex_widths = [784, 200, 100, 70, 30, 10]
-        ex_dp = {}
-        for rows_b in (128, 1024):
-            rb_run = FusedRun(ex_widths, rows_b, kind, 32, 0, 1, comm, True, use_graph=use_graph)
-            ex_dp[str(rows_b)] = brief(measure(solo, rb_run, warmup, steps, 3, args.min_ms, rows_b),
-                                       graph_captured=rb_run.chunk is not None)
-            del rb_run
-        if line is not None:
-            line["dp_world1_batch_sizes"] = dict(dp_sizes, note="the data-parallel step (both collectives issued, world 1) at the "
-                                                 "per-rank batches of the strong curve (256 / 512) and of weak_scaling_1024; transport: %s"
-                                                 % (transports["used"] if transports else "rccl"))
-            line.setdefault("reference_example_net", {"widths": "-".join(map(str, ex_widths))})["dp_world1"] = ex_dp
+    if comm is not None and world == 1 and args.workload == "A" and args.path == "fused" and extras and args.rows is None:
+        dp_world1_batch_sizes(line, args, widths, kind, warmup, steps, solo, use_graph, comm, transports)
 
     # ---------------------------------------------------------------- configs[4] (bf16, 8 GPUs) on the data-parallel line
     # (a peer-to-peer-only group carries the bandwidth-sized collectives on the transport's bulk path — but only two such ranks may
@@ -479,7 +514,7 @@ def main():
     e_leg_ok = getattr(comm, "_rccl", False) or (getattr(comm, "p2p_bulk_bytes", 0) > 0 and
                                                  (os.environ.get("TNN_DEVICE") is None or world <= 2))
     if (comm is not None and e_leg_ok and args.workload == "A" and args.path == "fused"
-            and not args.no_extras and args.rows is None and os.environ.get("TNN_BENCH_CONFIG_E", "1") != "0"):
+            and extras and args.rows is None and os.environ.get("TNN_BENCH_CONFIG_E", "1") != "0"):
         # never at the price of the line: a watchdog on EVERY rank emits the line as it stands and ends the process if the
         # extra measurement does not come back (it is the first time this step form meets real links)
         limit_e = int(os.environ.get("TNN_BENCH_CONFIG_E_TIMEOUT_S", "180"))
@@ -514,13 +549,13 @@ def main():
             line["config_E"] = obj_e
 
     # ---------------------------------------------------------------- secondary objects (rank 0, N = 1)
-    if line is not None and world == 1 and not args.no_extras:
+    if line is not None and world == 1 and extras:
         single_gpu_secondary(line, args, widths, rows, kind, res, runner, solo, use_graph, comm)
 
-    if (rank == 0 and world == 1 and comm is None and line is not None and not args.no_extras and args.workload == "A"
+    if (rank == 0 and world == 1 and comm is None and line is not None and extras and args.workload == "A"
             and args.path == "fused" and args.rows is None):
         dp_world1_objects(line, args, widths, kind, warmup, steps, solo, use_graph)
-    if rank == 0 and world == 1 and line is not None and not args.no_extras:
+    if rank == 0 and world == 1 and line is not None and extras:
         line["box"] = box_object(line)
     emit(line)
     if comm is not None:

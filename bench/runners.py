@@ -24,6 +24,7 @@ class Runner(object):
     per-step losses, and eager_step(i) for the graph-less form."""
     n_batches = 1
     chunk = None
+    last_loss = None                 # loss of the last step of the last timed region (Clock.timed)
 
     def plan(self, first, count):
         out, i = [], first
@@ -114,6 +115,18 @@ class FusedRun(Runner):
     def params_crc(self):
         return int(np.frombuffer(np.asarray(self.trainer.params).tobytes(), dtype=np.uint32).sum(dtype=np.uint64))
 
+    def outputs(self):
+        """What a caller of the last timed step holds after it: its loss and every layer's weight and bias (a bf16 trainer's fp32
+        masters), host copies.  Sharded masters (data-parallel bf16 steps) are made whole first — a collective: every rank calls
+        this."""
+        if self.trainer.masters_sharded():
+            self.trainer.gather_masters()
+        out = [("loss", np.array([float(self.last_loss)], dtype=np.float32))]
+        for l in range(len(self.widths) - 1):
+            for key in ("w", "b"):
+                out.append(("%s%d" % (key, l), np.asarray(self.trainer.param_view(l, key))))
+        return out
+
     def launches_per_step(self):
         """Primitive calls (= kernel launches at this size) of the single-GPU step, counted by the library itself."""
         n = __import__("ctypes").c_int(0)
@@ -154,6 +167,7 @@ class OpsRun(Runner):
     staging copies are needed."""
 
     def __init__(self, widths, rows, kind, n_batches, rank=0, world=1, comm=None, graph=False):
+        from tinynn_autograd_amd.core.layers import Dense
         from tinynn_autograd_amd.core.losses import SoftmaxCrossEntropyLoss, SquaredErrorLoss
         from tinynn_autograd_amd.core.model import Model
         from tinynn_autograd_amd.core.optimizer import Adam
@@ -163,7 +177,9 @@ class OpsRun(Runner):
         X, Y = da.asarray(x_host), da.asarray(y_host)
         self.batches = [(X[i * rows:(i + 1) * rows], Y[i * rows:(i + 1) * rows]) for i in range(n_batches)]
         loss_layer = SoftmaxCrossEntropyLoss(comm=comm) if kind == "softmax_nll" else SquaredErrorLoss()
-        model = Model(net=build_net(widths), loss=loss_layer, optimizer=Adam(lr=1e-3), comm=comm)
+        net = build_net(widths)
+        self.dense = [layer for layer in net.layers if isinstance(layer, Dense)]
+        model = Model(net=net, loss=loss_layer, optimizer=Adam(lr=1e-3), comm=comm)
         tbatches = [(Tensor(a), Tensor(b)) for a, b in self.batches]
 
         def step(i):
@@ -184,6 +200,14 @@ class OpsRun(Runner):
 
     def eager_step(self, i):
         return self._step(i).values
+
+    def outputs(self):
+        """The last timed step's loss and every Dense layer's weight and bias after it, host copies (names as FusedRun.outputs)."""
+        out = [("loss", np.array([float(self.last_loss)], dtype=np.float32))]
+        for l, layer in enumerate(self.dense):
+            for key in ("w", "b"):
+                out.append(("%s%d" % (key, l), np.asarray(layer.params[key].values)))
+        return out
 
 
 def fixture_check(widths, rows, kind, rank, world, comm, force_dp, use_graph):

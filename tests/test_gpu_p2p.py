@@ -237,7 +237,7 @@ def test_bench_two_ranks_under_torchrun_share_the_gpu():
                PYTHONDONTWRITEBYTECODE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "128",
-           "--warmup", "64"]
+           "--warmup", "64", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -295,7 +295,7 @@ def test_bench_gpus_2_launches_its_own_ranks(gpus):
         env["TNN_BENCH_CONFIG_E"] = "0"                 # four 8192-wide bf16 trainers on one GPU: covered at N = 2
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "20", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -333,13 +333,15 @@ def test_bench_self_launch_fails_fast_when_a_rank_dies():
 
 
 @pytest.mark.gpu
-def test_bench_single_gpu_line_has_the_contract_objects():
-    """The driver's N = 1 command: one JSON line with the median-of-repeats protocol, the latency-bound roofline with the
-    per-launch event times, the 4096 GEMM roofline, config C's whole step, the drop-in API paths, the strong-scaling
-    N = 1 point (= `--workload A --rows 1024`), the parity check against the reference fixture and both CPU legs."""
+def test_bench_single_gpu_line_has_the_contract_objects(tmp_path):
+    """The driver's N = 1 command with --full: one JSON line with the median-of-repeats protocol, the latency-bound roofline
+    with the per-launch event times, the 4096 GEMM roofline, config C's whole step, the drop-in API paths, the strong-scaling
+    N = 1 point (= `--workload A --rows 1024`), the parity check against the reference fixture and both CPU legs.  Its
+    --dump-outputs are those of a plain run with the same arguments."""
     import json
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full",
+                        "--dump-outputs", str(tmp_path / "full")],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -364,9 +366,55 @@ def test_bench_single_gpu_line_has_the_contract_objects():
     assert cpu["cores"] == cpu[cpu["best_leg"]]["cores"]
     # `--workload A --rows 1024` is the same measurement as the strong-scaling N = 1 point
     r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                         "--rows", "1024", "--no-extras"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                         "--rows", "1024", "--no-extras", "--full"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, text=True, timeout=600)
     assert r2.returncode == 0, r2.stderr[-3000:]
     d2 = json.loads([l for l in r2.stdout.splitlines() if l.strip()][0])
     assert d2["config"]["global_batch"] == 1024
     assert abs(d2["value"] / d["strong_scaling"]["value"] - 1.0) < 0.1
+    # the same arguments without --full: the same outputs (--full times its repeats only after the plain run's steps)
+    r3 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                         "--dump-outputs", str(tmp_path / "plain")], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                        stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r3.returncode == 0, r3.stderr[-3000:]
+    names = sorted(p.name for p in (tmp_path / "full").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "plain").iterdir()) and "loss.npy" in names and "w0.npy" in names
+    for n in names:
+        np.testing.assert_array_equal(np.load(str(tmp_path / "full" / n)), np.load(str(tmp_path / "plain" / n)), err_msg=n)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_exactly_the_given_steps_and_dumps_its_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline alone, N steps in one timed region after W
+    warm-up steps, and --dump-outputs writes what that path computed in its last step — the loss and every layer's weight and
+    bias after W + N steps, as an eager trainer on the same seeded batches computes them."""
+    import json
+    from bench.common import WIDTHS_A
+    from bench.runners import FusedRun
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    warmup, steps = 7, 150                               # neither a multiple of the 64-step chunk: head and tail segments
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warmup), "--dump-outputs", str(tmp_path)], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["exit_code"] == 0 and d["value"] > 0
+    assert d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    t = d["timing"]
+    assert t["segments_per_repeat"] == 1 and "one timed region of %d steps" % steps in t["statistic"]
+    assert abs(t["timed_ms_per_repeat"] - steps * d["ms_per_step"]) <= 0.01
+    assert abs(d["value"] - 128 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for key in ("roofline", "cpu_baseline", "parity_vs_reference_fixture", "config_C", "epoch_loop", "box", "strong_scaling"):
+        assert key not in d, key
+    ref = FusedRun(WIDTHS_A, 128, "softmax_nll", 64, use_graph=False)
+    ref.last_loss = [ref.eager_step(i) for i in range(warmup + steps)][-1]
+    want = dict(ref.outputs())
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(n + ".npy" for n in want)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    np.testing.assert_allclose(np.load(str(tmp_path / "loss.npy")), [d["final_loss"]], rtol=1e-5)
+    for n, a in want.items():
+        got = np.load(str(tmp_path / (n + ".npy")))
+        assert got.dtype == np.float32 and got.shape == a.shape, n
+        np.testing.assert_allclose(got, a, rtol=1e-5, atol=1e-6, err_msg=n)

@@ -3,7 +3,7 @@
 gpurun call lands on a fresh box of the pool).  The fractions are quoted against the spec peak AND against the box's own probe
 (`box`, measured inside the same run).
 
-    for i in 1 2 3 4 5 6 7 8; do gpurun -- 'mkdir -p gpurun_out/spread; python3 bench.py > gpurun_out/spread/run'$i'.json'; done
+    python3 bench.py --full > run$i.json        (once on each of several boxes; the files gathered into the spread directory)
     python3 tools/box_spread.py > profiles/r05_box_spread.txt"""
 import glob
 import json

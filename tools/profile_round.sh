@@ -11,10 +11,10 @@ OUT=$ROOT/gpurun_out/${R}prof
 mkdir -p $OUT
 run() { echo "== $*" >> $OUT/log.txt; timeout 900 "$@" >> $OUT/log.txt 2>&1 < /dev/null; echo "rc=$?" >> $OUT/log.txt; }
 
-timeout 900 python3 bench.py --steps 20 --warmup 5 < /dev/null > $OUT/benchA.json 2>> $OUT/log.txt
-timeout 900 python3 bench.py --workload C < /dev/null > $OUT/benchC.json 2>> $OUT/log.txt
-timeout 900 python3 bench.py --workload E < /dev/null > $OUT/benchE.json 2>> $OUT/log.txt
-TNN_FORCE_COMM=1 timeout 900 python3 bench.py --no-cpu-baseline < /dev/null > $OUT/benchA_dp_world1.json 2>> $OUT/log.txt
+timeout 900 python3 bench.py --full --steps 20 --warmup 5 < /dev/null > $OUT/benchA.json 2>> $OUT/log.txt
+timeout 900 python3 bench.py --full --workload C < /dev/null > $OUT/benchC.json 2>> $OUT/log.txt
+timeout 900 python3 bench.py --full --workload E < /dev/null > $OUT/benchE.json 2>> $OUT/log.txt
+TNN_FORCE_COMM=1 timeout 900 python3 bench.py --full --no-cpu-baseline < /dev/null > $OUT/benchA_dp_world1.json 2>> $OUT/log.txt
 timeout 900 python3 tools/p2p_bench.py < /dev/null > $OUT/p2p_latency.txt 2>> $OUT/log.txt
 for w in 2 4 8; do timeout 400 python3 tools/p2p_stress.py --spawn $w --iters 1500 < /dev/null 2>> $OUT/log.txt | grep "^rank" >> $OUT/p2p_stress.txt; done
 # in-kernel wall-clock stamps of the data-parallel step's two communicating launches (debug library: make -C tinynn-autograd_amd/csrc trace)
@@ -58,10 +58,10 @@ run rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/cal/write -o cal -- tools/
 timeout 900 python3 tools/fetch_calibration.py $OUT/cal/known.txt $(find $OUT/cal/fetch -name "*.db" | head -1) $(find $OUT/cal/write -name "*.db" | head -1) < /dev/null > $OUT/fetch_calibration.txt 2>> $OUT/log.txt
 TNN_HOST_COMPILED=0 timeout 900 python3 tools/probes/eager_phases.py < /dev/null >> $OUT/eager_phases.txt 2>> $OUT/log.txt
 
-run rocprofv3 --kernel-trace --stats -d $OUT/ktA -o A -- python3 bench.py --steps 20 --warmup 5
+run rocprofv3 --kernel-trace --stats -d $OUT/ktA -o A -- python3 bench.py --full --steps 20 --warmup 5
 run rocprofv3 --kernel-trace --stats -d $OUT/ktAstep -o Astep -- python3 bench.py --no-extras --steps 2000 --warmup 64
-run rocprofv3 --kernel-trace --stats -d $OUT/ktC -o C -- python3 bench.py --workload C --no-cpu-baseline
-run rocprofv3 --kernel-trace --stats -d $OUT/ktE -o E -- python3 bench.py --workload E
+run rocprofv3 --kernel-trace --stats -d $OUT/ktC -o C -- python3 bench.py --full --workload C --no-cpu-baseline
+run rocprofv3 --kernel-trace --stats -d $OUT/ktE -o E -- python3 bench.py --full --workload E
 # the data-parallel step at world 1 (RCCL leg first, then the peer-to-peer leg) and the single-GPU step: duration + gap per launch
 TNN_FORCE_COMM=1 timeout 900 rocprofv3 --kernel-trace -d $OUT/ktDP -o dp -- python3 bench.py --no-extras --no-cpu-baseline --steps 2000 --warmup 64 >> $OUT/log.txt 2>&1 < /dev/null
 
