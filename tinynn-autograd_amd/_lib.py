@@ -31,6 +31,10 @@ from ._signatures import _SIGNATURES, _i64p, _p        # noqa: E402  (name -> ar
 
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["tnn_last_error"])
 
+from ._index_signatures import _INDEX_SIGNATURES, IndexDesc   # noqa: E402,F401  (include/tnn_index.h: libtnn_hip.so only)
+
+INDEX_SYMBOLS = sorted(_INDEX_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -81,6 +85,25 @@ class _Lib(object):
             setattr(self, name[4:], fast.get(name) or self._wrap(name, fn))
         self.fast_calls = len(fast)
         self.kind = self.cdll.tnn_backend_kind()
+        # the advanced-indexing entry points (include/tnn_index.h): required of the product library; the CPU test twin has
+        # none, and the paths that need them raise there
+        for name, argtypes in _INDEX_SIGNATURES.items():
+            fn = getattr(self.cdll, name, None)
+            if fn is None:
+                if self.kind == 1:
+                    raise ImportError("%s lacks %s (include/tnn_index.h) — rebuild it" % (path, name))
+                setattr(self, name[4:], self._absent(name))
+                continue
+            fn.argtypes = argtypes
+            fn.restype = c_int
+            setattr(self, name[4:], self._wrap(name, fn))
+
+    @staticmethod
+    def _absent(name):
+        def call(*args):
+            raise TnnError("%s (advanced indexing) needs libtnn_hip.so; the CPU test twin does not implement it" % name)
+        call.__name__ = name
+        return call
 
     def _wrap(self, name, fn):
         last_error = self.cdll.tnn_last_error

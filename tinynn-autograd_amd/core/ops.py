@@ -212,10 +212,13 @@ def transpose_(ts, axes=None):
 
 
 def getitem_(ts, key):
-    """reference: core/ops.py:282-290 (slice = view, integer array = row gather kernel)"""
+    """reference: core/ops.py:282-290 (slice = view, 1-D integer array = row gather kernel, any other numpy key = one
+    gather of csrc/tnn_index.hip).  The vjp assigns, as the reference's `recover_grad[key] = grad` does: where the key repeats
+    an index the LAST gradient wins (deterministic scatter) — not the sum np.add.at would give."""
     x = ts.values
     if isinstance(key, ts.__class__):
         key = key.values
+    key = da.expand_masks(key)         # a device mask is counted once: forward and vjp share its coordinates
     values = x[key]
 
     def grad_fn(g):

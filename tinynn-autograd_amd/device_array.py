@@ -26,6 +26,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from . import indexing as _ix
 from ._lib import F32, F64, I64, U8
 
 _CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int64): I64,
@@ -429,6 +430,18 @@ class DeviceArray(object):
     def _is_advanced(key):
         return isinstance(key, (list, np.ndarray, DeviceArray)) and not _is_scalar_like(key)
 
+    @staticmethod
+    def _is_rows_key(key):
+        """A 1-D integer key on axis 0 (a list, ndarray or device array): the row gather / scatter of tnn_ewise.hip.  Every
+        other array key (boolean masks, N-d index arrays, tuples that hold arrays) goes through indexing.py."""
+        if isinstance(key, DeviceArray):
+            return key.ndim == 1 and key.dtype != np.bool_
+        idx = np.asarray(key)
+        return idx.ndim == 1 and idx.dtype != np.bool_
+
+    def nonzero(self):
+        return _nonzero(self)
+
     def _index_array(self, key):
         if isinstance(key, DeviceArray):
             if key.dtype == np.bool_:
@@ -450,7 +463,7 @@ class DeviceArray(object):
                 return self
             raise IndexError("too many indices for array")
         src = self._contig()
-        if DeviceArray._is_advanced(key):
+        if DeviceArray._is_advanced(key) and DeviceArray._is_rows_key(key):
             if src.ndim < 1:
                 raise IndexError("too many indices for array")
             idx = src._index_array(key)
@@ -460,6 +473,8 @@ class DeviceArray(object):
                 _lib.get().gather_rows(src._ptr, idx._ptr, out._ptr, idx.size, row, src.shape[0],
                                        src._code())
             return out
+        if not _ix.is_basic(key):
+            return _index_gather(src, key)
         offset, shape, strides = src._basic_index(key)
         ptr = src._ptr + offset * src.itemsize
         owner = src if src._base is None else src._base
@@ -477,11 +492,31 @@ class DeviceArray(object):
         """np.take(a, indices, axis=0[, out]): the row gather of `a[indices]` (tnn_gather_rows), optionally INTO an existing
         array — a per-epoch permutation of a resident dataset (utils/data_iterator.py:27-28) then lands at the same HBM
         addresses every epoch, which is what lets a hipGraph captured over the epoch's batches be replayed."""
-        if not (axis == 0 or (axis is None and self.ndim == 1)) or mode != "raise":
-            raise TypeError("take: only axis 0 / mode 'raise' are implemented on device")
+        if mode != "raise":
+            raise TypeError("take: only mode 'raise' is implemented on device")
         src = self._contig()
+        if axis is None and src.ndim != 1:
+            src, axis = src.ravel(), 0
+        elif axis is None:
+            axis = 0
         if src.ndim < 1:
             raise IndexError("too many indices for array")
+        axis = int(axis)
+        if not -src.ndim <= axis < src.ndim:
+            raise np.exceptions.AxisError("axis %d is out of bounds for array of dimension %d" % (axis, src.ndim))
+        axis %= src.ndim
+        if axis != 0 or not DeviceArray._is_rows_key(indices):
+            # any other axis or index shape: one gather of a[:, ..., indices]
+            res = _index_gather(src, (slice(None),) * axis + (indices,))
+            if out is None:
+                return res
+            if (not isinstance(out, DeviceArray) or out.shape != res.shape or out.dtype != src.dtype or out._t
+                    or out._hv is not None):
+                raise ValueError("take: `out` must be a dense device array of shape %s and dtype %s"
+                                 % (res.shape, src.dtype))
+            if res.size:
+                _lib.get().memcpy_d2d(out._ptr, res._ptr, res.nbytes)
+            return out
         idx = src._index_array(indices)
         shape = (idx.size,) + src.shape[1:]
         if out is None:
@@ -501,13 +536,20 @@ class DeviceArray(object):
             raise ValueError("assignment destination is a read-only COPY (a padded trainer's logical parameter block): "
                              "use MLPTrainer.set_param(layer, key, value)")
         lib = _lib.get()
-        if DeviceArray._is_advanced(key):
+        if DeviceArray._is_advanced(key) and DeviceArray._is_rows_key(key):
             idx = self._index_array(key)
+            if isinstance(key, DeviceArray) or np.unique(np.asarray(key) % max(self.shape[0], 1)).size != idx.size:
+                # indices that may repeat: numpy's assignment, the last one wins (deterministic scatter)
+                _index_scatter(self, idx, value)
+                return
             row_shape = (idx.size,) + self.shape[1:]
             val = asarray(value).astype(self.dtype)._broadcast_to(row_shape)
             if val.size:
                 lib.scatter_rows(val._ptr, idx._ptr, self._ptr, idx.size, _prod(self.shape[1:]),
                                  self.shape[0], self._code())
+            return
+        if not _ix.is_basic(key):
+            _index_scatter(self, key, value)
             return
         offset, shape, strides = self._basic_index(key)
         if _prod(shape) == 0:
@@ -1076,6 +1118,152 @@ def matmul(a, b):
     return res
 
 
+# ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)
+def _need_eager(what):
+    if _lib.capturing:
+        raise RuntimeError("%s inside a graph capture: the output shape depends on the data (a device boolean mask must "
+                           "be counted and read back), which a captured graph cannot do; index with integer arrays or "
+                           "run it outside the capture" % what)
+
+
+class _DeviceHooks(_ix.HostHooks):
+    """indexing.normalize's view of device-resident keys: they stay on the device."""
+
+    def is_device(self, obj):
+        return isinstance(obj, DeviceArray)
+
+    def dtype_kind(self, obj):
+        return obj.dtype.kind
+
+    def as_index(self, obj):
+        return obj.astype(np.int64)._contig()
+
+    def nonzero(self, obj):
+        return _nonzero(obj)
+
+    def scalar_bool(self, obj):
+        _need_eager("a device boolean index")
+        return bool(obj.item())
+
+
+_HOOKS = _DeviceHooks()
+
+
+def _index_desc(plan):
+    """indexing.IndexPlan -> the tnn_index_desc structure; host index arrays are uploaded (returned, to stay alive)."""
+    desc = _lib.IndexDesc()
+    desc.ndim = len(plan.out_shape)
+    desc.narr = len(plan.arrays)
+    desc.base = plan.base
+    for d, (n, st) in enumerate(zip(plan.out_shape, plan.strides)):
+        desc.shape[d] = n
+        desc.stride[d] = st
+    keep = []
+    for k, (a, ist, astride, alen) in enumerate(plan.arrays):
+        a = asarray(a) if isinstance(a, np.ndarray) else a
+        keep.append(a)
+        desc.idx[k] = a._ptr
+        for d, s in enumerate(ist):
+            desc.istride[k][d] = s
+        desc.astride[k] = astride
+        desc.alen[k] = alen
+    return desc, keep
+
+
+def _index_gather(src, key):
+    """src[key] for any numpy key (indexing.py): ONE tnn_index_gather launch.  src: dense."""
+    plan = _ix.normalize(src.shape, key, _HOOKS)
+    out = DeviceArray._new(plan.out_shape, src.dtype)
+    if out.size:
+        desc, keep = _index_desc(plan)
+        _lib.get().index_gather(src._ptr, out._ptr, ctypes.byref(desc), src.itemsize)
+    return out
+
+
+def _index_scatter(dst, key, value):
+    """dst[key] = value for any numpy key: numpy's assignment — where targets repeat, the last position in C order of the
+    broadcast index space wins, deterministically (tnn_index_scatter).  dst: dense, not transposed."""
+    plan = _ix.normalize(dst.shape, key, _HOOKS)
+    if plan.size == 0:
+        return
+    val = asarray(value).astype(dst.dtype)
+    if val._hv is None:
+        val = val._contig()
+        while val.ndim > len(plan.out_shape) and val.shape[0] == 1:      # numpy drops leading unit dims of the value
+            val = val.reshape(val.shape[1:])
+    vst = _broadcast_strides(val.shape, plan.out_shape)
+    desc, keep = _index_desc(plan)
+    lib = _lib.get()
+    unique = plan.unique
+    winner = None
+    if not unique:
+        winner = DeviceArray._new((plan.target_count(),), np.int64)
+        lib.fill(winner._ptr, -1.0, winner.size, I64)
+    lib.index_scatter(val._dev(), _i64arr(vst) if vst else _i64arr((0,)), dst._ptr, ctypes.byref(desc), int(unique),
+                      winner._ptr if winner is not None else None, dst.itemsize)
+
+
+def _mask_total(m):
+    """(scratch, total) of a dense bool device array: launches 1 and 2 of the mask path plus one 8-B read-back."""
+    lib = _lib.get()
+    elems = ctypes.c_int64(0)
+    lib.mask_scratch_elems(m.size, ctypes.byref(elems))
+    scratch = DeviceArray._new((elems.value,), np.int64)
+    lib.mask_count(m._ptr if m.size else None, m.size, scratch._ptr)
+    total = np.zeros(1, dtype=np.int64)
+    lib.memcpy_d2h(total.ctypes.data, scratch._ptr + (elems.value - 1) * 8, 8)
+    return scratch, int(total[0])
+
+
+def _as_mask(a):
+    a = asarray(a)
+    if a._hv is not None:
+        a = a._contig()
+    return (a if a.dtype == np.bool_ else _compare(_lib.NE, a, 0.0))._contig()
+
+
+def _nonzero(a):
+    """np.nonzero on the device: a tuple of int64 coordinate arrays in C order (tnn_mask_count + tnn_mask_nonzero)."""
+    _need_eager("nonzero of a device array")
+    m = _as_mask(a)
+    if m.ndim == 0:
+        raise ValueError("Calling nonzero on 0d arrays is not allowed. Use np.atleast_1d(scalar).nonzero() instead.")
+    if m.ndim > MAX_NDIM:
+        raise TypeError("nonzero supports up to %d dimensions on device" % MAX_NDIM)
+    scratch, count = _mask_total(m)
+    coords = DeviceArray._new((m.ndim, count), np.int64)
+    if count:
+        _lib.get().mask_nonzero(m._ptr, m.size, scratch._ptr, m.ndim, _i64arr(m.shape), coords._ptr, count)
+    return tuple(coords[k] for k in range(m.ndim))
+
+
+def _np_count_nonzero(a, axis=None, keepdims=False):
+    if axis is not None or keepdims:
+        raise TypeError("np.count_nonzero on device supports axis=None only")
+    _need_eager("count_nonzero of a device array")
+    m = _as_mask(a)
+    return _mask_total(m)[1]
+
+
+def _np_flatnonzero(a):
+    return _nonzero(asarray(a)._contig().ravel())[0]
+
+
+def expand_masks(key):
+    """The key with every DEVICE boolean mask replaced by its nonzero() coordinate arrays (numpy's own rule for a mask), so
+    that a forward and its vjp index with one read-back between them (core/ops.py getitem_)."""
+    items = key if isinstance(key, tuple) else (key,)
+    if not any(isinstance(k, DeviceArray) and k.dtype == np.bool_ and k.ndim > 0 for k in items):
+        return key
+    out = []
+    for k in items:
+        if isinstance(k, DeviceArray) and k.dtype == np.bool_ and k.ndim > 0:
+            out.extend(_nonzero(k))
+        else:
+            out.append(k)
+    return tuple(out)
+
+
 # ---------------------------------------------------------------------- numpy function overrides
 def _np_concatenate(arrays, axis=0, **_):
     arrays = [asarray(x)._contig() for x in arrays]
@@ -1146,9 +1334,30 @@ def _np_repeat(a, repeats, axis=None):
     return out.reshape(a.shape[:axis] + (a.shape[axis] * repeats,) + a.shape[axis + 1:])
 
 
+_PAD_GATHER_MODES = ("edge", "reflect", "symmetric", "wrap")
+
+
 def _np_pad(a, pad_width, mode="constant", **kwargs):
-    if mode != "constant" or kwargs.get("constant_values", 0) != 0:
-        raise TypeError("np.pad on device supports mode='constant' with zeros only")
+    if mode in _PAD_GATHER_MODES and not kwargs:
+        # one gather: per axis a source table np.pad(arange(n), (before, after), mode) — tiny, and it handles widths past
+        # the axis (which reflect repeats) — passed as np.ix_-shaped index arrays, broadcast through stride 0
+        a = asarray(a)._contig()
+        pw = np.broadcast_to(np.asarray(pad_width, dtype=np.int64), (a.ndim, 2))
+        tables = [np.pad(np.arange(n, dtype=np.int64), (int(b), int(e)), mode) for n, (b, e) in zip(a.shape, pw)]
+        if not tables:
+            return a.copy()
+        return _index_gather(a, np.ix_(*tables))
+    cv = kwargs.get("constant_values", 0)
+    if mode != "constant" or set(kwargs) - {"constant_values"} or np.ndim(cv) != 0:
+        raise TypeError("np.pad on device supports the modes constant (scalar constant_values), edge, reflect, symmetric "
+                        "and wrap")
+    if cv != 0:
+        a = asarray(a)._contig()
+        pw = np.broadcast_to(np.asarray(pad_width, dtype=np.int64), (a.ndim, 2))
+        out = full(tuple(int(s + b + e) for s, (b, e) in zip(a.shape, pw)), float(cv), a.dtype)
+        if a.size:
+            out[tuple(slice(int(b), int(b) + s) for s, (b, e) in zip(a.shape, pw))] = a
+        return out
     a = asarray(a)._contig()
     pw = np.broadcast_to(np.asarray(pad_width, dtype=np.int64), (a.ndim, 2))
     out_shape = tuple(int(s + b + e) for s, (b, e) in zip(a.shape, pw))
@@ -1160,8 +1369,10 @@ def _np_pad(a, pad_width, mode="constant", **kwargs):
 
 
 def _np_where(cond, x=None, y=None):
+    if x is None and y is None:
+        return _nonzero(cond)
     if x is None or y is None:
-        raise TypeError("np.where(cond) without x, y has no device implementation")
+        raise ValueError("either both or neither of x and y should be given")
     c = asarray(cond)
     c = c if c.dtype == np.bool_ else _compare(_lib.NE, c, 0.0)
     cf = c.astype(_float_result_dtype(asarray(x), asarray(y)))
@@ -1203,6 +1414,9 @@ _ARRAY_FUNCTIONS = {
     np.clip: clip,
     np.pad: _np_pad,
     np.where: _np_where,
+    np.nonzero: _nonzero,
+    np.flatnonzero: _np_flatnonzero,
+    np.count_nonzero: _np_count_nonzero,
     np.copy: lambda a, **_: asarray(a).copy(),
     np.take: lambda a, indices, axis=None, out=None, mode="raise": asarray(a).take(indices, axis=axis, out=out, mode=mode),
     np.shape: lambda a: asarray(a).shape,
