@@ -35,6 +35,10 @@ from ._index_signatures import _INDEX_SIGNATURES, IndexDesc   # noqa: E402,F401 
 
 INDEX_SYMBOLS = sorted(_INDEX_SIGNATURES)
 
+from ._bmm_signatures import _BMM_SIGNATURES                  # noqa: E402  (include/tnn_bmm.h: libtnn_hip.so only)
+
+BMM_SYMBOLS = sorted(_BMM_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -87,21 +91,25 @@ class _Lib(object):
         self.kind = self.cdll.tnn_backend_kind()
         # the advanced-indexing entry points (include/tnn_index.h): required of the product library; the CPU test twin has
         # none, and the paths that need them raise there
-        for name, argtypes in _INDEX_SIGNATURES.items():
-            fn = getattr(self.cdll, name, None)
-            if fn is None:
-                if self.kind == 1:
-                    raise ImportError("%s lacks %s (include/tnn_index.h) — rebuild it" % (path, name))
-                setattr(self, name[4:], self._absent(name))
-                continue
-            fn.argtypes = argtypes
-            fn.restype = c_int
-            setattr(self, name[4:], self._wrap(name, fn))
+        # and the strided-batched GEMM (include/tnn_bmm.h), likewise: under the twin device_array.matmul loops over tnn_gemm
+        for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
+                                    (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul")):
+            for name, argtypes in table.items():
+                fn = getattr(self.cdll, name, None)
+                if fn is None:
+                    if self.kind == 1:
+                        raise ImportError("%s lacks %s (include/%s) — rebuild it" % (path, name, header))
+                    setattr(self, name[4:], self._absent(name, what))
+                    continue
+                fn.argtypes = argtypes
+                fn.restype = c_int
+                setattr(self, name[4:], self._wrap(name, fn))
+        self.has_bmm = hasattr(self.cdll, "tnn_gemm_batched")
 
     @staticmethod
-    def _absent(name):
+    def _absent(name, what):
         def call(*args):
-            raise TnnError("%s (advanced indexing) needs libtnn_hip.so; the CPU test twin does not implement it" % name)
+            raise TnnError("%s (%s) needs libtnn_hip.so; the CPU test twin does not implement it" % (name, what))
         call.__name__ = name
         return call
 

@@ -118,13 +118,59 @@ def pow_(ts1, ts2):
 
 
 def dot_(ts1, ts2):
-    """reference: core/ops.py:150-163.  `.T` is a lazy flag, so the vjps run as NT / TN GEMMs."""
-    values = ts1.values @ ts2.values
-    return build_binary_ops_tensor(
-        ts1, ts2,
-        lambda g: da.asarray(g) @ ts2.values.T,
-        lambda g: ts1.values.T @ da.asarray(g),
-        values)
+    """reference: core/ops.py:150-163.  `.T` is a lazy flag, so the vjps run as NT / TN GEMMs.
+
+    2-D @ 2-D is the reference's pair of calls.  For every other form numpy's matmul admits (stacks of matrices, broadcast
+    batch dimensions, 1-D operands) the reference's backward raises or mis-shapes (`.T` reverses ALL axes), so the vjps
+    follow the mathematics: dA = unbroadcast(G @ swap(B), A.shape), dB = unbroadcast(swap(A) @ G, B.shape), swap = the
+    last two axes, handed to the batched product as transpose flags and never copied; 1-D operands are promoted as
+    numpy promotes them."""
+    a, b = ts1.values, ts2.values
+    values = a @ b
+    if a.ndim == 2 and b.ndim == 2:
+        return build_binary_ops_tensor(
+            ts1, ts2,
+            lambda g: da.asarray(g) @ ts2.values.T,
+            lambda g: ts1.values.T @ da.asarray(g),
+            values)
+    grad_a, grad_b = _dot_vjps_nd(ts1, ts2)
+    return build_binary_ops_tensor(ts1, ts2, grad_a, grad_b, values)
+
+
+def _dot_vjps_nd(ts1, ts2):
+    """The two vjps of `a @ b` when an operand is 1-D or N-d (saved inputs are read at backward time, like everywhere)."""
+    a_shape, b_shape = tuple(ts1.values.shape), tuple(ts2.values.shape)
+    a2_shape = (1,) + a_shape if len(a_shape) == 1 else a_shape          # numpy's promotion: a row ...
+    b2_shape = b_shape + (1,) if len(b_shape) == 1 else b_shape          # ... and a column
+    K, N = b2_shape[-2], b2_shape[-1]
+
+    def promoted(g):
+        """g in the shape of the promoted product [batch..., M, N]"""
+        g = da.asarray(g)
+        shape = list(g.shape)
+        if len(b_shape) == 1:
+            shape.append(1)
+        if len(a_shape) == 1:
+            shape.insert(len(shape) - 1, 1)
+        return g.reshape(shape)
+
+    def grad_a(g):
+        b2 = da.asarray(ts2.values).reshape(b2_shape)
+        ga = da.matmul(promoted(g), b2, swap_b=True)                     # [batch..., M, K]
+        return _unbroadcast(ga, a2_shape).reshape(a_shape)
+
+    def grad_b(g):
+        a2 = da.asarray(ts1.values).reshape(a2_shape)
+        g = promoted(g)
+        if len(b2_shape) == 2 and len(a2_shape) > 2:
+            # X[..., M, K] @ W[K, N]: dW is ONE long-K TN product over all the rows — no [batch, K, N] temporary, no
+            # reduction pass
+            gb = a2.reshape(-1, K).T @ g.reshape(-1, N)
+        else:
+            gb = _unbroadcast(da.matmul(a2, g, swap_a=True), b2_shape)   # [batch..., K, N]
+        return gb.reshape(b_shape)
+
+    return grad_a, grad_b
 
 
 def maximum_(ts1, ts2):

@@ -26,6 +26,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from . import batching as _bt
 from . import indexing as _ix
 from ._lib import F32, F64, I64, U8
 
@@ -373,6 +374,17 @@ class DeviceArray(object):
                                 src._code())
         return out
 
+    def swapaxes(self, axis1, axis2):
+        """np.swapaxes: a transpose with the two axes exchanged (2-D: the lazy `.T`)."""
+        nd = self.ndim
+        for ax in (axis1, axis2):
+            if not -nd <= int(ax) < nd:
+                raise np.exceptions.AxisError("axis %d is out of bounds for array of dimension %d" % (ax, nd))
+        perm = list(range(nd))
+        i, j = int(axis1) % nd, int(axis2) % nd
+        perm[i], perm[j] = perm[j], perm[i]
+        return self.transpose(perm)
+
     def _broadcast_to(self, shape):
         """Materialised broadcast (np.broadcast_to + copy)."""
         shape = tuple(int(s) for s in shape)
@@ -620,7 +632,7 @@ class DeviceArray(object):
         return clip(self, min, max)
 
     def dot(self, o):
-        return matmul(self, o)
+        return _np_dot(self, o)
 
     # ------------------------------------------------------------------ numpy protocols
     def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
@@ -1083,13 +1095,16 @@ def argmax(a, axis=None, **_):
 
 
 # ---------------------------------------------------------------------- kernels: matmul
-def matmul(a, b):
-    """a @ b for 1-D / 2-D operands; a lazy `.T` on either side selects the NT / TN / TT kernel."""
+def matmul(a, b, swap_a=False, swap_b=False):
+    """a @ b by numpy's matmul rules.  1-D / 2-D operands: one tnn_gemm, a lazy `.T` on either side selects the NT / TN / TT
+    kernel.  N-d operands (stacks of matrices, broadcast batch dimensions): planned by batching.py — one 2-D GEMM where the
+    stack folds into the rows, one tnn_gemm_batched launch otherwise, a loop of tnn_gemm for few large matrices.
+    swap_a / swap_b: use that operand with its last two axes exchanged, by stride (the vjps of core/ops.py dot_)."""
     a, b = asarray(a), asarray(b)
     if a._hv is not None or b._hv is not None or a.ndim == 0 or b.ndim == 0:
         raise ValueError("matmul: input operand does not have enough dimensions")
-    if a.ndim > 2 or b.ndim > 2:
-        raise TypeError("matmul supports 1-D and 2-D operands on device")
+    if a.ndim > 2 or b.ndim > 2 or swap_a or swap_b:
+        return _matmul_nd(a, b, swap_a, swap_b)
     dt = _float_result_dtype(a, b)
     a, b = a._as_float(dt), b._as_float(dt)
     squeeze_m = a.ndim == 1
@@ -1116,6 +1131,56 @@ def matmul(a, b):
     if squeeze_n:
         return res.reshape(M)
     return res
+
+
+BMM_ROUTE = None      # tests / probes: "batched" or "loop" overrides the planner's choice between those two routes
+BMM_FORM = 0          # tests / probes: TNN_BMM_FORM_* of the batched launches (0: the library picks by shape)
+
+
+def _matmul_nd(a, b, swap_a, swap_b):
+    """The N-d product (and the 2-D one with an exchanged operand): plan on the host, then one of the three routes."""
+    dt = _float_result_dtype(a, b)
+    a, b = a._as_float(dt), b._as_float(dt)
+    lib = _lib.get()
+    plan = _bt.plan_matmul(a.shape, b.shape, a_t=a._t, b_t=b._t, swap_a=swap_a, swap_b=swap_b, native=lib.has_bmm)
+    if plan.copy_a or plan.copy_b:     # (dense arrays and 2-D lazy transposes are always expressible by stride)
+        raise TypeError("matmul: operand layout not expressible by strides")
+    if len(plan.out_shape) > MAX_NDIM:
+        raise TypeError("matmul supports results of up to %d dimensions on device" % MAX_NDIM)
+    res = DeviceArray._new(plan.out_shape, dt)
+    if not res.size:
+        return res
+    M, N, K = plan.M, plan.N, plan.K
+    code = res._code()
+    if K == 0:
+        lib.fill(res._ptr, 0.0, res.size, code)
+        return res
+    route = plan.route
+    if route != "gemm2d" and BMM_ROUTE is not None:
+        route = BMM_ROUTE
+    if route == "gemm2d":
+        lib.gemm(plan.ta, plan.tb, M, N, K, 1.0, a._ptr, plan.lda, b._ptr, plan.ldb, 0.0, res._ptr, N, code)
+    elif route == "batched":
+        nb = len(plan.batch)
+        lib.gemm_batched(plan.ta, plan.tb, M, N, K, a._ptr, plan.lda, b._ptr, plan.ldb, res._ptr, nb,
+                         _i64arr(plan.batch), _i64arr(plan.a_bstrides), _i64arr(plan.b_bstrides), code, BMM_FORM)
+    else:
+        isz = res.itemsize
+        step = M * N * isz
+        gemm, pa, pb, pc = lib.gemm, a._ptr, b._ptr, res._ptr
+        for i, (oa, ob) in enumerate(_bt.batch_offsets(plan)):
+            gemm(plan.ta, plan.tb, M, N, K, 1.0, pa + oa * isz, plan.lda, pb + ob * isz, plan.ldb, 0.0,
+                 pc + i * step, N, code)
+    return res
+
+
+def _np_dot(a, b):
+    """np.dot for operands of at most two dimensions (where it is matmul); numpy's N-d dot is a different contraction."""
+    a, b = asarray(a), asarray(b)
+    if a.ndim > 2 or b.ndim > 2:
+        raise TypeError("np.dot with an N-d operand is not matmul (it contracts the last axis of a with the second-to-last "
+                        "of b for every pair of stacks) and has no device implementation; use a @ b / np.matmul")
+    return matmul(a, b)
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)
@@ -1401,6 +1466,7 @@ _ARRAY_FUNCTIONS = {
     np.ravel: lambda a, order="C": asarray(a).ravel(),
     np.reshape: _np_reshape,
     np.transpose: lambda a, axes=None: asarray(a).transpose(axes),
+    np.swapaxes: lambda a, axis1, axis2: asarray(a).swapaxes(axis1, axis2),
     np.concatenate: _np_concatenate,
     np.sum: lambda a, axis=None, keepdims=False, **_: _reduce(_lib.RSUM, a, axis, keepdims),
     np.max: lambda a, axis=None, keepdims=False, **_: _reduce(_lib.RMAX, a, axis, keepdims),
@@ -1422,7 +1488,7 @@ _ARRAY_FUNCTIONS = {
     np.shape: lambda a: asarray(a).shape,
     np.ndim: lambda a: asarray(a).ndim,
     np.size: lambda a, axis=None: asarray(a).size if axis is None else asarray(a).shape[axis],
-    np.dot: matmul,
+    np.dot: _np_dot,
     np.matmul: matmul,
     np.allclose: _np_allclose,
     np.array_equal: _np_array_equal,
