@@ -32,6 +32,7 @@ enum { TNN_F32 = 0, TNN_F64 = 1, TNN_I64 = 2, TNN_U8 = 3, TNN_BF16 = 4 /* storag
 
 /* binary elementwise ops — reference core/ops.py:33 (add), :66 (mul), :94 (div), :122 (pow),
  * :167 (maximum), :192 (minimum) and the arithmetic inside their vjp bodies */
+/* TNN_MAX / TNN_MIN follow np.maximum / np.minimum: a NaN in either operand (array or scalar, either side) is the result */
 enum { TNN_ADD = 0, TNN_SUB = 1, TNN_MUL = 2, TNN_DIV = 3, TNN_POW = 4, TNN_MAX = 5, TNN_MIN = 6 };
 /* comparisons — core/tensor.py:48-58 (raw bool arrays), core/ops.py:170,173,195,198,229,238,338,340 */
 enum { TNN_GT = 0, TNN_GE = 1, TNN_LT = 2, TNN_LE = 3, TNN_EQ = 4, TNN_NE = 5 };
@@ -185,10 +186,12 @@ TNN_API int tnn_cast(const void* in, int in_dtype, void* out, int out_dtype, int
 
 /* ------------------------------------------------------------------ reductions (K4) ----------- */
 /* in viewed as [outer, red, inner] -> out [outer, inner]; covers axis=None (1,n,1), axis=0 of a
- * matrix (1,R,C) = bias gradient, axis=1 (R,C,1).  Deterministic (no atomics). */
+ * matrix (1,R,C) = bias gradient, axis=1 (R,C,1).  Deterministic (no atomics); no extent is limited by the
+ * launch grid.  NaN rule (numpy's): TNN_RMAX / TNN_RMIN of a slice that holds a NaN is NaN, wherever it sits. */
 TNN_API int tnn_reduce(int rop, const void* in, void* out, int64_t outer, int64_t red,
                        int64_t inner, int dtype);
-/* first-max index per row (np.argmax(x, axis=1), examples/mnist/run.py:89) -> int64 */
+/* first-max index per row (np.argmax(x, axis=1), examples/mnist/run.py:89) -> int64.  NaN rule (numpy's): a NaN counts
+ * as the maximum, so a row that holds one yields the index of its first NaN; an all -inf row yields 0. */
 TNN_API int tnn_argmax_rows(const void* in, void* out_i64, int64_t rows, int64_t cols, int dtype);
 
 /* ------------------------------------------------------------------ data movement (K5,K6) ----- */

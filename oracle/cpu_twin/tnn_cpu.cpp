@@ -15,6 +15,7 @@
 #include <string.h>
 #include <time.h>
 
+#include <cmath>
 #include <functional>
 #include <unordered_map>
 #include <set>
@@ -74,8 +75,8 @@ template <typename T> T bin(int op, T a, T b) {
         case TNN_MUL: return a * b;
         case TNN_DIV: return a / b;
         case TNN_POW: return (T)pow((double)a, (double)b);
-        case TNN_MAX: return a >= b ? a : b;
-        case TNN_MIN: return a <= b ? a : b;
+        case TNN_MAX: return (a >= b || a != a) ? a : b;   // np.maximum / np.minimum: a NaN on either side is the result
+        case TNN_MIN: return (a <= b || a != a) ? a : b;
     }
     return a;
 }
@@ -97,7 +98,7 @@ template <typename T> T una(int op, T a) {
         case TNN_LOG: return (T)log((double)a);
         case TNN_SQRT: return (T)sqrt((double)a);
         case TNN_SQUARE: return a * a;
-        case TNN_ABS: return a < 0 ? -a : a;
+        case TNN_ABS: return std::fabs(a);       // |-0.0| is +0.0
         case TNN_RECIP: return T(1) / a;
         case TNN_SIGMOID: return (T)(1.0 / (1.0 + exp(-(double)a)));
         case TNN_TANH: return (T)tanh((double)a);
@@ -142,6 +143,19 @@ Strides keep(const int64_t* s, int nd) {
     r.null = s == nullptr;
     for (int k = 0; k < kMaxDim; ++k) r.v[k] = (s && k < nd) ? s[k] : 0;
     return r;
+}
+// one direct conversion between the two C types, as the kernel and numpy do (a detour through double rounds an int64
+// above 2^53 twice on its way to float)
+template <typename TI>
+int cast_from(const TI* in, void* out, int odt, int64_t n) {
+    switch (odt) {
+        case TNN_F32: for (int64_t i = 0; i < n; ++i) ((float*)out)[i] = (float)in[i]; return 0;
+        case TNN_F64: for (int64_t i = 0; i < n; ++i) ((double*)out)[i] = (double)in[i]; return 0;
+        case TNN_I64: for (int64_t i = 0; i < n; ++i) ((int64_t*)out)[i] = (int64_t)in[i]; return 0;
+        case TNN_U8: for (int64_t i = 0; i < n; ++i) ((uint8_t*)out)[i] = in[i] != TI(0); return 0;
+    }
+    tnn::set_error("tnn_cast: unknown output dtype %d", odt);
+    return 2;
 }
 }  // namespace
 
@@ -226,6 +240,7 @@ int tnn_graph_destroy(void* ge) { delete (Graph*)ge; return 0; }
 int tnn_fill(void* dst, double value, int64_t n, int dtype) {
     NEED_INIT();
     RECORD(tnn_fill(dst, value, n, dtype));
+    if (dtype == TNN_U8) value = value != 0.0;      // a bool mask holds 0 or 1, like the kernel's fill
     ANY_SWITCH(dtype, "tnn_fill", { T* o = (T*)dst; for (int64_t i = 0; i < n; ++i) o[i] = (T)value; });
     return 0;
 }
@@ -440,24 +455,14 @@ int tnn_axpy(void* y, double alpha, const void* x, int64_t n, int dtype) {
 int tnn_cast(const void* in, int idt, void* out, int odt, int64_t n) {
     NEED_INIT();
     RECORD(tnn_cast(in, idt, out, odt, n));
-    for (int64_t i = 0; i < n; ++i) {
-        double v;
-        switch (idt) {
-            case TNN_F32: v = ((const float*)in)[i]; break;
-            case TNN_F64: v = ((const double*)in)[i]; break;
-            case TNN_I64: v = (double)((const int64_t*)in)[i]; break;
-            case TNN_U8: v = ((const uint8_t*)in)[i]; break;
-            default: tnn::set_error("tnn_cast: unknown input dtype %d", idt); return 2;
-        }
-        switch (odt) {
-            case TNN_F32: ((float*)out)[i] = (float)v; break;
-            case TNN_F64: ((double*)out)[i] = v; break;
-            case TNN_I64: ((int64_t*)out)[i] = idt == TNN_I64 ? ((const int64_t*)in)[i] : (int64_t)v; break;
-            case TNN_U8: ((uint8_t*)out)[i] = v != 0.0; break;
-            default: tnn::set_error("tnn_cast: unknown output dtype %d", odt); return 2;
-        }
+    switch (idt) {
+        case TNN_F32: return cast_from((const float*)in, out, odt, n);
+        case TNN_F64: return cast_from((const double*)in, out, odt, n);
+        case TNN_I64: return cast_from((const int64_t*)in, out, odt, n);
+        case TNN_U8: return cast_from((const uint8_t*)in, out, odt, n);
     }
-    return 0;
+    tnn::set_error("tnn_cast: unknown input dtype %d", idt);
+    return 2;
 }
 
 // ---- reductions ----
@@ -472,7 +477,8 @@ int tnn_reduce(int rop, const void* in, void* out, int64_t outer, int64_t red, i
                 double acc = rop == TNN_RSUM ? 0.0 : rop == TNN_RMAX ? -INFINITY : INFINITY;
                 for (int64_t r = 0; r < red; ++r) {
                     double v = ((const T*)in)[(o * red + r) * inner + i];
-                    acc = rop == TNN_RSUM ? acc + v : rop == TNN_RMAX ? (v > acc ? v : acc) : (v < acc ? v : acc);
+                    acc = rop == TNN_RSUM ? acc + v                               // max / min: a NaN is the result (numpy)
+                        : rop == TNN_RMAX ? ((v > acc || v != v) ? v : acc) : ((v < acc || v != v) ? v : acc);
                 }
                 ((T*)out)[o * inner + i] = (T)acc;
             }
@@ -487,7 +493,8 @@ int tnn_argmax_rows(const void* in, void* out, int64_t rows, int64_t cols, int d
         for (int64_t r = 0; r < rows; ++r) {
             const T* p = (const T*)in + r * cols;
             int64_t bi = 0;
-            for (int64_t k = 1; k < cols; ++k) if (p[k] > p[bi]) bi = k;
+            for (int64_t k = 1; k < cols && p[bi] == p[bi]; ++k)             // numpy: the first NaN is the maximum
+                if (p[k] > p[bi] || p[k] != p[k]) bi = k;
             ((int64_t*)out)[r] = bi;
         }
     });

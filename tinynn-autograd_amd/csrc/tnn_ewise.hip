@@ -43,8 +43,8 @@ __device__ __forceinline__ T bin(T a, T b) {
     if constexpr (OP == TNN_MUL) return a * b;
     if constexpr (OP == TNN_DIV) return a / b;
     if constexpr (OP == TNN_POW) return t_pow<T>(a, b);
-    if constexpr (OP == TNN_MAX) return a >= b ? a : b;   // np.maximum; ties irrelevant for values
-    if constexpr (OP == TNN_MIN) return a <= b ? a : b;
+    if constexpr (OP == TNN_MAX) return (a >= b || a != a) ? a : b;   // np.maximum: a NaN on either side is the result
+    if constexpr (OP == TNN_MIN) return (a <= b || a != a) ? a : b;
     return a;
 }
 
@@ -66,7 +66,10 @@ __device__ __forceinline__ T una(T a) {
     if constexpr (OP == TNN_LOG) return t_log<T>(a);
     if constexpr (OP == TNN_SQRT) return t_sqrt<T>(a);
     if constexpr (OP == TNN_SQUARE) return a * a;
-    if constexpr (OP == TNN_ABS) return a < T(0) ? -a : a;
+    if constexpr (OP == TNN_ABS) {      // clears the sign bit: |-0.0| is +0.0 (a `a < 0` test would leave it set)
+        if constexpr (sizeof(T) == 4) return __builtin_fabsf(a);
+        else return __builtin_fabs(a);
+    }
     if constexpr (OP == TNN_RECIP) return T(1) / a;
     if constexpr (OP == TNN_SIGMOID) return T(1) / (T(1) + t_exp<T>(-a));
     if constexpr (OP == TNN_TANH) return t_tanh<T>(a);

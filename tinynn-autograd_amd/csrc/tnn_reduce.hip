@@ -21,8 +21,10 @@ __device__ __forceinline__ A r_init() {
 template <int ROP>
 __device__ __forceinline__ A r_comb(A a, A b) {
     if constexpr (ROP == TNN_RSUM) return a + b;
-    if constexpr (ROP == TNN_RMAX) return b > a ? b : a;
-    return b < a ? b : a;
+    // numpy's rule: a NaN on either side is the result, so the outcome does not depend on which lane, slice or
+    // partial met it first
+    if constexpr (ROP == TNN_RMAX) return (b > a || b != b) ? b : a;
+    return (b < a || b != b) ? b : a;
 }
 template <int ROP>
 __device__ __forceinline__ A r_wave(A v) {
@@ -85,32 +87,36 @@ __global__ __launch_bounds__(kThreads) void row_split_kernel(const TI* __restric
 }
 
 // ---- inner > 1 : column reduce (the bias gradient, core/ops.py:52-54) --------------------------
-// block = 64 columns x 4 row-lanes; blockIdx.x = column strip, blockIdx.y = outer, blockIdx.z =
-// slice of `red`.  Loads are coalesced along `inner`.  out is [slice, outer, inner].
+// block = 64 columns x 4 row-lanes; blockIdx.x = column strip, blockIdx.y walks `outer` (stride gridDim.y: the grid's y
+// extent stops at 65535, `outer` does not), blockIdx.z = slice of `red`.  Loads are coalesced along `inner`.
+// out is [slice, outer, inner].
 template <typename TI, typename TO, int ROP>
 __global__ __launch_bounds__(kThreads) void col_kernel(const TI* __restrict__ in,
-                                                       TO* __restrict__ out, int64_t red,
-                                                       int64_t inner, int64_t rows_per_slice) {
+                                                       TO* __restrict__ out, int64_t outer,
+                                                       int64_t red, int64_t inner,
+                                                       int64_t rows_per_slice) {
     __shared__ A lds[4][64];
     int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     int64_t c = (int64_t)blockIdx.x * 64 + tx;
-    int64_t o = blockIdx.y;
     int64_t r0 = (int64_t)blockIdx.z * rows_per_slice;
     int64_t r1 = r0 + rows_per_slice;
     if (r1 > red) r1 = red;
-    A acc = r_init<ROP>();
-    if (c < inner) {
-        const TI* p = in + (o * red) * inner + c;
-        for (int64_t r = r0 + ty; r < r1; r += 4) acc = r_comb<ROP>(acc, (A)p[r * inner]);
-    }
-    lds[ty][tx] = acc;
-    __syncthreads();
-    if (ty == 0 && c < inner) {
-        A v = lds[0][tx];
-        v = r_comb<ROP>(v, lds[1][tx]);
-        v = r_comb<ROP>(v, lds[2][tx]);
-        v = r_comb<ROP>(v, lds[3][tx]);
-        out[((int64_t)blockIdx.z * gridDim.y + o) * inner + c] = (TO)v;
+    for (int64_t o = blockIdx.y; o < outer; o += gridDim.y) {   // block-uniform trip count: the barriers are safe
+        A acc = r_init<ROP>();
+        if (c < inner) {
+            const TI* p = in + (o * red) * inner + c;
+            for (int64_t r = r0 + ty; r < r1; r += 4) acc = r_comb<ROP>(acc, (A)p[r * inner]);
+        }
+        lds[ty][tx] = acc;
+        __syncthreads();
+        if (ty == 0 && c < inner) {
+            A v = lds[0][tx];
+            v = r_comb<ROP>(v, lds[1][tx]);
+            v = r_comb<ROP>(v, lds[2][tx]);
+            v = r_comb<ROP>(v, lds[3][tx]);
+            out[((int64_t)blockIdx.z * outer + o) * inner + c] = (TO)v;
+        }
+        if (o + gridDim.y < outer) __syncthreads();   // lds is written again by the next row group
     }
 }
 
@@ -159,21 +165,21 @@ int reduce_typed(const void* in, void* out, int64_t outer, int64_t red, int64_t 
     }
     int64_t rows_per_slice = (red + slices - 1) / slices;
     slices = (red + rows_per_slice - 1) / rows_per_slice;
-    dim3 grid((unsigned)strips, (unsigned)outer, (unsigned)slices);
+    dim3 grid((unsigned)strips, (unsigned)(outer > 65535 ? 65535 : outer), (unsigned)slices);
     if (slices == 1) {
-        hipLaunchKernelGGL((col_kernel<T, T, ROP>), grid, kThreads, 0, s, (const T*)in, (T*)out, red,
-                           inner, rows_per_slice);
+        hipLaunchKernelGGL((col_kernel<T, T, ROP>), grid, kThreads, 0, s, (const T*)in, (T*)out, outer,
+                           red, inner, rows_per_slice);
         TNN_LAUNCH_OK();
         return 0;
     }
     void* ws = nullptr;
     int64_t oi = outer * inner;
     if (tnn_malloc((size_t)(slices * oi) * sizeof(A), &ws)) return 1;
-    hipLaunchKernelGGL((col_kernel<T, A, ROP>), grid, kThreads, 0, s, (const T*)in, (A*)ws, red, inner,
-                       rows_per_slice);
+    hipLaunchKernelGGL((col_kernel<T, A, ROP>), grid, kThreads, 0, s, (const T*)in, (A*)ws, outer, red,
+                       inner, rows_per_slice);
     // second pass: ws is [slices, outer*inner] -> reduce over slices
     hipLaunchKernelGGL((col_kernel<A, T, ROP>), dim3((unsigned)((oi + 63) / 64), 1, 1), kThreads, 0, s,
-                       (const A*)ws, (T*)out, slices, oi, slices);
+                       (const A*)ws, (T*)out, (int64_t)1, slices, oi, slices);
     tnn_free(ws);
     TNN_LAUNCH_OK();
     return 0;
@@ -190,7 +196,14 @@ int reduce_dispatch(int rop, const void* in, void* out, int64_t outer, int64_t r
     return 2;
 }
 
-// first index of the row maximum (numpy argmax tie rule): one wave per row
+// first index of the row maximum (numpy argmax tie rule; a NaN counts as the maximum, so the first NaN wins): one
+// wave per row
+template <typename T>
+__device__ __forceinline__ bool argmax_better(T ov, int64_t oi, T best, int64_t bi) {
+    if (ov != ov) return !(best != best) || oi < bi;
+    if (best != best) return false;
+    return ov > best || (ov == best && oi < bi);
+}
 template <typename T>
 __global__ __launch_bounds__(kThreads) void argmax_rows_kernel(const T* __restrict__ in,
                                                                int64_t* __restrict__ out,
@@ -204,13 +217,14 @@ __global__ __launch_bounds__(kThreads) void argmax_rows_kernel(const T* __restri
         int64_t bi = INT64_MAX;
         for (int64_t k = lane; k < cols; k += 64) {
             T v = p[k];
-            if (v > best || bi == INT64_MAX) { best = v; bi = k; }   // strictly greater keeps the first
+            // strictly greater keeps the first; the seed takes whatever comes first (an all -inf row), a NaN sticks
+            if (bi == INT64_MAX || (!(best != best) && (v > best || v != v))) { best = v; bi = k; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             T ov = __shfl_xor(best, o, 64);
             int64_t oi = __shfl_xor(bi, o, 64);
-            if (oi != INT64_MAX && (bi == INT64_MAX || ov > best || (ov == best && oi < bi))) {
+            if (oi != INT64_MAX && (bi == INT64_MAX || argmax_better<T>(ov, oi, best, bi))) {
                 best = ov;
                 bi = oi;
             }
@@ -229,7 +243,8 @@ int tnn_reduce(int rop, const void* in, void* out, int64_t outer, int64_t red, i
     TNN_REQUIRE(outer >= 0 && red >= 0 && inner >= 0, "tnn_reduce: negative extent");
     if (outer * inner == 0) return 0;
     TNN_REQUIRE(red > 0 || rop == TNN_RSUM, "tnn_reduce: max/min of an empty axis");
-    TNN_REQUIRE(outer <= 65535 || inner == 1, "tnn_reduce: outer %lld too large", (long long)outer);
+    if (red == 0 && (dtype == TNN_F32 || dtype == TNN_F64))      // the sum over an empty axis is 0 (the slice arithmetic below divides by the rows per slice)
+        return tnn_memset(out, 0, (size_t)(outer * inner) * (dtype == TNN_F32 ? 4 : 8));
     switch (dtype) {
         case TNN_F32: return reduce_dispatch<float>(rop, in, out, outer, red, inner);
         case TNN_F64: return reduce_dispatch<double>(rop, in, out, outer, red, inner);
