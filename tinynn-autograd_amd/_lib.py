@@ -39,6 +39,10 @@ from ._bmm_signatures import _BMM_SIGNATURES                  # noqa: E402  (inc
 
 BMM_SYMBOLS = sorted(_BMM_SIGNATURES)
 
+from ._conv_signatures import _CONV_SIGNATURES                # noqa: E402  (include/tnn_conv.h: libtnn_hip.so only)
+
+CONV_SYMBOLS = sorted(_CONV_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -92,8 +96,10 @@ class _Lib(object):
         # the advanced-indexing entry points (include/tnn_index.h): required of the product library; the CPU test twin has
         # none, and the paths that need them raise there
         # and the strided-batched GEMM (include/tnn_bmm.h), likewise: under the twin device_array.matmul loops over tnn_gemm
+        # and convolution / pooling (include/tnn_conv.h): under the twin device_array composes them from slices and products
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
-                                    (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul")):
+                                    (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
+                                    (_CONV_SIGNATURES, "tnn_conv.h", "convolution")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -105,6 +111,7 @@ class _Lib(object):
                 fn.restype = c_int
                 setattr(self, name[4:], self._wrap(name, fn))
         self.has_bmm = hasattr(self.cdll, "tnn_gemm_batched")
+        self.has_conv = hasattr(self.cdll, "tnn_conv2d_fwd")
 
     @staticmethod
     def _absent(name, what):

@@ -5,6 +5,8 @@ Device-side differences: `Dense.forward` issues ONE GEMM with a bias epilogue (o
 node plus a broadcast-add node (`fused=False` restores the literal `inputs @ w + b`, core/layers.py:49);
 `Sigmoid` is a single fused kernel (the reference's raises on a Tensor).  The parameter dict order is
 "w" then "b" (core/layers.py:35): the optimizer's flatten order and the trainer's arena layout depend on it.
+
+Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / ops.max_pool2d_), enough for a LeNet.
 """
 
 from . import ops
@@ -113,3 +115,72 @@ class Tanh(Activation):
     def func(self, x):
         decay = ops.exp(-x)
         return (1.0 - decay) / (1.0 + decay)
+
+
+class Conv2D(Layer):
+    """2-D convolution over NCHW batches.  `kernel = (KH, KW, C_in, F)` in the upstream framework's order; the weight is
+    STORED as [F, C_in, KH, KW] (what the kernels read, and the order for which initializer.get_fans gives fan-in =
+    C_in KH KW and fan-out = F), the bias as [F].  C_in may be None and is then read off the first batch.  `fused=False`
+    runs the composed route (a loop over the filter taps on the generic array operations) and a separate ReLU."""
+
+    def __init__(self, kernel, stride=1, padding=0, w_init=XavierUniformInit(), b_init=ZerosInit(), fused=True):
+        super().__init__("Conv2D")
+        if len(kernel) != 4:
+            raise ValueError("Conv2D: kernel must be (KH, KW, C_in, F), got %r" % (kernel,))
+        kh, kw, c_in, f = kernel
+        self.fused = fused
+        self.stride, self.padding = stride, padding
+        self.initializers = dict(zip(PARAM_ORDER, (w_init, b_init)))
+        self.shapes = {"w": [int(f), c_in, int(kh), int(kw)], "b": [int(f)]}
+        self.params = dict.fromkeys(PARAM_ORDER)
+        self.inputs = None
+        self.is_init = False
+        if c_in is not None:
+            self._init_parameters(int(c_in))
+
+    def _init_parameters(self, channels):
+        self.shapes["w"][1] = channels
+        for name in PARAM_ORDER:
+            tensor = self.initializers[name](shape=self.shapes[name])
+            tensor.zero_grad()
+            self.params[name] = tensor
+        self.is_init = True
+
+    def forward(self, inputs, relu=False):
+        """relu=True is passed by Net.forward when the next layer is a ReLU: one launch for both (ops.conv2d_)."""
+        if len(inputs.shape) != 4:
+            raise ValueError("Conv2D: the input must be [N, C, H, W], got shape %s" % (tuple(inputs.shape),))
+        if not self.is_init:
+            self._init_parameters(int(inputs.shape[1]))
+        self.inputs = inputs
+        w, b = (self.params[name] for name in PARAM_ORDER)
+        if self.fused:
+            return ops.conv2d_(inputs, w, b, self.stride, self.padding, relu=relu)
+        out = ops.conv2d_(inputs, w, b, self.stride, self.padding, route="composed")
+        return ops.clip(out, 0.0) if relu else out
+
+
+class MaxPool2D(Layer):
+    """Max pooling over `pool_size` windows (integer or pair); stride None = the window; padding is -inf (ops.max_pool2d_:
+    the first maximum of a window in row-major order receives its gradient)."""
+
+    def __init__(self, pool_size, stride=None, padding=0):
+        super().__init__("MaxPool2D")
+        self.pool_size, self.stride, self.padding = pool_size, stride, padding
+        self.inputs = None
+
+    def forward(self, inputs):
+        self.inputs = inputs
+        return ops.max_pool2d_(inputs, self.pool_size, self.stride, self.padding)
+
+
+class Flatten(Layer):
+    """[N, ...] -> [N, prod(...)]: the batch axis is kept (ops.flatten_ ravels it away too)."""
+
+    def __init__(self):
+        super().__init__("Flatten")
+        self.inputs = None
+
+    def forward(self, inputs):
+        self.inputs = inputs
+        return ops.reshape(inputs, (int(inputs.shape[0]), -1))

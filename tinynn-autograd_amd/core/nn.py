@@ -2,7 +2,7 @@
 iteration over parameter tensors in the optimizer's flattening order, parameter counting and the Dense/ReLU
 structure query the whole-step trainer uses."""
 
-from .layers import Dense, ReLU
+from .layers import Conv2D, Dense, ReLU
 
 
 class Net(object):
@@ -16,7 +16,8 @@ class Net(object):
     # ------------------------------------------------------------------ reference API
     def forward(self, inputs):
         """Thread the input through the layers (core/nn.py:10-13).  A fused `Dense` directly followed by a `ReLU` runs
-        as ONE node (GEMM + bias + clip(., 0) epilogue, ops.dense_(relu=True)); the ReLU layer object is then skipped —
+        as ONE node (GEMM + bias + clip(., 0) epilogue, ops.dense_(relu=True); likewise a fused `Conv2D`, ops.conv2d_); the
+        ReLU layer object is then skipped —
         its `inputs` attribute (cached but never read by the reference, core/layers.py:67) holds the fused output."""
         layers, i, activations = self.layers, 0, inputs
         n = len(layers)
@@ -32,6 +33,10 @@ class Net(object):
                 feeds_head = head and i == n - 3
                 activations = layer.forward(activations, relu=True, head_w=layers[-1].params["w"] if feeds_head else None,
                                             head_b=layers[-1].params["b"] if feeds_head else None)
+                nxt.inputs = activations
+                i += 2
+            elif type(layer) is Conv2D and layer.fused and type(nxt) is ReLU:
+                activations = layer.forward(activations, relu=True)       # clip(., 0) in the convolution's epilogue
                 nxt.inputs = activations
                 i += 2
             else:

@@ -7,7 +7,8 @@ HIP kernels behind the C-ABI; nothing is computed on the host.  Cited line numbe
 reference expression each piece replaces.
 
 Extra fused nodes used by this package's own layers/losses (parity-tested against the generic chain):
-`dense_` (GEMM + bias epilogue), `sigmoid_`, `softmax_nll_` (whole-batch softmax NLL).
+`dense_` (GEMM + bias epilogue), `sigmoid_`, `softmax_nll_` (whole-batch softmax NLL), `conv2d_` / `max_pool2d_` (NCHW
+convolution and max pooling, csrc/tnn_conv.hip; the reference has neither).
 """
 
 import math
@@ -481,6 +482,87 @@ def dense_(x, w, b, relu=False, head_w=None, lazy=False, head_b=None):
     return node
 
 
+class _ConvVjp(object):
+    """The vjps of one ops.conv2d_ node: `fused_vjp` for Tensor.backward (dw and db from ONE launch, written into the
+    parameters' arena views when they are lent; dx only when x is an edge), per-edge forms for everybody else."""
+    __slots__ = ("x", "w", "b", "out", "stride", "padding", "relu", "route", "edges")
+
+    def __init__(self, x, w, b, out, stride, padding, relu, route):
+        self.x, self.w, self.b, self.out = x, w, b, out       # saved inputs by reference, read at backward time
+        self.stride, self.padding, self.relu, self.route = stride, padding, relu, route
+        self.edges = ()
+
+    def dz_of(self, g):
+        g = da.asarray(g)
+        if g._hv is not None or g.shape != self.out.shape:
+            g = g._as_float(self.out.dtype)._broadcast_to(self.out.shape)
+        return da.mul_signmask(g, self.out) if self.relu else g
+
+    def d_x(self, g):
+        return self.d_x_from(self.dz_of(g))
+
+    def d_w(self, g):
+        return da.conv2d_bwd_filter(self.x.values, self.dz_of(g), self.w.values.shape, self.stride, self.padding,
+                                    with_db=False, route=self.route)[0]
+
+    def d_b(self, g):
+        return self.dz_of(g).sum(axis=(0, 2, 3)).reshape(self.b.shape)
+
+    def fused_vjp(self, g, homes):
+        edges = self.edges
+        dz = self.dz_of(g)
+        res = {}
+        if "x" in edges:
+            res["x"] = self.d_x_from(dz)
+        if "w" in edges or "b" in edges:
+            home = dict(zip(edges, homes))
+            dw, db = da.conv2d_bwd_filter(self.x.values, dz, self.w.values.shape, self.stride, self.padding,
+                                          with_db="b" in edges, dw_out=home.get("w"), db_out=home.get("b"),
+                                          route=self.route)
+            res["w"] = dw
+            if db is not None:
+                bhome = home.get("b")
+                res["b"] = bhome if db is bhome else db.reshape(self.b.shape)
+        return [res[name] for name in edges]
+
+    def d_x_from(self, dz):
+        return da.conv2d_bwd_data(dz, self.w.values, self.x.values.shape, self.stride, self.padding, route=self.route)
+
+
+def conv2d_(x, w, b=None, stride=1, padding=0, relu=False, route=None):
+    """2-D convolution node: x [N, C, H, W] (*) w [F, C, KH, KW] + b [F] -> [N, F, OH, OW], OH = (H + 2 p - KH) // s + 1
+    (cross-correlation, zero padding, integer or pair stride / padding; no dilation, no groups).
+
+    Forward is ONE tnn_conv2d_fwd launch (implicit GEMM on MFMA; relu=True adds the clip(., 0) epilogue and keeps the vjp
+    mask z >= 0 in the sign bit of zero, like dense_).  Backward: dx = tnn_conv2d_bwd_data — not computed at all when x does
+    not require a gradient (the first layer) — and dw together with db from ONE tnn_conv2d_bwd_filter launch.  Under the
+    CPU test twin, and with route="composed" (or device_array.CONV_ROUTE), the same products run as a loop over the filter
+    taps and relu=True is a clip followed by the same sign encoding."""
+    xv, wv = x.values, w.values
+    bv = None if b is None else b.values
+    out = da.conv2d(xv, wv, bv, stride, padding, relu=relu, route=route)
+    ctx = _ConvVjp(x, w, b, out, stride, padding, relu, route)
+    parents = [(x, ctx.d_x), (w, ctx.d_w)] + ([(b, ctx.d_b)] if b is not None else [])
+    node = _make_node(x.__class__, out, parents)
+    ctx.edges = [name for name, t in (("x", x), ("w", w), ("b", b)) if t is not None and t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
+def max_pool2d_(x, kernel, stride=None, padding=0, route=None):
+    """Max pooling node over kernel windows of every [H, W] plane of x [N, C, H, W]; stride None = the kernel; padding is
+    -inf and must not exceed kernel // 2.  Tie rule: the FIRST maximum of the window in row-major order receives the whole
+    gradient (numpy's argmax rule, the rule da.argmax follows and what a fold of maximum_ gives, whose ties go to the first
+    operand).  NaN propagates like max.  The forward records the winner's offset; the vjp (one thread per input pixel, no
+    atomics) sums the windows that recorded a pixel, so overlapping windows (stride < kernel) add up."""
+    xv = x.values
+    shape = tuple(xv.shape)
+    values, idx = da.max_pool2d(xv, kernel, stride, padding, route=route)
+    return build_unary_ops_tensor(
+        x, lambda g: da.max_pool2d_bwd(da.asarray(g)._as_float(values.dtype)._broadcast_to(values.shape), idx, shape,
+                                       kernel, stride, padding, route=route), values)
+
+
 def _softmax_head(logits, labels):
     """The classifier head as ONE launch when the logits are still pending (dense_(lazy=True)) and the shapes are the ones
     tnn_mlp_head_tick takes: last Dense forward (core/layers.py:49) + whole-batch softmax NLL (core/losses.py:24-32) + the last
@@ -726,3 +808,15 @@ def flatten(obj):
 
 def clip(obj, min=None, max=None):
     return clip_(as_tensor(obj), min, max)
+
+
+def conv2d(obj, w, b=None, stride=1, padding=0, dilation=1, groups=1):
+    """not in the reference: see conv2d_ (dilation / groups other than 1 raise ValueError)"""
+    if dilation not in (1, (1, 1)) or groups != 1:
+        raise ValueError("conv2d: dilation and groups are not supported")
+    return conv2d_(as_tensor(obj), as_tensor(w), None if b is None else as_tensor(b), stride, padding)
+
+
+def max_pool2d(obj, kernel, stride=None, padding=0):
+    """not in the reference: see max_pool2d_"""
+    return max_pool2d_(as_tensor(obj), kernel, stride=stride, padding=padding)

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import _lib
 from . import batching as _bt
+from . import conv as _cv
 from . import indexing as _ix
 from ._lib import F32, F64, I64, U8
 
@@ -1181,6 +1182,191 @@ def _np_dot(a, b):
         raise TypeError("np.dot with an N-d operand is not matmul (it contracts the last axis of a with the second-to-last "
                         "of b for every pair of stacks) and has no device implementation; use a @ b / np.matmul")
     return matmul(a, b)
+
+
+# ---------------------------------------------------------------------- kernels: convolution and pooling (csrc/tnn_conv.hip)
+CONV_ROUTE = None     # tests / probes: "native" or "composed" overrides the planner's choice (conv.py)
+CONV_FORM = 0         # tests / probes: TNN_CONV_FORM_* of the float32 launches (0: the library picks by channel count)
+CONV_SPLITS = None    # tests / probes: ranges of the filter gradient's contraction (None: conv.filter_splits)
+
+
+def _conv_operands(*arrays):
+    """The operands as dense arrays of one float dtype (None stays None)."""
+    present = [asarray(a) for a in arrays if a is not None]
+    dt = None
+    for a in present:
+        if a.dtype.kind == "f":
+            dt = a.dtype if dt is None or a.dtype.itemsize > dt.itemsize else dt
+    dt = dt or _default_float
+    return dt, [None if a is None else asarray(a)._as_float(dt)._contig() for a in arrays]
+
+
+def _conv_plan(x_shape, w_shape, b_shape, stride, padding, route):
+    return _cv.plan_conv2d(x_shape, w_shape, b_shape, stride, padding, native=_lib.get().has_conv,
+                           route=route or CONV_ROUTE)
+
+
+def _pad_hw(x, ph, pw, value=0.0):
+    if not ph and not pw:
+        return x
+    return _np_pad(x, ((0, 0), (0, 0), (ph, ph), (pw, pw)), constant_values=value)
+
+
+def conv2d(x, w, b=None, stride=1, padding=0, relu=False, route=None):
+    """y[n, f] = b[f] + sum_c x[n, c] (*) w[f, c]: 2-D cross-correlation of an NCHW batch with [F, C, KH, KW] filters, zero
+    padding, output extent (H + 2 p - KH) // s + 1.  relu=True: clip(., 0) in the same launch, the vjp mask z >= 0 kept in the
+    sign bit of zero (RELU_SIGN, as the fused Dense does).  One tnn_conv2d_fwd launch, or the tap loop of conv.py's composed
+    route (`route`, here and in the functions below: "native" / "composed" for this call, None = CONV_ROUTE / the planner)."""
+    dt, (x, w, b) = _conv_operands(x, w, b)
+    plan = _conv_plan(x.shape, w.shape, None if b is None else b.shape, stride, padding, route)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        if out.size:
+            _lib.get().conv2d_fwd(x._ptr, w._ptr, None if b is None else b._ptr, out._ptr, *plan.geometry(),
+                                  1 if relu else 0, out._code(), CONV_FORM)
+        if relu:
+            out._tag = RELU_SIGN
+        return out
+    n, ohw = plan.N, plan.OH * plan.OW
+    xp = _pad_hw(x, plan.ph, plan.pw)
+    acc = None
+    for kh, kw, rows, cols in _cv.taps(plan):
+        patch = xp[:, :, rows, cols].reshape(n, plan.C, ohw)
+        term = matmul(w[:, :, kh, kw], patch)                  # [F, C] @ [N, C, OH OW]
+        acc = term if acc is None else acc + term
+    out = acc.reshape(plan.out_shape)
+    if b is not None:
+        out = out + b.reshape(1, plan.F, 1, 1)
+    if relu:                                               # the same sign encoding: z < 0 -> -0.0, z >= 0 -> |z|
+        out = clip(out, 0.0) * (1.0 - 2.0 * (out < 0.0).astype(dt))
+        out._tag = RELU_SIGN
+    return out
+
+
+def conv2d_bwd_data(dy, w, x_shape, stride=1, padding=0, route=None):
+    """dx of conv2d for the gradient dy of its output: every input pixel collects dy * w over the taps that reach it."""
+    dt, (dy, w) = _conv_operands(dy, w)
+    plan = _conv_plan(x_shape, w.shape, None, stride, padding, route)
+    if dy.shape != plan.out_shape:
+        raise ValueError("conv2d_bwd_data: dy has shape %s, the output of this convolution %s" % (dy.shape, plan.out_shape))
+    if plan.route == "native":
+        dx = DeviceArray._new((plan.N, plan.C, plan.H, plan.W), dt)
+        if dx.size:
+            _lib.get().conv2d_bwd_data(dy._ptr, w._ptr, dx._ptr, *plan.geometry(), dx._code(), CONV_FORM)
+        return dx
+    dxp = zeros((plan.N, plan.C, plan.H + 2 * plan.ph, plan.W + 2 * plan.pw), dt)
+    dy3 = dy.reshape(plan.N, plan.F, plan.OH * plan.OW)
+    for kh, kw, rows, cols in _cv.taps(plan):
+        key = (slice(None), slice(None), rows, cols)
+        term = matmul(w[:, :, kh, kw].T, dy3).reshape(plan.N, plan.C, plan.OH, plan.OW)
+        dxp[key] = dxp[key] + term
+    return dxp[:, :, plan.ph:plan.ph + plan.H, plan.pw:plan.pw + plan.W]
+
+
+def _grad_dest(out, shape, dt):
+    """`out` when it is a dense array of this many elements and dtype that the launch may write (an arena view), else None."""
+    if (out is not None and isinstance(out, DeviceArray) and type(out) is DeviceArray and out.size == _prod(shape)
+            and out.dtype == dt and not out._t and out._hv is None and out._tag is not READONLY_COPY):
+        return out
+    return None
+
+
+def conv2d_bwd_filter(x, dy, w_shape, stride=1, padding=0, with_db=True, dw_out=None, db_out=None, route=None):
+    """(dw, db) of conv2d: dw[f, c, kh, kw] = sum over batch and output pixels of dy * the input under that tap, db[f] = the
+    sum of dy (None when with_db is false) — both from ONE tnn_conv2d_bwd_filter launch, whose split contraction is reduced
+    in a fixed order (run-to-run identical bits).  dw_out / db_out: dense arrays the results are written into."""
+    dt, (x, dy) = _conv_operands(x, dy)
+    plan = _conv_plan(x.shape, w_shape, None, stride, padding, route)
+    if dy.shape != plan.out_shape:
+        raise ValueError("conv2d_bwd_filter: dy has shape %s, the output of this convolution %s" % (dy.shape, plan.out_shape))
+    w_shape = (plan.F, plan.C, plan.KH, plan.KW)
+    if plan.route == "native":
+        lib = _lib.get()
+        dw = _grad_dest(dw_out, w_shape, dt)
+        if dw is None:
+            dw = DeviceArray._new(w_shape, dt)
+        db = _grad_dest(db_out, (plan.F,), dt) if with_db else None
+        if db is None and with_db:
+            db = DeviceArray._new((plan.F,), dt)
+        splits = 1
+        if dt == np.float32 and plan.N:
+            splits = CONV_SPLITS if CONV_SPLITS is not None else _cv.filter_splits(plan, with_db, CONV_FORM)
+        nbytes = _cv.filter_workspace_bytes(plan, with_db, CONV_FORM, splits)
+        ws = None
+        if nbytes:
+            ws = DeviceArray._new((nbytes // 4,), np.float32)
+            counters = (nbytes - splits * _cv.tiles(plan.F, plan.C * plan.KH * plan.KW + int(with_db), CONV_FORM)
+                        * _cv.TILE_ELEMS * 4) // 4
+            lib.fill(ws._ptr, 0.0, counters, F32)              # the arrival counters start at zero (and end there)
+        lib.conv2d_bwd_filter(x._ptr, dy._ptr, dw._ptr, None if db is None else db._ptr, None if ws is None else ws._ptr,
+                              nbytes, *plan.geometry(), dw._code(), CONV_FORM, splits)
+        return dw, db
+    xp = _pad_hw(x, plan.ph, plan.pw)
+    dy3 = dy.reshape(plan.N, plan.F, plan.OH * plan.OW)
+    dw = zeros(w_shape, dt)
+    for kh, kw, rows, cols in _cv.taps(plan):
+        patch = xp[:, :, rows, cols].reshape(plan.N, plan.C, plan.OH * plan.OW)
+        dw[:, :, kh, kw] = matmul(dy3, patch, swap_b=True).sum(axis=0)       # [N, F, C] summed over the batch
+    db = dy.sum(axis=(0, 2, 3)) if with_db else None
+    return dw, db
+
+
+def _pool_offsets(plan, kh, kw, dt):
+    """[OH, OW] flat offsets h * W + w of tap (kh, kw) of every window (taps in the padding get offsets outside the plane's
+    rows or columns; they hold -inf and are never recorded)."""
+    h = np.arange(plan.OH) * plan.sh - plan.ph + kh
+    w = np.arange(plan.OW) * plan.sw - plan.pw + kw
+    return asarray((h[:, None] * plan.W + w[None, :]).astype(dt))
+
+
+def max_pool2d(x, kernel, stride=None, padding=0, route=None):
+    """(y, idx): the maximum of every kernel window of every [H, W] plane (padding = -inf) and the flat offset h * W + w of
+    the FIRST maximum of the window in row-major order inside its input plane — numpy's argmax rule.  NaN propagates like
+    max.  Native: int32 offsets from tnn_maxpool2d_fwd; composed: a fold of `maximum` over the shifted slices in row-major
+    tap order (ties stay with the earlier tap), offsets as whole numbers of x's dtype."""
+    x = asarray(x)
+    dt, (x,) = _conv_operands(x)
+    plan = _cv.plan_pool2d(x.shape, kernel, stride, padding, native=_lib.get().has_conv, route=route or CONV_ROUTE)
+    if plan.route == "native":
+        y = DeviceArray._new(plan.out_shape, dt)
+        idx = DeviceArray._new(plan.out_shape, np.int32)
+        if y.size:
+            _lib.get().maxpool2d_fwd(x._ptr, y._ptr, idx._ptr, *plan.geometry(), y._code())
+        return y, idx
+    xp = _pad_hw(x, plan.ph, plan.pw, -math.inf)
+    best = idx = None
+    for kh, kw, rows, cols in _cv.taps(plan):
+        v = xp[:, :, rows, cols]
+        off = _pool_offsets(plan, kh, kw, dt)
+        if best is None:
+            best, idx = v, off._broadcast_to(plan.out_shape)
+        else:
+            idx = _np_where(v > best, off, idx)
+            best = maximum(best, v)
+    return best, idx
+
+
+def max_pool2d_bwd(dy, idx, x_shape, kernel, stride=None, padding=0, route=None):
+    """dx of max_pool2d: every window's gradient goes, whole, to the pixel whose offset it recorded; a pixel recorded by several
+    (overlapping) windows receives their sum."""
+    dt, (dy,) = _conv_operands(dy)
+    plan = _cv.plan_pool2d(x_shape, kernel, stride, padding, native=_lib.get().has_conv, route=route or CONV_ROUTE)
+    if dy.shape != plan.out_shape or tuple(idx.shape) != plan.out_shape:
+        raise ValueError("max_pool2d_bwd: dy %s / idx %s do not match the pooled shape %s" % (dy.shape, idx.shape, plan.out_shape))
+    if plan.route == "native":
+        if idx.dtype != np.int32:
+            raise TypeError("max_pool2d_bwd: the native route takes the int32 offsets of its own forward")
+        dx = DeviceArray._new((plan.N, plan.C, plan.H, plan.W), dt)
+        if dx.size:
+            _lib.get().maxpool2d_bwd(dy._ptr, idx._ptr, dx._ptr, *plan.geometry(), dx._code())
+        return dx
+    if idx.dtype.kind != "f":
+        raise TypeError("max_pool2d_bwd: the composed route takes the offsets of its own forward")
+    dxp = zeros((plan.N, plan.C, plan.H + 2 * plan.ph, plan.W + 2 * plan.pw), dt)
+    for kh, kw, rows, cols in _cv.taps(plan):
+        key = (slice(None), slice(None), rows, cols)
+        dxp[key] = dxp[key] + mul_mask(dy, idx == _pool_offsets(plan, kh, kw, idx.dtype))
+    return dxp[:, :, plan.ph:plan.ph + plan.H, plan.pw:plan.pw + plan.W]
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)
