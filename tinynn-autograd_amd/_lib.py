@@ -43,6 +43,10 @@ from ._conv_signatures import _CONV_SIGNATURES                # noqa: E402  (inc
 
 CONV_SYMBOLS = sorted(_CONV_SIGNATURES)
 
+from ._attn_signatures import _ATTN_SIGNATURES                # noqa: E402  (include/tnn_attn.h: libtnn_hip.so only)
+
+ATTN_SYMBOLS = sorted(_ATTN_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -97,9 +101,11 @@ class _Lib(object):
         # none, and the paths that need them raise there
         # and the strided-batched GEMM (include/tnn_bmm.h), likewise: under the twin device_array.matmul loops over tnn_gemm
         # and convolution / pooling (include/tnn_conv.h): under the twin device_array composes them from slices and products
+        # and fused attention (include/tnn_attn.h): under the twin device_array composes it from products, exp and sums
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
-                                    (_CONV_SIGNATURES, "tnn_conv.h", "convolution")):
+                                    (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
+                                    (_ATTN_SIGNATURES, "tnn_attn.h", "attention")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -112,6 +118,7 @@ class _Lib(object):
                 setattr(self, name[4:], self._wrap(name, fn))
         self.has_bmm = hasattr(self.cdll, "tnn_gemm_batched")
         self.has_conv = hasattr(self.cdll, "tnn_conv2d_fwd")
+        self.has_attn = hasattr(self.cdll, "tnn_attn_fwd")
 
     @staticmethod
     def _absent(name, what):

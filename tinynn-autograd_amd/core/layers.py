@@ -6,7 +6,8 @@ node plus a broadcast-add node (`fused=False` restores the literal `inputs @ w +
 `Sigmoid` is a single fused kernel (the reference's raises on a Tensor).  The parameter dict order is
 "w" then "b" (core/layers.py:35): the optimizer's flatten order and the trainer's arena layout depend on it.
 
-Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / ops.max_pool2d_), enough for a LeNet.
+Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / ops.max_pool2d_), enough for a LeNet, and
+`MultiHeadAttention` (ops.attention_), whose parameter dict order is MHA_PARAM_ORDER.
 """
 
 from . import ops
@@ -14,6 +15,7 @@ from .initializer import XavierUniformInit
 from .initializer import ZerosInit
 
 PARAM_ORDER = ("w", "b")
+MHA_PARAM_ORDER = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")
 
 
 class Layer(object):
@@ -184,3 +186,58 @@ class Flatten(Layer):
     def forward(self, inputs):
         self.inputs = inputs
         return ops.reshape(inputs, (int(inputs.shape[0]), -1))
+
+
+class MultiHeadAttention(Layer):
+    """Multi-head self-attention over [B, T, E] inputs: three projections to queries, keys and values, `num_heads` heads of
+    E / num_heads dimensions each, softmax(q k^T / sqrt(E / num_heads)) v per head (causal=True: position i attends to
+    positions <= i), and an output projection back to E.
+
+    Parameters: "wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo" (w: [E, E], b: [1, E]), created and stored in THAT order —
+    the optimizer's flatten order depends on it, as it depends on "w" then "b" for Dense.  E (`num_in`) may be omitted and
+    is then read off the first batch.
+
+    Forward: [B T, E] rows -> three ops.dense_ -> [B, T, H, E / H] by reshape alone -> ops.attention_(layout="bthd"), whose
+    kernels take strides, so nothing is transposed -> [B T, E] -> the output projection -> [B, T, E].  `fused=False` runs
+    the attention on the composed route (batched products, exp and sums on the generic array operations)."""
+
+    def __init__(self, num_heads, num_in=None, causal=False, w_init=XavierUniformInit(), b_init=ZerosInit(), fused=True):
+        super().__init__("MultiHeadAttention")
+        num_heads = int(num_heads)
+        if num_heads < 1:
+            raise ValueError("MultiHeadAttention: num_heads must be >= 1, got %r" % (num_heads,))
+        self.num_heads, self.causal, self.fused = num_heads, bool(causal), fused
+        self.initializers = {name: (w_init if name[0] == "w" else b_init) for name in MHA_PARAM_ORDER}
+        self.shapes = {name: ([num_in, num_in] if name[0] == "w" else [1, num_in]) for name in MHA_PARAM_ORDER}
+        self.params = dict.fromkeys(MHA_PARAM_ORDER)
+        self.inputs = None
+        self.is_init = False
+        if num_in is not None:
+            self._init_parameters(int(num_in))
+
+    def _init_parameters(self, width):
+        if width % self.num_heads != 0:
+            raise ValueError("MultiHeadAttention: the input width %d is not a multiple of num_heads = %d"
+                             % (width, self.num_heads))
+        for name in MHA_PARAM_ORDER:                 # host RNG in parameter order: wq, wk, wv, wo draw, the biases do not
+            self.shapes[name] = [width, width] if name[0] == "w" else [1, width]
+            tensor = self.initializers[name](shape=self.shapes[name])
+            tensor.zero_grad()
+            self.params[name] = tensor
+        self.is_init = True
+
+    def forward(self, inputs):
+        if len(inputs.shape) != 3:
+            raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
+        b, t, e = (int(s) for s in inputs.shape)
+        if not self.is_init:
+            self._init_parameters(e)
+        if e != self.shapes["wq"][0]:
+            raise ValueError("MultiHeadAttention: the input width %d differs from the layer's %d" % (e, self.shapes["wq"][0]))
+        self.inputs = inputs
+        p, h = self.params, self.num_heads
+        rows = ops.reshape(inputs, (b * t, e))
+        q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h, e // h)) for n in "qkv")
+        att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=None if self.fused else "composed")
+        out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
+        return ops.reshape(out, (b, t, e))

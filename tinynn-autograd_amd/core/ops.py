@@ -8,7 +8,8 @@ reference expression each piece replaces.
 
 Extra fused nodes used by this package's own layers/losses (parity-tested against the generic chain):
 `dense_` (GEMM + bias epilogue), `sigmoid_`, `softmax_nll_` (whole-batch softmax NLL), `conv2d_` / `max_pool2d_` (NCHW
-convolution and max pooling, csrc/tnn_conv.hip; the reference has neither).
+convolution and max pooling, csrc/tnn_conv.hip; the reference has neither), `attention_` (fused scaled-dot-product attention,
+csrc/tnn_attn.hip; likewise).
 """
 
 import math
@@ -563,6 +564,74 @@ def max_pool2d_(x, kernel, stride=None, padding=0, route=None):
                                        kernel, stride, padding, route=route), values)
 
 
+class _AttnVjp(object):
+    """The vjps of one ops.attention_ node: `fused_vjp` for Tensor.backward (only the gradients whose edges require them: dq
+    from ONE launch — which also produces delta — and dk + dv from ONE launch, written into arena views when they are lent),
+    per-edge forms for everybody else."""
+    __slots__ = ("q", "k", "v", "out", "lse", "causal", "scale", "layout", "route", "edges")
+
+    def __init__(self, q, k, v, out, lse, causal, scale, layout, route):
+        self.q, self.k, self.v = q, k, v                       # saved inputs by reference, read at backward time
+        self.out, self.lse = out, lse                          # the output and the per-row log-sum-exp: p is recomputed
+        self.causal, self.scale, self.layout, self.route = causal, scale, layout, route
+        self.edges = ()
+
+    def _opts(self):
+        return dict(causal=self.causal, scale=self.scale, layout=self.layout, route=self.route)
+
+    def _bwd_q(self, g, need_dq, dq_out=None):
+        return da.attention_bwd_q(self.q.values, self.k.values, self.v.values, self.out, g, self.lse, need_dq=need_dq,
+                                  dq_out=dq_out, **self._opts())
+
+    def _bwd_kv(self, g, delta, need_dk, need_dv, dk_out=None, dv_out=None):
+        return da.attention_bwd_kv(self.q.values, self.k.values, self.v.values, g, self.lse, delta, need_dk=need_dk,
+                                   need_dv=need_dv, dk_out=dk_out, dv_out=dv_out, **self._opts())
+
+    def d_q(self, g):
+        return self._bwd_q(g, True)[0]
+
+    def d_k(self, g):
+        return self._bwd_kv(g, self._bwd_q(g, False)[1], True, False)[0]
+
+    def d_v(self, g):
+        return self._bwd_kv(g, self._bwd_q(g, False)[1], False, True)[1]
+
+    def fused_vjp(self, g, homes):
+        edges = self.edges
+        home = dict(zip(edges, homes))
+        res = {}
+        kv = "k" in edges or "v" in edges
+        dq, delta = self._bwd_q(g, "q" in edges, home.get("q"))
+        if "q" in edges:
+            res["q"] = dq
+        if kv:
+            res["k"], res["v"] = self._bwd_kv(g, delta, "k" in edges, "v" in edges, home.get("k"), home.get("v"))
+        return [res[name] for name in edges]
+
+
+def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **unknown):
+    """Scaled-dot-product attention node: softmax(scale q k^T) v, softmax over the key axis, scale = 1 / sqrt(D) by default.
+
+    layout "bhtd": q [..., Tq, D], k [..., Tk, D], v [..., Tk, Dv] -> [..., Tq, Dv] (identical leading dimensions, no
+    broadcasting); layout "bthd": q [B, Tq, H, D], k [B, Tk, H, D], v [B, Tk, H, Dv] -> [B, Tq, H, Dv], what a [B T, H D]
+    projection reshapes to for free.  causal=True keeps key j for query i iff j <= i (top-left aligned for any Tq, Tk).
+    float32 and float64; other dtypes are promoted the way matmul promotes them.  Out of scope: arbitrary or padding masks,
+    dropout, bf16 — unknown keyword arguments raise.
+
+    Forward is ONE tnn_attn_fwd launch (online softmax on MFMA; the [Tq, Tk] scores never reach memory) that also keeps the
+    per-row log-sum-exp.  Backward recomputes the probabilities from it: dq from one launch (not computed when q does not
+    require a gradient), dk + dv from one launch.  Under the CPU test twin, beyond head dimension 128 and with
+    route="composed" (or device_array.ATTN_ROUTE) the same mathematics runs on batched products, exp and sums."""
+    if unknown:
+        raise TypeError("attention_: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
+    out, lse = da.attention(q.values, k.values, v.values, causal=causal, scale=scale, layout=layout, route=route)
+    ctx = _AttnVjp(q, k, v, out, lse, causal, scale, layout, route)
+    node = _make_node(q.__class__, out, [(q, ctx.d_q), (k, ctx.d_k), (v, ctx.d_v)])
+    ctx.edges = [name for name, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
 def _softmax_head(logits, labels):
     """The classifier head as ONE launch when the logits are still pending (dense_(lazy=True)) and the shapes are the ones
     tnn_mlp_head_tick takes: last Dense forward (core/layers.py:49) + whole-batch softmax NLL (core/losses.py:24-32) + the last
@@ -820,3 +889,10 @@ def conv2d(obj, w, b=None, stride=1, padding=0, dilation=1, groups=1):
 def max_pool2d(obj, kernel, stride=None, padding=0):
     """not in the reference: see max_pool2d_"""
     return max_pool2d_(as_tensor(obj), kernel, stride=stride, padding=padding)
+
+
+def attention(obj, k, v, causal=False, scale=None, layout="bhtd", **unknown):
+    """not in the reference: see attention_ (masks, dropout and bf16 are out of scope: unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("attention: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
+    return attention_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, layout=layout)

@@ -26,6 +26,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from . import attention as _at
 from . import batching as _bt
 from . import conv as _cv
 from . import indexing as _ix
@@ -94,6 +95,7 @@ def trim_cache():
     """Return every cached buffer to the native pool (tests that audit tnn_pool_stats, shutdown)."""
     global _cache_bytes
     lib = _lib._lib
+    _ATTN_MASKS.clear()               # the composed attention route's causal masks: device buffers like any other
     for cls, ptrs in _cache.items():
         for ptr in ptrs:
             if lib is not None:
@@ -1367,6 +1369,175 @@ def max_pool2d_bwd(dy, idx, x_shape, kernel, stride=None, padding=0, route=None)
         key = (slice(None), slice(None), rows, cols)
         dxp[key] = dxp[key] + mul_mask(dy, idx == _pool_offsets(plan, kh, kw, idx.dtype))
     return dxp[:, :, plan.ph:plan.ph + plan.H, plan.pw:plan.pw + plan.W]
+
+
+# ---------------------------------------------------------------------- kernels: fused attention (csrc/tnn_attn.hip)
+ATTN_ROUTE = None     # tests / probes: "native" or "composed" overrides the planner's choice (attention.py)
+_ATTN_MASKS = {}      # (Tq, Tk, dtype) -> [Tq, Tk] array, 0 where key j <= query i and -inf above the diagonal
+_ATTN_MASKS_MAX = 8   # masks kept (4 MiB each at T = 1024); trim_cache() drops them all
+
+
+def _attn_operands(*arrays):
+    """The operands as dense arrays of one float dtype, promoted the way matmul promotes (_float_result_dtype)."""
+    arrays = [asarray(a) for a in arrays]
+    cands = [a.dtype for a in arrays if a._hv is None and a.dtype.kind == "f"]
+    dt = _default_float if not cands else np.dtype(np.float64) if np.dtype(np.float64) in cands else np.dtype(np.float32)
+    return dt, [a._as_float(dt)._contig() for a in arrays]
+
+
+def _attn_plan(q, k, v, causal, scale, layout, route):
+    return _at.plan_attention(q.shape, k.shape, v.shape, causal, scale, layout, native=_lib.get().has_attn,
+                              route=route or ATTN_ROUTE)
+
+
+def _attn_mask(tq, tk, dt):
+    key = (tq, tk, dt)
+    m = _ATTN_MASKS.get(key)
+    if m is None:
+        if _lib.capturing:
+            raise RuntimeError("attention (composed route): the causal mask of a new (Tq, Tk, dtype) is uploaded from the "
+                               "host, which a graph capture cannot do; run one step outside the capture first")
+        host = np.zeros((tq, tk), dtype=dt)
+        host[np.triu_indices(tq, 1, tk)] = -np.inf
+        if len(_ATTN_MASKS) >= _ATTN_MASKS_MAX:
+            _ATTN_MASKS.clear()
+        m = _ATTN_MASKS[key] = asarray(host, dtype=dt)
+    return m
+
+
+def _attn3(x, plan, rows, width):
+    """[B H, rows, width] view of an operand (layout "bthd": a transposed copy)."""
+    if plan.layout == "bthd":
+        x = x.transpose(0, 2, 1, 3)
+    return x.reshape(plan.B * plan.H, rows, width)
+
+
+def _attn_from3(x3, plan, rows, width):
+    if plan.layout == "bthd":
+        return x3.reshape(plan.B, plan.H, rows, width).transpose(0, 2, 1, 3)
+    return x3.reshape(plan.out_shape[:-2] + (rows, width))
+
+
+def _attn_scores(q, k, plan):
+    """scale q k^T (+ the causal mask) as [B H, Tq, Tk] — the composed route's score array."""
+    s = matmul(_attn3(q, plan, plan.Tq, plan.D), _attn3(k, plan, plan.Tk, plan.D), swap_b=True) * plan.scale
+    if plan.causal:
+        s = s + _attn_mask(plan.Tq, plan.Tk, s.dtype)
+    return s
+
+
+def _attn_dest(out, shape, dt):
+    """`out` when the launch may write a gradient of this shape into it (a lent arena view of exactly that shape: the
+    kernels address it with the operand's strides), else None."""
+    out = _grad_dest(out, shape, dt)
+    return out if out is not None and tuple(out.shape) == tuple(shape) else None
+
+
+def _attn_empty(plan, dt):
+    return zeros(plan.out_shape, dt), zeros(plan.lse_shape, dt)
+
+
+def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None):
+    """(o, lse): o = softmax(scale q k^T) v over the key axis and the per-row log-sum-exp of the scaled scores (what the
+    backward recomputes the probabilities from).  Layouts, the causal rule and the routes: attention.py.  Native: ONE
+    tnn_attn_fwd launch, the scores never reach memory; composed: two batched products, max-subtract, exp, sum, divide."""
+    dt, (q, k, v) = _attn_operands(q, k, v)
+    plan = _attn_plan(q, k, v, causal, scale, layout, route)
+    if plan.empty():
+        return _attn_empty(plan, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        lse = DeviceArray._new(plan.lse_shape, dt)
+        _lib.get().attn_fwd(q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr, *plan.geometry(),
+                            _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
+        return out, lse
+    s = _attn_scores(q, k, plan)
+    m = s.max(axis=-1, keepdims=True)
+    e = exp(s - m)
+    l = e.sum(axis=-1, keepdims=True)
+    o3 = matmul(e / l, _attn3(v, plan, plan.Tk, plan.Dv))
+    return _attn_from3(o3, plan, plan.Tq, plan.Dv), (m + log(l)).reshape(plan.lse_shape)
+
+
+def _attn_bwd_check(plan, o_shape, lse, what):
+    if tuple(o_shape) != plan.out_shape or tuple(lse.shape) != plan.lse_shape:
+        raise ValueError("%s: do / o %s and lse %s do not match the output %s and row statistics %s of this attention"
+                         % (what, tuple(o_shape), tuple(lse.shape), plan.out_shape, plan.lse_shape))
+
+
+def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd", route=None, need_dq=True, dq_out=None):
+    """(dq, delta) for the gradient `do` of attention's output: delta[i] = sum_c do[i, c] o[i, c] (what attention_bwd_kv
+    reads) and dq = scale dS k with dS = p (dP - delta), dP = do v^T, p recomputed from lse.  need_dq=False: dq is None and
+    only delta is produced (native: the key loop is skipped).  dq_out: a dense array the result is written into."""
+    dt, (q, k, v, o, do, lse) = _attn_operands(q, k, v, o, do, lse)
+    plan = _attn_plan(q, k, v, causal, scale, layout, route)
+    _attn_bwd_check(plan, o.shape, lse, "attention_bwd_q")
+    if do.shape != plan.out_shape:
+        do = do._broadcast_to(plan.out_shape)
+    if plan.empty():
+        return (zeros(q.shape, dt) if need_dq else None), zeros(plan.lse_shape, dt)
+    if plan.route == "native":
+        dq = None
+        if need_dq:
+            dq = _attn_dest(dq_out, q.shape, dt)
+            if dq is None:
+                dq = DeviceArray._new(q.shape, dt)
+        delta = DeviceArray._new(plan.lse_shape, dt)
+        _lib.get().attn_bwd_q(q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, None if dq is None else dq._ptr, delta._ptr,
+                              *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale,
+                              int(plan.causal), delta._code())
+        return dq, delta
+    do3 = _attn3(do, plan, plan.Tq, plan.Dv)
+    delta3 = (do3 * _attn3(o, plan, plan.Tq, plan.Dv)).sum(axis=-1, keepdims=True)
+    dq = None
+    if need_dq:
+        p = exp(_attn_scores(q, k, plan) - lse.reshape(plan.B * plan.H, plan.Tq, 1))
+        ds = p * (matmul(do3, _attn3(v, plan, plan.Tk, plan.Dv), swap_b=True) - delta3)
+        dq = _attn_from3(matmul(ds, _attn3(k, plan, plan.Tk, plan.D)) * plan.scale, plan, plan.Tq, plan.D)
+    return dq, delta3.reshape(plan.lse_shape)
+
+
+def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="bhtd", route=None, need_dk=True,
+                     need_dv=True, dk_out=None, dv_out=None):
+    """(dk, dv): dv = p^T do and dk = scale dS^T q from ONE launch, with the delta attention_bwd_q produced (on the native
+    route the launch must follow that call).  need_dk / need_dv = False: that product is skipped and None returned.  A key
+    that no query sees (causal, Tk > Tq) gets exact zeros.  dk_out / dv_out: dense arrays the results are written into."""
+    dt, (q, k, v, do, lse, delta) = _attn_operands(q, k, v, do, lse, delta)
+    plan = _attn_plan(q, k, v, causal, scale, layout, route)
+    if tuple(lse.shape) != plan.lse_shape or tuple(delta.shape) != plan.lse_shape:
+        raise ValueError("attention_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
+                         % (tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
+    if do.shape != plan.out_shape:
+        do = do._broadcast_to(plan.out_shape)
+    if not need_dk and not need_dv:
+        return None, None
+    if plan.empty():
+        return (zeros(k.shape, dt) if need_dk else None), (zeros(v.shape, dt) if need_dv else None)
+    if plan.route == "native":
+        dk = dv = None
+        if need_dk:
+            dk = _attn_dest(dk_out, k.shape, dt)
+            if dk is None:
+                dk = DeviceArray._new(k.shape, dt)
+        if need_dv:
+            dv = _attn_dest(dv_out, v.shape, dt)
+            if dv is None:
+                dv = DeviceArray._new(v.shape, dt)
+        _lib.get().attn_bwd_kv(q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, None if dk is None else dk._ptr,
+                               None if dv is None else dv._ptr, *plan.geometry(),
+                               _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale, int(plan.causal),
+                               lse._code())
+        return dk, dv
+    rows = plan.B * plan.H
+    do3 = _attn3(do, plan, plan.Tq, plan.Dv)
+    p = exp(_attn_scores(q, k, plan) - lse.reshape(rows, plan.Tq, 1))
+    dk = dv = None
+    if need_dv:
+        dv = _attn_from3(matmul(p, do3, swap_a=True), plan, plan.Tk, plan.Dv)
+    if need_dk:
+        ds = p * (matmul(do3, _attn3(v, plan, plan.Tk, plan.Dv), swap_b=True) - delta.reshape(rows, plan.Tq, 1))
+        dk = _attn_from3(matmul(ds, _attn3(q, plan, plan.Tq, plan.D), swap_a=True) * plan.scale, plan, plan.Tk, plan.D)
+    return dk, dv
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)
