@@ -47,6 +47,10 @@ from ._attn_signatures import _ATTN_SIGNATURES                # noqa: E402  (inc
 
 ATTN_SYMBOLS = sorted(_ATTN_SIGNATURES)
 
+from ._norm_signatures import _NORM_SIGNATURES                # noqa: E402  (include/tnn_norm.h: libtnn_hip.so only)
+
+NORM_SYMBOLS = sorted(_NORM_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -102,10 +106,13 @@ class _Lib(object):
         # and the strided-batched GEMM (include/tnn_bmm.h), likewise: under the twin device_array.matmul loops over tnn_gemm
         # and convolution / pooling (include/tnn_conv.h): under the twin device_array composes them from slices and products
         # and fused attention (include/tnn_attn.h): under the twin device_array composes it from products, exp and sums
+        # and layer norm, RMS norm and GELU (include/tnn_norm.h): under the twin device_array composes them from sums,
+        # products, sqrt and tanh (the exact GELU has no composed form and raises there)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
-                                    (_ATTN_SIGNATURES, "tnn_attn.h", "attention")):
+                                    (_ATTN_SIGNATURES, "tnn_attn.h", "attention"),
+                                    (_NORM_SIGNATURES, "tnn_norm.h", "normalisation")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -119,6 +126,7 @@ class _Lib(object):
         self.has_bmm = hasattr(self.cdll, "tnn_gemm_batched")
         self.has_conv = hasattr(self.cdll, "tnn_conv2d_fwd")
         self.has_attn = hasattr(self.cdll, "tnn_attn_fwd")
+        self.has_norm = hasattr(self.cdll, "tnn_norm_fwd")
 
     @staticmethod
     def _absent(name, what):

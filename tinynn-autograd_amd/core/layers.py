@@ -7,15 +7,21 @@ node plus a broadcast-add node (`fused=False` restores the literal `inputs @ w +
 "w" then "b" (core/layers.py:35): the optimizer's flatten order and the trainer's arena layout depend on it.
 
 Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / ops.max_pool2d_), enough for a LeNet, and
-`MultiHeadAttention` (ops.attention_), whose parameter dict order is MHA_PARAM_ORDER.
+`MultiHeadAttention` (ops.attention_), whose parameter dict order is MHA_PARAM_ORDER; `LayerNorm` / `RMSNorm`
+(ops.layer_norm_ / ops.rms_norm_; "gamma" then "beta"), `GELU`, and `TransformerBlock`, a pre-norm block built from them whose
+ONE flat parameter dict has the order BLOCK_PARAM_ORDER.
 """
 
 from . import ops
+from .initializer import ConstantInit
 from .initializer import XavierUniformInit
 from .initializer import ZerosInit
 
 PARAM_ORDER = ("w", "b")
 MHA_PARAM_ORDER = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")
+NORM_PARAM_ORDER = ("gamma", "beta")
+BLOCK_PARAM_ORDER = (("ln1.gamma", "ln1.beta") + tuple("attn." + name for name in MHA_PARAM_ORDER)
+                     + ("ln2.gamma", "ln2.beta", "fc1.w", "fc1.b", "fc2.w", "fc2.b"))
 
 
 class Layer(object):
@@ -241,3 +247,127 @@ class MultiHeadAttention(Layer):
         att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=None if self.fused else "composed")
         out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
         return ops.reshape(out, (b, t, e))
+
+
+class LayerNorm(Layer):
+    """Layer normalisation over the LAST axis of inputs of any rank >= 1: (x - mean) / sqrt(var + eps) * gamma + beta with
+    the biased variance.  Parameters: "gamma" (ones) then "beta" (zeros), shape [1, N], created and stored in THAT order.  N
+    (`num_in`) may be omitted and is then read off the first batch's last axis.  `fused=False` runs the composed route (sums,
+    products and a square root on the generic array operations)."""
+    KIND, NAMES = "layer", NORM_PARAM_ORDER
+
+    def __init__(self, num_in=None, eps=1e-5, fused=True):
+        super().__init__(type(self).__name__)
+        self.eps, self.fused = float(eps), fused
+        self.initializers = {"gamma": ConstantInit(1.0), "beta": ZerosInit()}
+        self.shapes = {name: [1, num_in] for name in self.NAMES}
+        self.params = dict.fromkeys(self.NAMES)
+        self.inputs = None
+        self.is_init = False
+        if num_in is not None:
+            self._init_parameters(int(num_in))
+
+    def _init_parameters(self, width):
+        if width < 1:
+            raise ValueError("%s: the normalised axis must hold at least one element, got %d" % (self.name, width))
+        for name in self.NAMES:                      # (constants: no draw from the host RNG)
+            self.shapes[name] = [1, width]
+            tensor = self.initializers[name](shape=self.shapes[name])
+            tensor.zero_grad()
+            self.params[name] = tensor
+        self.is_init = True
+
+    def forward(self, inputs):
+        if len(inputs.shape) < 1:
+            raise ValueError("%s: the input needs at least one axis, got a scalar" % self.name)
+        width = int(inputs.shape[-1])
+        if not self.is_init:
+            self._init_parameters(width)
+        if width != self.shapes["gamma"][1]:
+            raise ValueError("%s: the input width %d differs from the layer's %d" % (self.name, width, self.shapes["gamma"][1]))
+        self.inputs = inputs
+        route = None if self.fused else "composed"
+        if self.KIND == "layer":
+            return ops.layer_norm_(inputs, self.params["gamma"], self.params["beta"], eps=self.eps, route=route)
+        return ops.rms_norm_(inputs, self.params["gamma"], eps=self.eps, route=route)
+
+
+class RMSNorm(LayerNorm):
+    """RMS normalisation over the LAST axis: x / sqrt(mean(x^2) + eps) * gamma.  One parameter, "gamma" (ones, [1, N]);
+    otherwise as LayerNorm."""
+    KIND, NAMES = "rms", ("gamma",)
+
+
+class GELU(Activation):
+    """GELU.  approximate="none": 0.5 x (1 + erf(x / sqrt(2))) — needs the native library; "tanh": the tanh form, which also
+    has a composed route."""
+
+    def __init__(self, approximate="none"):
+        super().__init__("GELU")
+        from ..norm import gelu_form
+        self.approximate = gelu_form(approximate)
+
+    def func(self, x):
+        return ops.gelu_(x, approximate=self.approximate)
+
+
+class TransformerBlock(Layer):
+    """Pre-norm transformer block over [B, T, E] inputs:
+
+        h   = x + MHA(LN1(x))                                  `num_heads` heads, causal=True: position i attends to <= i
+        out = h + GELU(LN2(h) W1 + b1) W2 + b2                 W1: [E, hidden], W2: [hidden, E]; hidden defaults to 4 E
+
+    GELU is the tanh form (the one with a composed route, so the block also runs without the native library).  The block owns
+    its parts (`ln1`, `attn`, `ln2`, `fc1`, `fc2`) and exposes ONE flat parameter dict in the order BLOCK_PARAM_ORDER:
+    ln1.gamma ln1.beta, attn.wq attn.bq attn.wk attn.bk attn.wv attn.bv attn.wo attn.bo, ln2.gamma ln2.beta, fc1.w fc1.b,
+    fc2.w fc2.b.  The parameters are created — and the host RNG is drawn from — in that order, so Net.get_parameters, the
+    optimizer's flatten order and Model.step see the block as one layer.  The dict is what counts: every forward hands its
+    tensors to the parts, so Net.set_parameters works unchanged.  E (`num_in`) may be omitted and is then read off the first
+    batch.  `fused=False` puts every part on its composed route."""
+
+    def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True):
+        super().__init__("TransformerBlock")
+        self.num_heads, self.hidden, self.causal, self.eps, self.fused = int(num_heads), hidden, bool(causal), float(eps), fused
+        if self.num_heads < 1:
+            raise ValueError("TransformerBlock: num_heads must be >= 1, got %r" % (num_heads,))
+        if hidden is not None and int(hidden) < 1:
+            raise ValueError("TransformerBlock: hidden must be >= 1, got %r" % (hidden,))
+        self.parts = None
+        self.params = dict.fromkeys(BLOCK_PARAM_ORDER)
+        self.inputs = None
+        self.is_init = False
+        if num_in is not None:
+            self._init_parameters(int(num_in))
+
+    def _init_parameters(self, width):
+        hidden = 4 * width if self.hidden is None else int(self.hidden)
+        # created in BLOCK_PARAM_ORDER: each part draws from the host RNG as it is built
+        parts = {}
+        parts["ln1"] = LayerNorm(width, eps=self.eps, fused=self.fused)
+        parts["attn"] = MultiHeadAttention(self.num_heads, num_in=width, causal=self.causal, fused=self.fused)
+        parts["ln2"] = LayerNorm(width, eps=self.eps, fused=self.fused)
+        parts["fc1"] = Dense(hidden, num_in=width, fused=self.fused)
+        parts["fc2"] = Dense(width, num_in=hidden, fused=self.fused)
+        self.parts, self.hidden, self.width = parts, hidden, width
+        for key in BLOCK_PARAM_ORDER:
+            part, name = key.split(".")
+            self.params[key] = parts[part].params[name]
+        self.is_init = True
+
+    def forward(self, inputs):
+        if len(inputs.shape) != 3:
+            raise ValueError("TransformerBlock: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
+        b, t, e = (int(s) for s in inputs.shape)
+        if not self.is_init:
+            self._init_parameters(e)
+        if e != self.width:
+            raise ValueError("TransformerBlock: the input width %d differs from the block's %d" % (e, self.width))
+        self.inputs = inputs
+        parts = self.parts
+        for key in BLOCK_PARAM_ORDER:                # the flat dict is the truth (Net.set_parameters replaces its tensors)
+            part, name = key.split(".")
+            parts[part].params[name] = self.params[key]
+        h = inputs + parts["attn"].forward(parts["ln1"].forward(inputs))
+        z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))
+        z = ops.gelu_(z, approximate="tanh", route=None if self.fused else "composed")
+        return h + ops.reshape(parts["fc2"].forward(z), (b, t, e))

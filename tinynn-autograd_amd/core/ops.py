@@ -9,7 +9,7 @@ reference expression each piece replaces.
 Extra fused nodes used by this package's own layers/losses (parity-tested against the generic chain):
 `dense_` (GEMM + bias epilogue), `sigmoid_`, `softmax_nll_` (whole-batch softmax NLL), `conv2d_` / `max_pool2d_` (NCHW
 convolution and max pooling, csrc/tnn_conv.hip; the reference has neither), `attention_` (fused scaled-dot-product attention,
-csrc/tnn_attn.hip; likewise).
+csrc/tnn_attn.hip; likewise), `layer_norm_` / `rms_norm_` / `gelu_` (csrc/tnn_norm.hip; likewise).
 """
 
 import math
@@ -632,6 +632,93 @@ def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **u
     return node
 
 
+class _NormVjp(object):
+    """The vjps of one ops.layer_norm_ / ops.rms_norm_ node: `fused_vjp` for Tensor.backward (ONE tnn_norm_bwd call for
+    whichever of x, gamma, beta require gradients, written into arena views when they are lent), per-edge forms for
+    everybody else."""
+    __slots__ = ("x", "gamma", "beta", "mean", "rstd", "kind", "route", "edges")
+
+    def __init__(self, x, gamma, beta, mean, rstd, kind, route):
+        self.x, self.gamma, self.beta = x, gamma, beta         # saved inputs by reference, read at backward time
+        self.mean, self.rstd = mean, rstd                      # the row statistics of the forward launch
+        self.kind, self.route = kind, route
+        self.edges = ()
+
+    def _bwd(self, g, names, home=None):
+        home = home or {}
+        dx, dgamma, dbeta = da.norm_bwd(self.x.values, g, None if self.gamma is None else self.gamma.values, self.mean,
+                                        self.rstd, kind=self.kind, route=self.route, need_dx="x" in names,
+                                        need_dgamma="gamma" in names, need_dbeta="beta" in names, dx_out=home.get("x"),
+                                        dgamma_out=home.get("gamma"), dbeta_out=home.get("beta"))
+        if dgamma is not None and dgamma is not home.get("gamma"):
+            dgamma = dgamma.reshape(self.gamma.shape)
+        if dbeta is not None and dbeta is not home.get("beta"):
+            dbeta = dbeta.reshape(self.beta.shape)
+        return {"x": dx, "gamma": dgamma, "beta": dbeta}
+
+    def d_x(self, g):
+        return self._bwd(g, ("x",))["x"]
+
+    def d_gamma(self, g):
+        return self._bwd(g, ("gamma",))["gamma"]
+
+    def d_beta(self, g):
+        return self._bwd(g, ("beta",))["beta"]
+
+    def fused_vjp(self, g, homes):
+        edges = self.edges
+        res = self._bwd(g, edges, dict(zip(edges, homes)))
+        return [res[name] for name in edges]
+
+
+def _norm_node(kind, x, gamma, beta, eps, route):
+    gv = None if gamma is None else gamma.values
+    if kind == "layer":
+        out, mean, rstd = da.layer_norm(x.values, gv, None if beta is None else beta.values, eps=eps, route=route)
+    else:
+        mean = None
+        out, rstd = da.rms_norm(x.values, gv, eps=eps, route=route)
+    ctx = _NormVjp(x, gamma, beta, mean, rstd, kind, route)
+    named = [("x", x, ctx.d_x), ("gamma", gamma, ctx.d_gamma), ("beta", beta, ctx.d_beta)]
+    node = _make_node(x.__class__, out, [(t, fn) for _, t, fn in named if t is not None])
+    ctx.edges = [name for name, t, _ in named if t is not None and t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
+def layer_norm_(x, gamma=None, beta=None, eps=1e-5, route=None, **unknown):
+    """Layer normalisation node over the LAST axis of x (any rank >= 1): (x - mean) * rstd * gamma + beta with the biased
+    variance and rstd = 1 / sqrt(var + eps).  gamma / beta: [N] or [1, N] tensors, or None (1 and 0).  float32 and float64.
+
+    Forward is ONE tnn_norm_fwd launch that reads x once, writes y once and keeps the row statistics; backward is ONE
+    tnn_norm_bwd call for whichever of x, gamma, beta require gradients (one pass over x and dy, the parameter gradients
+    reduced in a fixed order).  Under the CPU test twin, for rows wider than norm.BLOCK_MAX_N and with route="composed" (or
+    device_array.NORM_ROUTE) the same mathematics runs on sums, products and a square root.  Out of scope: bf16, a fused
+    residual add, dropout — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("layer_norm_: unsupported arguments %s" % sorted(unknown))
+    return _norm_node("layer", x, gamma, beta, eps, route)
+
+
+def rms_norm_(x, gamma=None, eps=1e-5, route=None, **unknown):
+    """RMS normalisation node over the LAST axis of x: x * rstd * gamma with rstd = 1 / sqrt(mean(x^2) + eps); no mean and no
+    beta.  Launches and routes: layer_norm_.  Unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("rms_norm_: unsupported arguments %s (RMS norm takes no beta)" % sorted(unknown))
+    return _norm_node("rms", x, gamma, None, eps, route)
+
+
+def gelu_(x, approximate="none", route=None, **unknown):
+    """GELU node.  approximate="none": 0.5 x (1 + erf(x / sqrt(2))); "tanh": 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715
+    x^3))).  One launch forward, one backward (the slope is recomputed from x).  The composed route (CPU test twin,
+    route="composed") exists for the tanh form only; the exact form raises there.  Unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("gelu_: unsupported arguments %s" % sorted(unknown))
+    xv = x.values
+    out = da.gelu(xv, approximate=approximate, route=route)
+    return build_unary_ops_tensor(x, lambda g: da.gelu_bwd(xv, g, approximate=approximate, route=route), out)
+
+
 def _softmax_head(logits, labels):
     """The classifier head as ONE launch when the logits are still pending (dense_(lazy=True)) and the shapes are the ones
     tnn_mlp_head_tick takes: last Dense forward (core/layers.py:49) + whole-batch softmax NLL (core/losses.py:24-32) + the last
@@ -896,3 +983,28 @@ def attention(obj, k, v, causal=False, scale=None, layout="bhtd", **unknown):
     if unknown:
         raise TypeError("attention: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
     return attention_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, layout=layout)
+
+
+def _opt_tensor(obj):
+    return None if obj is None else as_tensor(obj)
+
+
+def layer_norm(obj, gamma=None, beta=None, eps=1e-5, **unknown):
+    """not in the reference: see layer_norm_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("layer_norm: unsupported arguments %s" % sorted(unknown))
+    return layer_norm_(as_tensor(obj), _opt_tensor(gamma), _opt_tensor(beta), eps=eps)
+
+
+def rms_norm(obj, gamma=None, eps=1e-5, **unknown):
+    """not in the reference: see rms_norm_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("rms_norm: unsupported arguments %s (RMS norm takes no beta)" % sorted(unknown))
+    return rms_norm_(as_tensor(obj), _opt_tensor(gamma), eps=eps)
+
+
+def gelu(obj, approximate="none", **unknown):
+    """not in the reference: see gelu_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("gelu: unsupported arguments %s" % sorted(unknown))
+    return gelu_(as_tensor(obj), approximate=approximate)

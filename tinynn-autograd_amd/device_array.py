@@ -30,6 +30,7 @@ from . import attention as _at
 from . import batching as _bt
 from . import conv as _cv
 from . import indexing as _ix
+from . import norm as _nm
 from ._lib import F32, F64, I64, U8
 
 _CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int64): I64,
@@ -1538,6 +1539,162 @@ def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="
         ds = p * (matmul(do3, _attn3(v, plan, plan.Tk, plan.Dv), swap_b=True) - delta.reshape(rows, plan.Tq, 1))
         dk = _attn_from3(matmul(ds, _attn3(q, plan, plan.Tq, plan.D), swap_a=True) * plan.scale, plan, plan.Tk, plan.D)
     return dk, dv
+
+
+# ---------------------------------------------------------------------- kernels: layer norm, RMS norm, GELU (csrc/tnn_norm.hip)
+NORM_ROUTE = None     # tests / probes: "native" or "composed" overrides the planner's choice (norm.py)
+_GELU_C = math.sqrt(2.0 / math.pi)
+_GELU_A = 0.044715
+
+
+def _norm_operands(*arrays):
+    """The operands (None stays None) as dense arrays of one float dtype, promoted the way matmul promotes."""
+    there = [a for a in arrays if a is not None]
+    dt, dense = _attn_operands(*there)
+    dense = iter(dense)
+    return dt, [None if a is None else next(dense) for a in arrays]
+
+
+def _norm_plan(x, gamma, beta, kind, eps, route):
+    return _nm.plan_norm(x.shape, None if gamma is None else gamma.shape, None if beta is None else beta.shape, kind, eps,
+                         native=_lib.get().has_norm, route=route or NORM_ROUTE)
+
+
+def _ptr_of(a):
+    return None if a is None else a._ptr
+
+
+def _norm_fwd(x, gamma, beta, kind, eps, route):
+    dt, (x, gamma, beta) = _norm_operands(x, gamma, beta)
+    plan = _norm_plan(x, gamma, beta, kind, eps, route)
+    layer = kind == "layer"
+    if plan.empty():
+        return zeros(plan.x_shape, dt), (zeros(plan.stats_shape, dt) if layer else None), zeros(plan.stats_shape, dt)
+    if plan.route == "native":
+        y = DeviceArray._new(plan.x_shape, dt)
+        mean = DeviceArray._new(plan.stats_shape, dt) if layer else None
+        rstd = DeviceArray._new(plan.stats_shape, dt)
+        _lib.get().norm_fwd(x._ptr, _ptr_of(gamma), _ptr_of(beta), y._ptr, _ptr_of(mean), rstd._ptr, plan.M, plan.N,
+                            plan.eps, _nm.KIND_CODE[kind], y._code())
+        return y, mean, rstd
+    d = x.reshape(plan.M, plan.N)
+    mean = None
+    if layer:
+        mean = d.sum(axis=1, keepdims=True) / float(plan.N)
+        d = d - mean
+    rstd = 1.0 / sqrt((d * d).sum(axis=1, keepdims=True) / float(plan.N) + plan.eps)
+    y = d * rstd
+    if gamma is not None:
+        y = y * gamma.reshape(1, plan.N)
+    if beta is not None:
+        y = y + beta.reshape(1, plan.N)
+    return (y.reshape(plan.x_shape), None if mean is None else mean.reshape(plan.stats_shape),
+            rstd.reshape(plan.stats_shape))
+
+
+def layer_norm(x, gamma=None, beta=None, eps=1e-5, route=None):
+    """(y, mean, rstd): y = (x - mean) * rstd * gamma + beta over the LAST axis of x, with the biased variance (the mean of
+    the squared deviations from the mean, never E[x^2] - mean^2) and rstd = 1 / sqrt(var + eps); mean and rstd have shape
+    x.shape[:-1] and are what norm_bwd reads.  gamma / beta: [N] or [1, N] or None (1 and 0).  Native: ONE tnn_norm_fwd launch
+    that reads x once and writes y once; composed (norm.py: the CPU test twin, rows wider than BLOCK_MAX_N,
+    route="composed"): sums, products and a square root on the generic operations."""
+    return _norm_fwd(x, gamma, beta, "layer", eps, route)
+
+
+def rms_norm(x, gamma=None, eps=1e-5, route=None):
+    """(y, rstd): y = x * rstd * gamma with rstd = 1 / sqrt(mean(x^2) + eps) over the LAST axis of x.  Routes: layer_norm."""
+    y, _, rstd = _norm_fwd(x, gamma, None, "rms", eps, route)
+    return y, rstd
+
+
+def norm_bwd(x, dy, gamma, mean, rstd, kind="layer", route=None, need_dx=True, need_dgamma=True, need_dbeta=True,
+             dx_out=None, dgamma_out=None, dbeta_out=None):
+    """(dx, dgamma, dbeta) of layer_norm / rms_norm for the gradient `dy` of y, from the saved row statistics.  With
+    g = dy * gamma and xh = (x - mean) * rstd:  dx = rstd * (g - mean_N(g) - xh * mean_N(g xh)) (RMS norm: xh = x * rstd and
+    no mean_N(g) term), dgamma = sum over the rows of dy * xh, dbeta = the sum of dy.  need_* = False: that gradient is not
+    computed and None is returned (RMS norm has no dbeta at all).  dgamma / dbeta take gamma's shape ([N] without one).
+    Native: ONE tnn_norm_bwd call — one pass over x and dy; the parameter gradients are reduced in a fixed order, so
+    repeated calls give identical bits.  *_out: dense arrays the results are written into."""
+    layer = kind == "layer"
+    need_dbeta = need_dbeta and layer
+    dt, (x, dy, gamma, mean, rstd) = _norm_operands(x, dy, gamma, mean if layer else None, rstd)
+    plan = _norm_plan(x, gamma, None, kind, 0.0, route)
+    if tuple(rstd.shape) != plan.stats_shape or (layer and (mean is None or tuple(mean.shape) != plan.stats_shape)):
+        raise ValueError("norm_bwd: the row statistics must have shape %s, got mean %s and rstd %s"
+                         % (plan.stats_shape, None if mean is None else tuple(mean.shape), tuple(rstd.shape)))
+    if dy.shape != plan.x_shape:
+        dy = dy._broadcast_to(plan.x_shape)
+    if not (need_dx or need_dgamma or need_dbeta):
+        return None, None, None
+    p_shape = (plan.N,) if gamma is None else tuple(gamma.shape)
+    if plan.empty():
+        return ((zeros(plan.x_shape, dt) if need_dx else None), (zeros(p_shape, dt) if need_dgamma else None),
+                (zeros(p_shape, dt) if need_dbeta else None))
+    if plan.route == "native":
+        def dest(need, out, shape):
+            if not need:
+                return None
+            d = _grad_dest(out, shape, dt)
+            return DeviceArray._new(shape, dt) if d is None else d
+        dx, dgamma, dbeta = dest(need_dx, dx_out, plan.x_shape), dest(need_dgamma, dgamma_out, p_shape), \
+            dest(need_dbeta, dbeta_out, p_shape)
+        nbytes = plan.workspace_bytes(dt.itemsize, need_dgamma, need_dbeta)
+        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+        _lib.get().norm_bwd(x._ptr, dy._ptr, _ptr_of(gamma), _ptr_of(mean), rstd._ptr, _ptr_of(dx), _ptr_of(dgamma),
+                            _ptr_of(dbeta), _ptr_of(ws), nbytes, plan.M, plan.N, _nm.KIND_CODE[kind], x._code())
+        return dx, dgamma, dbeta
+    x2, dy2, r = x.reshape(plan.M, plan.N), dy.reshape(plan.M, plan.N), rstd.reshape(plan.M, 1)
+    xh = ((x2 - mean.reshape(plan.M, 1)) if layer else x2) * r
+    dx = dgamma = dbeta = None
+    if need_dx:
+        g = dy2 if gamma is None else dy2 * gamma.reshape(1, plan.N)
+        inner = g - xh * ((g * xh).sum(axis=1, keepdims=True) / float(plan.N))
+        if layer:
+            inner = inner - g.sum(axis=1, keepdims=True) / float(plan.N)
+        dx = (r * inner).reshape(plan.x_shape)
+    if need_dgamma:
+        dgamma = (dy2 * xh).sum(axis=0).reshape(p_shape)
+    if need_dbeta:
+        dbeta = dy2.sum(axis=0).reshape(p_shape)
+    return dx, dgamma, dbeta
+
+
+def _gelu_route(x, approximate, route):
+    return _nm.gelu_route(approximate, native=_lib.get().has_norm, route=route or NORM_ROUTE)
+
+
+def _gelu_inner(x):
+    """tanh(u) of the tanh form, u = sqrt(2 / pi) (x + 0.044715 x^3)."""
+    return tanh((x + (x * x * x) * _GELU_A) * _GELU_C)
+
+
+def gelu(x, approximate="none", route=None):
+    """GELU, elementwise.  approximate="none": 0.5 x (1 + erf(x / sqrt(2))); "tanh": 0.5 x (1 + tanh(sqrt(2 / pi)
+    (x + 0.044715 x^3))).  Native: ONE tnn_gelu_fwd launch.  The composed route (CPU test twin, route="composed") exists for
+    the tanh form only — there is no erf among the generic elementwise operations — and the exact form raises there."""
+    dt, (x,) = _norm_operands(x)
+    if _gelu_route(x, approximate, route) == "native":
+        y = DeviceArray._new(x.shape, dt)
+        _lib.get().gelu_fwd(x._ptr, y._ptr, x.size, _nm.GELU_CODE[approximate], y._code())
+        return y
+    return (x * 0.5) * (_gelu_inner(x) + 1.0)
+
+
+def gelu_bwd(x, dy, approximate="none", route=None, dx_out=None):
+    """dx = dy * gelu'(x), recomputed from x (ONE tnn_gelu_bwd launch on the native route).  dx_out: a dense array the result
+    is written into."""
+    dt, (x, dy) = _norm_operands(x, dy)
+    if dy.shape != x.shape:
+        dy = dy._broadcast_to(x.shape)
+    if _gelu_route(x, approximate, route) == "native":
+        dx = _grad_dest(dx_out, x.shape, dt)
+        if dx is None:
+            dx = DeviceArray._new(x.shape, dt)
+        _lib.get().gelu_bwd(x._ptr, dy._ptr, dx._ptr, x.size, _nm.GELU_CODE[approximate], dx._code())
+        return dx
+    t = _gelu_inner(x)
+    slope = (t + 1.0) * 0.5 + (x * 0.5) * (1.0 - t * t) * ((x * x) * (3.0 * _GELU_A) + 1.0) * _GELU_C
+    return dy * slope
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)
