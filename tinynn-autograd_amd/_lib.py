@@ -51,6 +51,10 @@ from ._norm_signatures import _NORM_SIGNATURES                # noqa: E402  (inc
 
 NORM_SYMBOLS = sorted(_NORM_SIGNATURES)
 
+from ._token_signatures import _TOKEN_SIGNATURES              # noqa: E402  (include/tnn_token.h: libtnn_hip.so only)
+
+TOKEN_SYMBOLS = sorted(_TOKEN_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -108,11 +112,14 @@ class _Lib(object):
         # and fused attention (include/tnn_attn.h): under the twin device_array composes it from products, exp and sums
         # and layer norm, RMS norm and GELU (include/tnn_norm.h): under the twin device_array composes them from sums,
         # products, sqrt and tanh (the exact GELU has no composed form and raises there)
+        # and the embedding and the per-row cross-entropy (include/tnn_token.h): under the twin device_array composes them
+        # from take, a one-hot product, max / exp / sum / log and the advanced-index gather
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
                                     (_ATTN_SIGNATURES, "tnn_attn.h", "attention"),
-                                    (_NORM_SIGNATURES, "tnn_norm.h", "normalisation")):
+                                    (_NORM_SIGNATURES, "tnn_norm.h", "normalisation"),
+                                    (_TOKEN_SIGNATURES, "tnn_token.h", "embedding / cross-entropy")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -127,6 +134,7 @@ class _Lib(object):
         self.has_conv = hasattr(self.cdll, "tnn_conv2d_fwd")
         self.has_attn = hasattr(self.cdll, "tnn_attn_fwd")
         self.has_norm = hasattr(self.cdll, "tnn_norm_fwd")
+        self.has_token = hasattr(self.cdll, "tnn_embed_fwd")
 
     @staticmethod
     def _absent(name, what):

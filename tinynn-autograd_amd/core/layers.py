@@ -9,17 +9,19 @@ node plus a broadcast-add node (`fused=False` restores the literal `inputs @ w +
 Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / ops.max_pool2d_), enough for a LeNet, and
 `MultiHeadAttention` (ops.attention_), whose parameter dict order is MHA_PARAM_ORDER; `LayerNorm` / `RMSNorm`
 (ops.layer_norm_ / ops.rms_norm_; "gamma" then "beta"), `GELU`, and `TransformerBlock`, a pre-norm block built from them whose
-ONE flat parameter dict has the order BLOCK_PARAM_ORDER.
+ONE flat parameter dict has the order BLOCK_PARAM_ORDER; `Embedding` (ops.embedding_; "tok" then "pos", EMBED_PARAM_ORDER).
 """
 
 from . import ops
 from .initializer import ConstantInit
+from .initializer import NormalInit
 from .initializer import XavierUniformInit
 from .initializer import ZerosInit
 
 PARAM_ORDER = ("w", "b")
 MHA_PARAM_ORDER = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo")
 NORM_PARAM_ORDER = ("gamma", "beta")
+EMBED_PARAM_ORDER = ("tok", "pos")
 BLOCK_PARAM_ORDER = (("ln1.gamma", "ln1.beta") + tuple("attn." + name for name in MHA_PARAM_ORDER)
                      + ("ln2.gamma", "ln2.beta", "fc1.w", "fc1.b", "fc2.w", "fc2.b"))
 
@@ -371,3 +373,41 @@ class TransformerBlock(Layer):
         z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))
         z = ops.gelu_(z, approximate="tanh", route=None if self.fused else "composed")
         return h + ops.reshape(parts["fc2"].forward(z), (b, t, e))
+
+
+class Embedding(Layer):
+    """Token embedding over integer ids [B, T] -> [B, T, width]: the rows "tok"[ids] of a [vocab, width] table, plus the
+    learned positions "pos"[t] of a [max_len, width] table when `max_len` is given (T > max_len raises).  Parameters: "tok"
+    then "pos" (EMBED_PARAM_ORDER; "pos" exists only with max_len), created — and drawn from the host RNG — in THAT order, both
+    with `w_init`.  The gradient of "tok" ACCUMULATES over repeated ids; the row `padding_idx` receives none.  The ids never
+    get a gradient.  `fused=False` runs the composed route (a row gather; a one-hot product backward that reads the ids on the
+    host)."""
+
+    def __init__(self, vocab, width, max_len=None, padding_idx=None, w_init=NormalInit(0.0, 0.02), fused=True):
+        super().__init__("Embedding")
+        self.vocab, self.width, self.max_len, self.fused = int(vocab), int(width), max_len, fused
+        if self.vocab < 1 or self.width < 1 or (max_len is not None and int(max_len) < 1):
+            raise ValueError("Embedding: vocab, width and max_len must be >= 1, got %r, %r, %r" % (vocab, width, max_len))
+        if padding_idx is not None and not 0 <= int(padding_idx) < self.vocab:
+            raise ValueError("Embedding: padding_idx %r outside [0, %d)" % (padding_idx, self.vocab))
+        self.padding_idx = None if padding_idx is None else int(padding_idx)
+        self.names = EMBED_PARAM_ORDER if max_len is not None else EMBED_PARAM_ORDER[:1]
+        self.shapes = {"tok": [self.vocab, self.width]}
+        if max_len is not None:
+            self.shapes["pos"] = [int(max_len), self.width]
+        self.params = {}
+        for name in self.names:                      # created in EMBED_PARAM_ORDER: each draws from the host RNG
+            tensor = w_init(shape=self.shapes[name])
+            tensor.zero_grad()
+            self.params[name] = tensor
+        self.inputs = None
+        self.is_init = True
+
+    def forward(self, inputs):
+        if len(inputs.shape) != 2:
+            raise ValueError("Embedding: the input must be integer ids [B, T], got shape %s" % (tuple(inputs.shape),))
+        if self.max_len is not None and int(inputs.shape[1]) > int(self.max_len):
+            raise ValueError("Embedding: sequences of %d ids exceed max_len %d" % (int(inputs.shape[1]), int(self.max_len)))
+        self.inputs = inputs
+        return ops.embedding_(self.params["tok"], inputs, self.params.get("pos"), padding_idx=self.padding_idx,
+                              route=None if self.fused else "composed")

@@ -5,6 +5,9 @@ m x c logits, core/losses.py:26-27), not a per-row softmax.  `fused=T
 one node / three kernels; `fused=False` evaluates the literal 12-op expression through the autograd ops.
 With a communicator the shards exchange one {max, sum-exp} pair so a data-parallel run equals the
 single-process run on the global batch.
+
+CrossEntropyLoss is NOT in the reference: the per-row softmax cross-entropy with integer targets that a token model needs
+(ops.cross_entropy_).
 """
 
 import numpy as np
@@ -39,6 +42,27 @@ class SoftmaxCrossEntropyLoss(BaseLoss):
         p = exps / exps.sum()
         nll = -ops.log((p * labels).sum(1))
         return nll.sum() / m
+
+
+class CrossEntropyLoss(BaseLoss):
+    """Softmax cross-entropy over the LAST axis of logits [..., V] with INTEGER targets [...]: per row,
+    log sum exp(x) - x[target]; `reduction` "mean" divides the sum by the number of counted rows, "sum" does not.  Rows whose
+    target equals `ignore_index` contribute nothing and get a zero gradient; when every row is ignored the loss is 0.
+
+    How it differs from SoftmaxCrossEntropyLoss, which is the reference's loss and stays what it is: that one normalises over
+    the WHOLE batch (one max and one sum of exponentials over all m x c logits), takes one-hot float labels and divides by m;
+    this one normalises each row on its own — the usual definition — takes class indices, knows `ignore_index`, and handles
+    rows as wide as a vocabulary.  `fused=False` runs the composed route (max / exp / sum / log and an index gather)."""
+
+    def __init__(self, ignore_index=None, reduction="mean", fused=True):
+        from ..tokens import REDUCTIONS
+        if reduction not in REDUCTIONS:
+            raise ValueError("CrossEntropyLoss: reduction must be one of %s, got %r" % (REDUCTIONS, reduction))
+        self.ignore_index, self.reduction, self.fused = ignore_index, reduction, fused
+
+    def loss(self, logits, targets):
+        return ops.cross_entropy_(logits, targets, ignore_index=self.ignore_index, reduction=self.reduction,
+                                  route=None if self.fused else "composed")
 
 
 class SquaredErrorLoss(BaseLoss):

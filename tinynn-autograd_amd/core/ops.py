@@ -9,7 +9,9 @@ reference expression each piece replaces.
 Extra fused nodes used by this package's own layers/losses (parity-tested against the generic chain):
 `dense_` (GEMM + bias epilogue), `sigmoid_`, `softmax_nll_` (whole-batch softmax NLL), `conv2d_` / `max_pool2d_` (NCHW
 convolution and max pooling, csrc/tnn_conv.hip; the reference has neither), `attention_` (fused scaled-dot-product attention,
-csrc/tnn_attn.hip; likewise), `layer_norm_` / `rms_norm_` / `gelu_` (csrc/tnn_norm.hip; likewise).
+csrc/tnn_attn.hip; likewise), `layer_norm_` / `rms_norm_` / `gelu_` (csrc/tnn_norm.hip; likewise), `embedding_` /
+`cross_entropy_` (csrc/tnn_token.hip; likewise — `embedding_` is the gather whose vjp ACCUMULATES over repeated ids, which
+`getitem_`'s does not).
 """
 
 import math
@@ -719,6 +721,91 @@ def gelu_(x, approximate="none", route=None, **unknown):
     return build_unary_ops_tensor(x, lambda g: da.gelu_bwd(xv, g, approximate=approximate, route=route), out)
 
 
+def _index_values(obj, limit, what, also=None):
+    """ids / targets given as a Tensor, a DeviceArray or numpy -> a dense int64 device array; host values are range-checked
+    once, here (IndexError); they never require a gradient."""
+    obj = getattr(obj, "values", obj) if hasattr(obj, "requires_grad") else obj
+    return da._token_ids(obj, limit, what, also)[0]
+
+
+class _EmbedVjp(object):
+    """The vjps of one ops.embedding_ node: `fused_vjp` for Tensor.backward (ONE tnn_embed_bwd call for whichever of table /
+    pos require gradients, written into arena views when they are lent), per-edge forms for everybody else."""
+    __slots__ = ("table", "pos", "ids", "padding_idx", "route", "edges")
+
+    def __init__(self, table, pos, ids, padding_idx, route):
+        self.table, self.pos, self.ids = table, pos, ids
+        self.padding_idx, self.route = padding_idx, route
+        self.edges = ()
+
+    def _bwd(self, g, names, home=None):
+        home = home or {}
+        dtable, dpos = da.embedding_bwd(g, self.ids, self.table.shape, None if self.pos is None else self.pos.shape,
+                                        self.padding_idx, need_dtable="table" in names, need_dpos="pos" in names,
+                                        dtable_out=home.get("table"), dpos_out=home.get("pos"), route=self.route)
+        return {"table": dtable, "pos": dpos}
+
+    def d_table(self, g):
+        return self._bwd(g, ("table",))["table"]
+
+    def d_pos(self, g):
+        return self._bwd(g, ("pos",))["pos"]
+
+    def fused_vjp(self, g, homes):
+        edges = self.edges
+        res = self._bwd(g, edges, dict(zip(edges, homes)))
+        return [res[name] for name in edges]
+
+
+def embedding_(table, ids, pos=None, padding_idx=None, route=None, **unknown):
+    """Token embedding node: out[..., :] = table[ids[...], :] (+ pos[t, :], t the index along the last axis of ids).  table
+    [V, E] and pos [T', E] (T' >= the last extent of ids) are tensors; ids — a Tensor, a DeviceArray or numpy, integers of any
+    shape — never require a gradient.  Host ids outside [0, V) raise IndexError; device-resident ones are not read back and
+    give a zero token row.  The vjp w.r.t. the table is a scatter-ADD: a token that occurs n times receives the sum of its n
+    gradients (`table[ids]` through getitem_ keeps only the last one); padding_idx, when given, receives none.
+
+    Forward is ONE tnn_embed_fwd launch, backward ONE tnn_embed_bwd call for whichever of table / pos require gradients — a
+    deterministic sort-and-segment sum without floating-point atomics.  Under the CPU test twin and with route="composed" (or
+    device_array.TOKEN_ROUTE) the same mathematics runs on a row gather and a one-hot product, whose backward reads the ids
+    on the host and therefore cannot be captured.  Out of scope: bf16, max_norm, sparse gradients — unknown keyword arguments
+    raise."""
+    if unknown:
+        raise TypeError("embedding_: unsupported arguments %s" % sorted(unknown))
+    idd = _index_values(ids, int(table.shape[0]), "embedding")
+    if padding_idx is not None and not 0 <= int(padding_idx) < int(table.shape[0]):
+        raise ValueError("embedding: padding_idx %d outside [0, %d)" % (int(padding_idx), int(table.shape[0])))
+    out = da.embedding(table.values, idd, None if pos is None else pos.values, route=route)
+    ctx = _EmbedVjp(table, pos, idd, padding_idx, route)
+    named = [("table", table, ctx.d_table), ("pos", pos, ctx.d_pos)]
+    node = _make_node(table.__class__, out, [(t, fn) for _, t, fn in named if t is not None])
+    ctx.edges = [name for name, t, _ in named if t is not None and t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
+def cross_entropy_(logits, targets, ignore_index=None, reduction="mean", route=None, **unknown):
+    """Per-row softmax cross-entropy node over the LAST axis of logits [..., V] with integer targets [...] (a Tensor, a
+    DeviceArray or numpy; never a gradient): the sum ("sum") or the mean over the counted rows ("mean") of
+    log sum exp(x) - x[target].  Rows whose target equals ignore_index are not counted and get no gradient; when nothing is
+    counted the loss is 0 and every gradient is zero.  Host targets that are neither in [0, V) nor ignore_index raise
+    IndexError; device-resident ones are not read back (out-of-range rows are not counted).
+
+    Forward is ONE tnn_xent_fwd call that reads every logit once and keeps the per-row log-sum-exp; backward ONE tnn_xent_bwd
+    launch that takes the upstream gradient and the row count as device scalars (nothing is read on the host).  Composed
+    route: as for embedding_.  Out of scope: label smoothing, class weights, bf16 — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("cross_entropy_: unsupported arguments %s" % sorted(unknown))
+    tg = _index_values(targets, int(logits.shape[-1]), "cross_entropy", also=ignore_index)
+    loss, _, lse, count = da.cross_entropy(logits.values, tg, ignore_index=ignore_index, reduction=reduction, route=route)
+
+    def grad_fn(g, out=None):
+        return da.cross_entropy_bwd(logits.values, tg, lse, count, g, ignore_index=ignore_index, reduction=reduction,
+                                    route=route, dlogits_out=out)
+    node = build_unary_ops_tensor(logits, grad_fn, loss)
+    node._fused_vjp = lambda g, homes: [grad_fn(g, homes[0])]
+    return node
+
+
 def _softmax_head(logits, labels):
     """The classifier head as ONE launch when the logits are still pending (dense_(lazy=True)) and the shapes are the ones
     tnn_mlp_head_tick takes: last Dense forward (core/layers.py:49) + whole-batch softmax NLL (core/losses.py:24-32) + the last
@@ -1008,3 +1095,17 @@ def gelu(obj, approximate="none", **unknown):
     if unknown:
         raise TypeError("gelu: unsupported arguments %s" % sorted(unknown))
     return gelu_(as_tensor(obj), approximate=approximate)
+
+
+def embedding(obj, ids, pos=None, padding_idx=None, **unknown):
+    """not in the reference: see embedding_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("embedding: unsupported arguments %s" % sorted(unknown))
+    return embedding_(as_tensor(obj), ids, _opt_tensor(pos), padding_idx=padding_idx)
+
+
+def cross_entropy(obj, targets, ignore_index=None, reduction="mean", **unknown):
+    """not in the reference: see cross_entropy_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("cross_entropy: unsupported arguments %s" % sorted(unknown))
+    return cross_entropy_(as_tensor(obj), targets, ignore_index=ignore_index, reduction=reduction)

@@ -31,6 +31,7 @@ from . import batching as _bt
 from . import conv as _cv
 from . import indexing as _ix
 from . import norm as _nm
+from . import tokens as _tk
 from ._lib import F32, F64, I64, U8
 
 _CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int64): I64,
@@ -1695,6 +1696,192 @@ def gelu_bwd(x, dy, approximate="none", route=None, dx_out=None):
     t = _gelu_inner(x)
     slope = (t + 1.0) * 0.5 + (x * 0.5) * (1.0 - t * t) * ((x * x) * (3.0 * _GELU_A) + 1.0) * _GELU_C
     return dy * slope
+
+
+# ---------------------------------------------------------------------- kernels: embedding, per-row cross-entropy (csrc/tnn_token.hip)
+TOKEN_ROUTE = None    # tests / probes: "native" or "composed" overrides the planner's choice (tokens.py)
+
+
+def _token_ids(ids, limit, what, also=None):
+    """(dense int64 device array, host copy or None) of ids / targets.  Host values (numpy, lists) are range-checked here —
+    outside [0, limit) and not `also` raises IndexError; device-resident ones are NOT read back (the kernels skip them)."""
+    if isinstance(ids, DeviceArray):
+        if ids._hv is not None or ids.dtype.kind not in "iu":
+            raise TypeError("%s: integer ids are needed, got a device array of dtype %s" % (what, ids.dtype))
+        return ids.astype(np.int64)._contig(), None
+    host = np.asarray(ids)
+    if host.dtype.kind not in "iu":
+        raise TypeError("%s: integer ids are needed, got dtype %s" % (what, host.dtype))
+    host = np.ascontiguousarray(host, dtype=np.int64)
+    bad = (host < 0) | (host >= limit)
+    if also is not None:
+        bad &= host != also
+    if bad.any():
+        raise IndexError("%s: index %d is out of bounds for %d entries" % (what, int(host[bad].flat[0]), limit))
+    return asarray(host), host
+
+
+def _token_dest(need, out, shape, dt):
+    if not need:
+        return None
+    d = _grad_dest(out, shape, dt)
+    return DeviceArray._new(shape, dt) if d is None else d
+
+
+def embedding(table, ids, pos=None, route=None):
+    """out[..., :] = table[ids[...], :] (+ pos[t, :], t the index along the LAST axis of ids; pos may hold more rows than
+    that axis is long).  table [V, E]; ids: integers of any shape, numpy / list (range-checked on the host: IndexError) or a
+    device int64 array (not read back; an id outside [0, V) gives a zero token row).  Native: ONE tnn_embed_fwd launch;
+    composed (tokens.py: the CPU test twin, route="composed"): a row gather and a broadcast addition."""
+    dt, (table, pos) = _norm_operands(table, pos)
+    if table.ndim != 2:
+        raise ValueError("embedding: the table must be [V, E], got shape %s" % (tuple(table.shape),))
+    idd, _ = _token_ids(ids, table.shape[0], "embedding")
+    plan = _tk.plan_embedding(table.shape, idd.shape, None if pos is None else pos.shape, None,
+                              native=_lib.get().has_token, route=route or TOKEN_ROUTE)
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        _lib.get().embed_fwd(table._ptr, idd._ptr, _ptr_of(pos), out._ptr, plan.M, plan.V, plan.E, plan.T, out._code())
+        return out
+    out = table.take(idd.reshape(plan.M))
+    if pos is not None:
+        out = out.reshape(plan.M // plan.T, plan.T, plan.E) + pos[:plan.T]
+    return out.reshape(plan.out_shape)
+
+
+def embedding_bwd(dy, ids, table_shape, pos_shape=None, padding_idx=None, need_dtable=True, need_dpos=True, dtable_out=None,
+                  dpos_out=None, route=None):
+    """(dtable, dpos) of embedding for the gradient `dy` of its output.  dtable[v] = the SUM of dy over the positions that
+    hold v — repeated ids accumulate — with EVERY row written (zeros for absent tokens and for padding_idx); dpos[t] = the sum
+    of dy over the sequences (rows past the sequence length: zeros).  need_* = False: not computed, None is returned.
+    Native: ONE tnn_embed_bwd call (a deterministic sort of the positions by token, then segmented sums: no floating-point
+    atomics, identical bits on every call).  Composed: one-hot^T @ dy through matmul; the one-hot is built from a HOST copy of
+    the ids, so the composed backward cannot be captured into a graph.  *_out: dense arrays the results are written into."""
+    dt, (dy,) = _norm_operands(dy)
+    idd, host = _token_ids(ids, int(table_shape[0]), "embedding")
+    need_dpos = need_dpos and pos_shape is not None
+    plan = _tk.plan_embedding(table_shape, idd.shape, pos_shape, padding_idx, native=_lib.get().has_token,
+                              route=route or TOKEN_ROUTE)
+    if dy.shape != plan.out_shape:
+        dy = dy._broadcast_to(plan.out_shape)._contig()
+    if not (need_dtable or need_dpos):
+        return None, None
+    t_shape = (plan.V, plan.E)
+    p_shape = None if pos_shape is None else tuple(int(s) for s in pos_shape)
+    if plan.empty():
+        return (zeros(t_shape, dt) if need_dtable else None), (zeros(p_shape, dt) if need_dpos else None)
+    if plan.route == "native":
+        dtable, dpos = _token_dest(need_dtable, dtable_out, t_shape, dt), _token_dest(need_dpos, dpos_out, p_shape, dt)
+        if dpos is not None and p_shape[0] > plan.T:
+            dpos.fill(0.0)                                       # the launch writes the first T rows
+        nbytes = plan.workspace_bytes(dt.itemsize) if need_dtable else 0
+        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+        _lib.get().embed_bwd(dy._ptr, idd._ptr, _ptr_of(dtable), _ptr_of(dpos), _ptr_of(ws), nbytes, plan.M, plan.V, plan.E,
+                             plan.T, plan.padding_idx, dy._code())
+        return dtable, dpos
+    dy2 = dy.reshape(plan.M, plan.E)
+    dtable = dpos = None
+    if need_dtable:
+        if host is None:
+            _need_eager("the composed embedding backward (its one-hot is built from a host copy of the ids)")
+            host = np.asarray(idd)
+        flat = host.reshape(plan.M)
+        one_hot = (flat[:, None] == np.arange(plan.V)[None, :]) & (flat[:, None] != plan.padding_idx)
+        dtable = matmul(asarray(one_hot.astype(dt), dtype=dt), dy2, swap_a=True)
+    if need_dpos:
+        dpos = dy2.reshape(plan.M // plan.T, plan.T, plan.E).sum(axis=0)
+        if p_shape[0] > plan.T:
+            full_rows = zeros(p_shape, dt)
+            full_rows[:plan.T] = dpos
+            dpos = full_rows
+    return dtable, dpos
+
+
+def _xent_plan(x, tg, ignore_index, reduction, route):
+    return _tk.plan_cross_entropy(x.shape, tg.shape, ignore_index, reduction, native=_lib.get().has_token,
+                                  route=route or TOKEN_ROUTE)
+
+
+def _xent_valid(plan, tg, host):
+    """Host view of the targets of the composed route: (flat targets, bool mask of the counted rows)."""
+    if host is None:
+        _need_eager("the composed cross-entropy with device-resident targets (they are read back)")
+        host = np.asarray(tg)
+    flat = host.reshape(plan.M)
+    return flat, (flat != plan.ignore_index) & (flat >= 0) & (flat < plan.V)
+
+
+def cross_entropy(logits, targets, ignore_index=None, reduction="mean", route=None):
+    """(loss, losses, lse, count) of the PER-ROW softmax cross-entropy over the last axis of logits [..., V] with integer
+    targets [...]: lse = log sum exp of the row, losses = lse - x[target]; a row whose target is ignore_index has loss 0 and is
+    not counted; count = the counted rows (a device scalar in the operand dtype), loss = sum of losses ("sum") or sum / count
+    ("mean"; 0 when nothing is counted).  targets: numpy / list (range-checked on the host: IndexError unless in [0, V) or
+    ignore_index) or a device int64 array (not read back; out-of-range rows are not counted).  -inf logits contribute 0; a
+    row of nothing but -inf is out of scope.  Native: ONE tnn_xent_fwd call that reads every logit once; composed: max, exp,
+    sum, log and the gather x[arange, t] as a row gather of the flattened logits, which the CPU test twin has too
+    (device-resident targets are read back there)."""
+    dt, (x,) = _norm_operands(logits)
+    if x.ndim < 1:
+        raise ValueError("cross_entropy: the logits need a last axis of classes, got a scalar")
+    tg, host = _token_ids(targets, x.shape[-1], "cross_entropy", also=ignore_index)
+    plan = _xent_plan(x, tg, ignore_index, reduction, route)
+    if plan.route == "native":
+        losses, lse = DeviceArray._new(plan.rows_shape, dt), DeviceArray._new(plan.rows_shape, dt)
+        loss, count = DeviceArray._new((), dt), DeviceArray._new((), dt)
+        _lib.get().xent_fwd(x._ptr, tg._ptr, losses._ptr, lse._ptr, loss._ptr, count._ptr, plan.M, plan.V, plan.ignore_index,
+                            _tk.REDUCTION_CODE[reduction], x._code())
+        return loss, losses, lse, count
+    if plan.empty():
+        return zeros((), dt), zeros(plan.rows_shape, dt), zeros(plan.rows_shape, dt), zeros((), dt)
+    flat, valid = _xent_valid(plan, tg, host)
+    x2 = x.reshape(plan.M, plan.V)
+    mx = x2.max(axis=1, keepdims=True)
+    lse = (log(exp(x2 - mx).sum(axis=1, keepdims=True)) + mx).reshape(plan.M)
+    rows = np.nonzero(valid)[0]
+    losses = zeros((plan.M,), dt)
+    if rows.size:
+        losses[rows] = lse.take(rows) - x.reshape(plan.M * plan.V).take(rows * plan.V + flat[rows])     # x[rows, t]
+    loss = losses.sum()
+    if reduction == "mean":
+        loss = loss / float(max(rows.size, 1))
+    return loss.reshape(()), losses.reshape(plan.rows_shape), lse.reshape(plan.rows_shape), full((), float(rows.size), dt)
+
+
+def cross_entropy_bwd(logits, targets, lse, count, g=1.0, ignore_index=None, reduction="mean", route=None, dlogits_out=None):
+    """dlogits = (softmax(x) - one_hot(target)) * g / count ("sum": without / count) from the saved per-row lse; rows that
+    were not counted get zeros, and count == 0 gives all zeros.  g (the gradient of the loss) and count (cross_entropy's) are
+    used as DEVICE scalars on the native route — nothing is read on the host, a training step stays capturable — which is
+    ONE tnn_xent_bwd launch: the logits are read once, dlogits written once.  dlogits_out: a dense array to write into."""
+    dt, (x, lse) = _norm_operands(logits, lse)
+    tg, host = _token_ids(targets, x.shape[-1], "cross_entropy", also=ignore_index)
+    plan = _xent_plan(x, tg, ignore_index, reduction, route)
+    if tuple(lse.shape) != plan.rows_shape:
+        raise ValueError("cross_entropy_bwd: lse must have shape %s, got %s" % (plan.rows_shape, tuple(lse.shape)))
+    g = asarray(g)
+    if g.size != 1:
+        raise ValueError("cross_entropy_bwd: the loss is a scalar, got a gradient of shape %s" % (tuple(g.shape),))
+    if plan.empty():
+        return zeros(plan.logits_shape, dt)
+    if plan.route == "native":
+        gd, cd = g.astype(dt)._contig(), asarray(count).astype(dt)._contig()
+        dx = _grad_dest(dlogits_out, plan.logits_shape, dt)
+        if dx is None:
+            dx = DeviceArray._new(plan.logits_shape, dt)
+        _lib.get().xent_bwd(x._ptr, tg._ptr, lse._ptr, cd._ptr, gd._ptr, dx._ptr, plan.M, plan.V, plan.ignore_index,
+                            _tk.REDUCTION_CODE[reduction], x._code())
+        return dx
+    flat, valid = _xent_valid(plan, tg, host)
+    n = int(valid.sum())
+    if n == 0:
+        return zeros(plan.logits_shape, dt)
+    x2 = x.reshape(plan.M, plan.V)
+    one_hot = (flat[:, None] == np.arange(plan.V)[None, :]) & valid[:, None]
+    p = exp(x2 - lse.reshape(plan.M, 1))
+    rows = asarray(valid.astype(dt).reshape(plan.M, 1) * (1.0 / n if reduction == "mean" else 1.0), dtype=dt)
+    g = g if g._hv is not None else g.astype(dt).reshape(1, 1)
+    return ((p - asarray(one_hot.astype(dt), dtype=dt)) * rows * g).reshape(plan.logits_shape)
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)

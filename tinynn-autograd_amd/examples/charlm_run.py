@@ -1,0 +1,105 @@
+"""A tiny causal language model through the ordinary `Model`: Embedding (tokens + learned positions) -> two pre-norm causal
+TransformerBlocks -> LayerNorm -> Dense head over every position -> per-row CrossEntropyLoss, Adam.  The data are synthetic
+and generated here: each sequence repeats a random motif of `period` tokens drawn from `vocab`, and the target is the next
+token — so every position >= period can be predicted by attending one period back, and the first `period` cannot.
+
+    python tinynn-autograd_amd/examples/charlm_run.py [--num_ep 4] [--batch_size 64] [--n_train 2048] [--lr 3e-3] [--seed 0]
+"""
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
+
+import tinynn_autograd_amd as tn                                                            # noqa: E402
+from tinynn_autograd_amd.core import ops                                                    # noqa: E402
+from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
+from tinynn_autograd_amd.core.losses import CrossEntropyLoss                                # noqa: E402
+from tinynn_autograd_amd.core.model import Model                                            # noqa: E402
+from tinynn_autograd_amd.core.nn import Net                                                 # noqa: E402
+from tinynn_autograd_amd.core.optimizer import Adam                                         # noqa: E402
+from tinynn_autograd_amd.core.tensor import Tensor                                          # noqa: E402
+
+
+class Rows(Layer):
+    """[B, T, E] -> [B T, E]: Dense stays 2-D."""
+
+    def __init__(self):
+        super().__init__("Rows")
+
+    def forward(self, inputs):
+        return ops.reshape(inputs, (-1, int(inputs.shape[-1])))
+
+
+def make_data(rs, count, seq, vocab, period):
+    """(ids [count, seq], targets [count, seq]) int64: a motif of `period` random tokens repeated; the target is the next token."""
+    motif = rs.randint(0, vocab, (count, period))
+    stream = motif[:, np.arange(seq + 1) % period]
+    return np.ascontiguousarray(stream[:, :-1]), np.ascontiguousarray(stream[:, 1:])
+
+
+def build(args):
+    fused = not args.composed
+    net = Net([Embedding(args.vocab, args.width, max_len=args.seq, fused=fused),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused),
+               LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
+    loss_layer = CrossEntropyLoss(fused=fused)
+    return Model(net=net, loss=loss_layer, optimizer=Adam(lr=args.lr)), loss_layer
+
+
+def main(args):
+    if args.seed >= 0:
+        np.random.seed(args.seed)
+    rs = np.random.RandomState(max(args.seed, 0))
+    train_x, train_y = make_data(rs, args.n_train, args.seq, args.vocab, args.period)
+    test_x, test_y = make_data(rs, args.n_test, args.seq, args.vocab, args.period)
+    model, loss_layer = build(args)
+    print("data: synthetic, %d sequences of %d tokens from %d, period %d; backend %s"
+          % (len(train_x), args.seq, args.vocab, args.period, tn.backend_name()))
+    history = []
+    for epoch in range(args.num_ep):
+        t0, losses = time.time(), []
+        for start in range(0, len(train_x) - args.batch_size + 1, args.batch_size):
+            x = Tensor(train_x[start:start + args.batch_size])
+            y = train_y[start:start + args.batch_size].reshape(-1)
+            model.zero_grad()
+            loss = loss_layer.loss(model.forward(x), y)
+            loss.backward()
+            model.step()
+            losses.append(loss)
+        mean = float(np.mean([float(l.values) for l in losses]))
+        model.set_phase("TEST")
+        logits = np.asarray(model.forward(Tensor(test_x)).values).reshape(len(test_x), args.seq, args.vocab)
+        model.set_phase("TRAIN")
+        hit = np.argmax(logits, axis=2) == test_y
+        accuracy = float(hit[:, args.period:].mean())         # the positions whose next token the context determines
+        history.append((mean, accuracy))
+        print("epoch %d: mean loss %.4f, accuracy on predictable positions %.4f, %.2f s" % (epoch, mean, accuracy, time.time() - t0))
+    return history
+
+
+def parse(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--num_ep", default=4, type=int)
+    parser.add_argument("--lr", default=3e-3, type=float)
+    parser.add_argument("--batch_size", default=64, type=int)
+    parser.add_argument("--n_train", default=2048, type=int)
+    parser.add_argument("--n_test", default=256, type=int)
+    parser.add_argument("--seq", default=16, type=int)
+    parser.add_argument("--vocab", default=16, type=int)
+    parser.add_argument("--width", default=32, type=int)
+    parser.add_argument("--heads", default=4, type=int)
+    parser.add_argument("--period", default=4, type=int)
+    parser.add_argument("--seed", default=0, type=int)
+    parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
+    return parser.parse_args(argv)
+
+
+if __name__ == "__main__":
+    main(parse())
