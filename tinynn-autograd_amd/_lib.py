@@ -55,6 +55,10 @@ from ._token_signatures import _TOKEN_SIGNATURES              # noqa: E402  (inc
 
 TOKEN_SYMBOLS = sorted(_TOKEN_SIGNATURES)
 
+from ._decode_signatures import _DECODE_SIGNATURES            # noqa: E402  (include/tnn_decode.h: libtnn_hip.so only)
+
+DECODE_SYMBOLS = sorted(_DECODE_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -114,12 +118,15 @@ class _Lib(object):
         # products, sqrt and tanh (the exact GELU has no composed form and raises there)
         # and the embedding and the per-row cross-entropy (include/tnn_token.h): under the twin device_array composes them
         # from take, a one-hot product, max / exp / sum / log and the advanced-index gather
+        # and decode attention and token sampling (include/tnn_decode.h): under the twin device_array appends by a slice
+        # assignment and runs the composed attention over the live prefix; sampling reads the logits back
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
                                     (_ATTN_SIGNATURES, "tnn_attn.h", "attention"),
                                     (_NORM_SIGNATURES, "tnn_norm.h", "normalisation"),
-                                    (_TOKEN_SIGNATURES, "tnn_token.h", "embedding / cross-entropy")):
+                                    (_TOKEN_SIGNATURES, "tnn_token.h", "embedding / cross-entropy"),
+                                    (_DECODE_SIGNATURES, "tnn_decode.h", "decode attention / sampling")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -135,6 +142,7 @@ class _Lib(object):
         self.has_attn = hasattr(self.cdll, "tnn_attn_fwd")
         self.has_norm = hasattr(self.cdll, "tnn_norm_fwd")
         self.has_token = hasattr(self.cdll, "tnn_embed_fwd")
+        self.has_decode = hasattr(self.cdll, "tnn_decode_attn")
 
     @staticmethod
     def _absent(name, what):

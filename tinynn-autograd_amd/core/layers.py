@@ -234,7 +234,10 @@ class MultiHeadAttention(Layer):
             self.params[name] = tensor
         self.is_init = True
 
-    def forward(self, inputs):
+    def forward(self, inputs, cache=None):
+        """cache: a generation.LayerCache (inference).  Empty: the PREFILL — the ordinary causal path runs and its k and v
+        [B, T, H, E / H] are slice-assigned into the cache; afterwards T must be 1: three projections of the one row,
+        ops.attention_decode_ with the append, the output projection.  None: today's path, bit for bit."""
         if len(inputs.shape) != 3:
             raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
         b, t, e = (int(s) for s in inputs.shape)
@@ -242,11 +245,24 @@ class MultiHeadAttention(Layer):
             self._init_parameters(e)
         if e != self.shapes["wq"][0]:
             raise ValueError("MultiHeadAttention: the input width %d differs from the layer's %d" % (e, self.shapes["wq"][0]))
-        self.inputs = inputs
         p, h = self.params, self.num_heads
+        route = None if self.fused else "composed"
+        if cache is not None:
+            if not self.causal:
+                raise ValueError("MultiHeadAttention: a key / value cache needs causal=True (a non-causal layer's earlier "
+                                 "positions would depend on later tokens)")
+            cache.check(b, t, h, e // h)                 # raises before any launch: a full cache, T > 1 after the prefill
+        self.inputs = inputs
         rows = ops.reshape(inputs, (b * t, e))
-        q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h, e // h)) for n in "qkv")
-        att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=None if self.fused else "composed")
+        if cache is not None and cache.length > 0:
+            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h, e // h)) for n in "qkv")
+            att = ops.attention_decode_(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
+            cache.length += 1
+        else:
+            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h, e // h)) for n in "qkv")
+            att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route)
+            if cache is not None:
+                cache.fill(k.values, v.values)
         out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
         return ops.reshape(out, (b, t, e))
 
@@ -356,7 +372,8 @@ class TransformerBlock(Layer):
             self.params[key] = parts[part].params[name]
         self.is_init = True
 
-    def forward(self, inputs):
+    def forward(self, inputs, cache=None):
+        """cache: handed to the attention part (MultiHeadAttention.forward); None: today's path."""
         if len(inputs.shape) != 3:
             raise ValueError("TransformerBlock: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
         b, t, e = (int(s) for s in inputs.shape)
@@ -369,7 +386,8 @@ class TransformerBlock(Layer):
         for key in BLOCK_PARAM_ORDER:                # the flat dict is the truth (Net.set_parameters replaces its tensors)
             part, name = key.split(".")
             parts[part].params[name] = self.params[key]
-        h = inputs + parts["attn"].forward(parts["ln1"].forward(inputs))
+        normed = parts["ln1"].forward(inputs)
+        h = inputs + parts["attn"].forward(normed, cache=cache)
         z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))
         z = ops.gelu_(z, approximate="tanh", route=None if self.fused else "composed")
         return h + ops.reshape(parts["fc2"].forward(z), (b, t, e))
@@ -403,11 +421,20 @@ class Embedding(Layer):
         self.inputs = None
         self.is_init = True
 
-    def forward(self, inputs):
+    def forward(self, inputs, offset=0):
+        """offset: the position of the first id (a decoding step embeds token `offset` alone): positions offset .. offset +
+        T - 1 are used, as the row slice of "pos"."""
         if len(inputs.shape) != 2:
             raise ValueError("Embedding: the input must be integer ids [B, T], got shape %s" % (tuple(inputs.shape),))
-        if self.max_len is not None and int(inputs.shape[1]) > int(self.max_len):
-            raise ValueError("Embedding: sequences of %d ids exceed max_len %d" % (int(inputs.shape[1]), int(self.max_len)))
+        offset = int(offset)
+        if offset < 0:
+            raise ValueError("Embedding: offset must be >= 0, got %d" % offset)
+        if self.max_len is not None and offset + int(inputs.shape[1]) > int(self.max_len):
+            raise ValueError("Embedding: sequences of %d ids%s exceed max_len %d"
+                             % (int(inputs.shape[1]), " at offset %d" % offset if offset else "", int(self.max_len)))
         self.inputs = inputs
-        return ops.embedding_(self.params["tok"], inputs, self.params.get("pos"), padding_idx=self.padding_idx,
+        pos = self.params.get("pos")
+        if pos is not None and offset:
+            pos = ops.getitem_(pos, slice(offset, offset + int(inputs.shape[1])))
+        return ops.embedding_(self.params["tok"], inputs, pos, padding_idx=self.padding_idx,
                               route=None if self.fused else "composed")

@@ -783,6 +783,43 @@ def embedding_(table, ids, pos=None, padding_idx=None, route=None, **unknown):
     return node
 
 
+def _raw_values(obj):
+    return obj.values if hasattr(obj, "requires_grad") else obj
+
+
+def attention_decode_(q, k_cache, v_cache, length, k_new=None, v_new=None, scale=None, layout="bthd", route=None, splits=None,
+                      **unknown):
+    """One decoding step of attention, INFERENCE ONLY: o [B, H, Dv] = softmax(scale q k^T) v for one query per (batch, head)
+    over the live rows of a key / value cache; with k_new / v_new the step's own row is first written into cache row `length`
+    (the caches — DeviceArrays or Tensors — are modified in place).  q [B, H, D]; `length` is a host integer shared by the
+    batch; layout "bthd" (caches [B, Tmax, H, D]) or "bhtd" ([B, H, Tmax, D]).  No mask: a decoding step sees every cached key.
+
+    The result is a LEAF tensor without a grad_fn — nothing here is differentiable, and the operands' graphs are not
+    extended.  ONE tnn_decode_attn call, whose keys are split over enough workgroups to cover the machine (decoding.py);
+    under the CPU test twin and with route="composed" (or device_array.DECODE_ROUTE) a slice assignment and the composed
+    attention.  Out of scope: ragged batches, grouped-query heads, chunked prefill, bf16 — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_decode_: unsupported arguments %s (ragged batches, grouped-query heads and bf16 are out "
+                        "of scope)" % sorted(unknown))
+    out = da.attention_decode(q.values, _raw_values(k_cache), _raw_values(v_cache), length,
+                              None if k_new is None else k_new.values, None if v_new is None else v_new.values, scale=scale,
+                              layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
+def sample_rows_(logits, u=None, temperature=1.0, top_k=None, route=None, **unknown):
+    """The next token of every row, INFERENCE ONLY: ids int64 [M] (a leaf tensor on the device, no grad_fn) from logits [M, V]
+    and one uniform number per row, u [M] in [0, 1) — a Tensor, a DeviceArray or numpy; not needed at temperature 0, which is
+    the first index of the row maximum.  Otherwise the inverse CDF of softmax(logits / temperature) restricted to the top_k
+    largest (None: all; ties at the threshold go to the lowest indices).  ONE tnn_sample_rows launch that reads nothing back:
+    the ids can feed embedding_ as they are.  The composed route (CPU test twin, route="composed") reads the logits back and
+    cannot be captured.  Out of scope: top-p, a device random generator, bf16 — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("sample_rows_: unsupported arguments %s (top-p is out of scope)" % sorted(unknown))
+    ids = da.sample_rows(logits.values, None if u is None else _raw_values(u), temperature=temperature, top_k=top_k, route=route)
+    return logits.__class__(ids, False, [])
+
+
 def cross_entropy_(logits, targets, ignore_index=None, reduction="mean", route=None, **unknown):
     """Per-row softmax cross-entropy node over the LAST axis of logits [..., V] with integer targets [...] (a Tensor, a
     DeviceArray or numpy; never a gradient): the sum ("sum") or the mean over the counted rows ("mean") of
@@ -1109,3 +1146,18 @@ def cross_entropy(obj, targets, ignore_index=None, reduction="mean", **unknown):
     if unknown:
         raise TypeError("cross_entropy: unsupported arguments %s" % sorted(unknown))
     return cross_entropy_(as_tensor(obj), targets, ignore_index=ignore_index, reduction=reduction)
+
+
+def attention_decode(obj, k_cache, v_cache, length, k_new=None, v_new=None, scale=None, layout="bthd", **unknown):
+    """not in the reference: see attention_decode_ (inference only; unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("attention_decode: unsupported arguments %s" % sorted(unknown))
+    return attention_decode_(as_tensor(obj), k_cache, v_cache, length, _opt_tensor(k_new), _opt_tensor(v_new), scale=scale,
+                             layout=layout)
+
+
+def sample_rows(obj, u=None, temperature=1.0, top_k=None, **unknown):
+    """not in the reference: see sample_rows_ (inference only; unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("sample_rows: unsupported arguments %s (top-p is out of scope)" % sorted(unknown))
+    return sample_rows_(as_tensor(obj), u, temperature=temperature, top_k=top_k)

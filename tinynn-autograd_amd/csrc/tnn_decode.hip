@@ -1,0 +1,565 @@
+// tnn_decode.hip — one step of autoregressive decoding in libtnn_hip.so (include/tnn_decode.h), gfx950 only: attention of ONE
+// query per (batch, head) over a key / value cache with the append of the step's own row, and the choice of the next token.
+//
+// Decode attention is a pair of matrix-vector products: 2 (D + Dv) flops per (D + Dv) itemsize bytes, so it is bound by the
+// rate at which K and V stream in and an MFMA tile would be 1/16 used — plain FMAs.  What counts is that every live K and V
+// element is fetched ONCE, in wide accesses, with enough of them in flight.  A key row is read by a GROUP of G lanes, one PACK
+// per lane (16 bytes when bases and strides allow it, one element otherwise; two packs per lane for element accesses beyond
+// 64 columns), so a wave takes 64 / G consecutive keys per load instruction — contiguous in a [B, H, Tmax, D] cache — and
+// issues the K and V loads of TNN_DECODE_UNROLL keys per group before it uses the first: 8 independent loads per lane.  q
+// stays in registers.  A group reduces its dot products by an exchange over its G lanes, keeps an online maximum m, a sum l
+// and its packs of acc[Dv]; the groups of a wave meet by a fixed exchange tree, the four waves through LDS in wave order, the
+// splits of one (batch, head) in a second launch in ascending order.  Nothing is atomic: identical bits on every call.
+//
+// The row appended by a step is taken from k_new / v_new by the group that owns position `len`, which also copies it into the
+// cache from the registers it loaded it into: nothing is read after being written inside the launch.
+//
+// Sampling: one workgroup per row.  The top-k threshold is found by a radix select over an order-preserving integer key of
+// z = x / temperature (256-bin histograms in LDS, integer atomics), the row is never sorted; the running sum that picks the
+// token is a block scan in index order.
+
+#include <math.h>
+
+#include "tnn_internal.h"
+#include "tnn_decode.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int WAVES = THREADS / 64;
+constexpr int CHUNK = TNN_DECODE_CHUNK;
+constexpr int U = TNN_DECODE_UNROLL;
+constexpr int MAXD = TNN_ATTN_MAX_HEAD_DIM;
+constexpr int ITEMS = TNN_SAMPLE_ITEMS;
+constexpr int BINS = 1 << TNN_SAMPLE_RADIX_BITS;
+static_assert(TNN_DECODE_VEC == 16, "wide accesses are global_load / store_dwordx4");
+static_assert(BINS == THREADS, "one thread clears one bin of the histogram");
+static_assert(MAXD <= 128, "two element packs per lane cover a row");
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+template <typename T, bool VECTOR> struct Pack { typedef T type; static constexpr int N = 1; };
+template <> struct Pack<float, true> { typedef f32x4 type; static constexpr int N = 4; };
+template <> struct Pack<double, true> { typedef f64x2 type; static constexpr int N = 2; };
+
+__device__ __forceinline__ float dot_pack(float a, float b, float d) { return fmaf(a, b, d); }
+__device__ __forceinline__ double dot_pack(double a, double b, double d) { return fma(a, b, d); }
+__device__ __forceinline__ float dot_pack(f32x4 a, f32x4 b, float d) {
+    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, d))));
+}
+__device__ __forceinline__ double dot_pack(f64x2 a, f64x2 b, double d) { return fma(a.y, b.y, fma(a.x, b.x, d)); }
+
+__device__ __forceinline__ float xor_pack(float v, int o) { return __shfl_xor(v, o, 64); }
+__device__ __forceinline__ double xor_pack(double v, int o) { return __shfl_xor(v, o, 64); }
+__device__ __forceinline__ f32x4 xor_pack(f32x4 v, int o) {
+    f32x4 r;
+    r.x = __shfl_xor(v.x, o, 64); r.y = __shfl_xor(v.y, o, 64); r.z = __shfl_xor(v.z, o, 64); r.w = __shfl_xor(v.w, o, 64);
+    return r;
+}
+__device__ __forceinline__ f64x2 xor_pack(f64x2 v, int o) {
+    f64x2 r;
+    r.x = __shfl_xor(v.x, o, 64); r.y = __shfl_xor(v.y, o, 64);
+    return r;
+}
+
+template <typename T> struct Math;
+template <> struct Math<float> {
+    static __device__ __forceinline__ float exp_(float v) { return expf(v); }
+};
+template <> struct Math<double> {
+    static __device__ __forceinline__ double exp_(double v) { return exp(v); }
+};
+
+// ------------------------------------------------------------------------------------------------ decode attention
+struct DecodeArgs {
+    const void* q; const void* k_new; const void* v_new;
+    void* k_cache; void* v_cache; void* o; void* ws;
+    int64_t sq[2], skn[2], svn[2], skc[3], svc[3], so[2];      // element strides: batch, head (, row)
+    int64_t nkeys;       // live keys, the appended one included
+    int64_t len;         // the cache row the appended key goes to (read only when k_new != NULL)
+    int64_t chunks, splits;
+    int H, D, Dv, G, log_g;
+    double scale;
+};
+
+template <typename T, bool VECTOR, int R>
+__global__ __launch_bounds__(THREADS) void decode_kernel(DecodeArgs a) {
+    typedef typename Pack<T, VECTOR>::type P;
+    constexpr int N = Pack<T, VECTOR>::N;
+    __shared__ T s_m[WAVES], s_l[WAVES];
+    __shared__ T s_acc[WAVES][MAXD];
+
+    const int split = blockIdx.x, bh = blockIdx.y;
+    const int b = bh / a.H, h = bh - b * a.H;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int G = a.G, c = lane & (G - 1), grp = lane >> a.log_g;
+    const int per_wave = 64 >> a.log_g, slots = WAVES * per_wave, slot = wave * per_wave + grp;
+
+    const T* q = static_cast<const T*>(a.q) + b * a.sq[0] + h * a.sq[1];
+    T* kc = static_cast<T*>(a.k_cache) + b * a.skc[0] + h * a.skc[1];
+    T* vc = static_cast<T*>(a.v_cache) + b * a.svc[0] + h * a.svc[1];
+    const bool append = a.k_new != nullptr;
+    const T* kn = append ? static_cast<const T*>(a.k_new) + b * a.skn[0] + h * a.skn[1] : nullptr;
+    const T* vn = append ? static_cast<const T*>(a.v_new) + b * a.svn[0] + h * a.svn[1] : nullptr;
+
+    // the run of chunks of this split: keys [k0, k1)
+    const int64_t k0 = (split * a.chunks / a.splits) * CHUNK;
+    int64_t k1 = ((split + 1) * a.chunks / a.splits) * CHUNK;
+    if (k1 > a.nkeys) k1 = a.nkeys;
+
+    int col[R];
+    bool dok[R], vok[R];
+    P qp[R], acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        col[r] = (c + r * G) * N;
+        dok[r] = col[r] < a.D;
+        vok[r] = col[r] < a.Dv;
+        qp[r] = dok[r] ? *reinterpret_cast<const P*>(q + col[r]) : P(0);
+        acc[r] = P(0);
+    }
+    const T scale = (T)a.scale;
+    T m = (T)-INFINITY, l = (T)0;
+
+    for (int64_t base = k0; base < k1; base += (int64_t)U * slots) {          // (workgroup-uniform trip count)
+        P kp[U][R], vp[U][R];
+        bool live[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t j = base + (int64_t)u * slots + slot;
+            live[u] = j < k1;
+            const bool fresh = append && live[u] && j == a.len;        // (only the split that owns the position)
+            const T* krow = fresh ? kn : kc + j * a.skc[2];
+            const T* vrow = fresh ? vn : vc + j * a.svc[2];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                kp[u][r] = live[u] && dok[r] ? *reinterpret_cast<const P*>(krow + col[r]) : P(0);
+                vp[u][r] = live[u] && vok[r] ? *reinterpret_cast<const P*>(vrow + col[r]) : P(0);
+            }
+            if (fresh) {                                       // the step's own row: from registers into cache row len
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (dok[r]) *reinterpret_cast<P*>(kc + j * a.skc[2] + col[r]) = kp[u][r];
+                    if (vok[r]) *reinterpret_cast<P*>(vc + j * a.svc[2] + col[r]) = vp[u][r];
+                }
+            }
+        }
+        T s[U];
+        T mx = m;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            T d = (T)0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) d = dot_pack(qp[r], kp[u][r], d);
+            for (int o = G >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+            s[u] = live[u] ? d * scale : (T)-INFINITY;
+            mx = s[u] > mx ? s[u] : mx;
+        }
+        if (mx > (T)-INFINITY) {                               // (uniform over the group: it shares m and the scores)
+            const T f = Math<T>::exp_(m - mx);                 // 0 on the group's first keys (m = -inf)
+            l *= f;
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] *= f;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const T p = Math<T>::exp_(s[u] - mx);          // 0 for a key that is not live
+                l += p;
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[r] += p * vp[u][r];
+            }
+            m = mx;
+        }
+    }
+
+    // the groups of the wave meet: a fixed exchange tree; group 0 holds the wave's result
+    for (int o = G; o < 64; o <<= 1) {
+        const T m2 = __shfl_xor(m, o, 64), l2 = __shfl_xor(l, o, 64);
+        P acc2[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc2[r] = xor_pack(acc[r], o);
+        const T mx = m2 > m ? m2 : m;
+        if (mx > (T)-INFINITY) {
+            const T f1 = Math<T>::exp_(m - mx), f2 = Math<T>::exp_(m2 - mx);
+            l = l * f1 + l2 * f2;
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] = acc[r] * f1 + acc2[r] * f2;
+            m = mx;
+        }
+    }
+    if (grp == 0) {
+        if (c == 0) { s_m[wave] = m; s_l[wave] = l; }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (vok[r]) *reinterpret_cast<P*>(&s_acc[wave][col[r]]) = acc[r];
+        }
+    }
+    __syncthreads();
+    // the waves meet in wave order; thread x owns column x of the result (every split holds at least one live key, so the
+    // maximum is finite; a wave without keys has m = -inf and weighs 0)
+    if (tid < a.Dv) {
+        T mx = s_m[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
+        T lsum = (T)0, asum = (T)0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const T f = Math<T>::exp_(s_m[w] - mx);
+            lsum += s_l[w] * f;
+            asum += s_acc[w][tid] * f;
+        }
+        if (a.splits == 1) {
+            static_cast<T*>(a.o)[b * a.so[0] + h * a.so[1] + tid] = asum / lsum;
+        } else {
+            T* rec = static_cast<T*>(a.ws) + ((int64_t)bh * a.splits + split) * (a.Dv + 2);
+            if (tid == 0) { rec[0] = mx; rec[1] = lsum; }
+            rec[2 + tid] = asum;
+        }
+    }
+}
+
+// o = the splits' (m, l, acc) records combined in ascending split order; one workgroup per (batch, head), thread x owns column x
+template <typename T>
+__global__ __launch_bounds__(MAXD) void decode_combine_kernel(DecodeArgs a) {
+    const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H, tid = threadIdx.x;
+    if (tid >= a.Dv) return;
+    const int64_t width = a.Dv + 2;
+    const T* rec = static_cast<const T*>(a.ws) + (int64_t)bh * a.splits * width;
+    T mx = rec[0];
+    for (int64_t s = 1; s < a.splits; ++s) {
+        const T v = rec[s * width];
+        mx = v > mx ? v : mx;
+    }
+    T lsum = (T)0, asum = (T)0;
+    for (int64_t s = 0; s < a.splits; ++s) {
+        const T f = Math<T>::exp_(rec[s * width] - mx);
+        lsum += rec[s * width + 1] * f;
+        asum += rec[s * width + 2 + tid] * f;
+    }
+    static_cast<T*>(a.o)[b * a.so[0] + h * a.so[1] + tid] = asum / lsum;
+}
+
+// ------------------------------------------------------------------------------------------------ sampling
+template <typename T> struct Key;
+template <> struct Key<float> {
+    typedef unsigned int type;
+    static constexpr int BITS = 32;
+    static __device__ __forceinline__ type of(float z) {
+        const type bits = __float_as_uint(z);
+        return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+    }
+    static __device__ __forceinline__ float value(type key) {
+        return __uint_as_float(key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+    }
+};
+template <> struct Key<double> {
+    typedef unsigned long long type;
+    static constexpr int BITS = 64;
+    static __device__ __forceinline__ type of(double z) {
+        const type bits = (type)__double_as_longlong(z);
+        return bits ^ ((bits >> 63) ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull);
+    }
+    static __device__ __forceinline__ double value(type key) {
+        return __longlong_as_double((long long)(key ^ ((key >> 63) ? 0x8000000000000000ull : 0xFFFFFFFFFFFFFFFFull)));
+    }
+};
+
+// z of the rule: x / temperature in the operand dtype, -0 counted as +0 (one key per value)
+template <typename T>
+__device__ __forceinline__ T tempered(T x, T temperature) {
+    const T z = x / temperature;
+    return z == (T)0 ? (T)0 : z;
+}
+
+// exclusive prefix of v over the threads of the workgroup in thread order, and the workgroup's total
+template <typename S>
+__device__ __forceinline__ S block_excl_scan(S v, S* wave_total, S& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    S inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const S t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    S excl = __shfl_up(inc, 1, 64);
+    if (lane == 0) excl = (S)0;
+    if (lane == 63) wave_total[wave] = inc;
+    __syncthreads();
+    S off = (S)0, tot = (S)0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const S t = wave_total[w];
+        if (w < wave) off += t;
+        tot += t;
+    }
+    __syncthreads();                                           // wave_total is free for the next call
+    total = tot;
+    return off + excl;
+}
+
+template <typename T>
+__global__ __launch_bounds__(THREADS) void sample_kernel(const T* __restrict__ logits, const T* __restrict__ uniform,
+                                                         int64_t* __restrict__ out, int V, T temperature, int top_k) {
+    typedef typename Key<T>::type K;
+    __shared__ T s_val[WAVES];
+    __shared__ int s_idx[WAVES];
+    __shared__ unsigned int s_hist[BINS];
+    __shared__ unsigned int s_cnt[WAVES];
+    __shared__ K s_prefix;
+    __shared__ unsigned int s_need;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* x = logits + (int64_t)blockIdx.x * V;
+
+    // ---- the row maximum and its first index
+    T best = (T)-INFINITY;
+    int at = 0x7fffffff;
+    for (int64_t i = tid; i < V; i += THREADS) {
+        const T v = x[i];
+        if (v > best || at == 0x7fffffff) { best = v; at = (int)i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const T v2 = __shfl_xor(best, o, 64);
+        const int i2 = __shfl_xor(at, o, 64);
+        if (v2 > best || (v2 == best && i2 < at)) { best = v2; at = i2; }
+    }
+    if (lane == 0) { s_val[wave] = best; s_idx[wave] = at; }
+    __syncthreads();
+    best = s_val[0]; at = s_idx[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) {
+        if (s_val[w] > best || (s_val[w] == best && s_idx[w] < at)) { best = s_val[w]; at = s_idx[w]; }
+    }
+    __syncthreads();
+    if (temperature == (T)0) {
+        if (tid == 0) out[blockIdx.x] = at;
+        return;
+    }
+    const T zmax = tempered(best, temperature);                // (x -> z is monotone: the maximum of z)
+
+    // ---- the top-k threshold: key `thr`, of whose columns the `need` lowest are kept
+    const bool all = top_k == 0 || top_k >= V;
+    K thr = 0;
+    unsigned int need = 0;
+    if (!all) {
+        K prefix = 0;
+        need = (unsigned int)top_k;
+        for (int shift = Key<T>::BITS - TNN_SAMPLE_RADIX_BITS; shift >= 0; shift -= TNN_SAMPLE_RADIX_BITS) {
+            const bool first = shift == Key<T>::BITS - TNN_SAMPLE_RADIX_BITS;
+            s_hist[tid] = 0;
+            __syncthreads();
+            for (int64_t i = tid; i < V; i += THREADS) {
+                const K key = Key<T>::of(tempered(x[i], temperature));
+                if (first || (key >> (shift + TNN_SAMPLE_RADIX_BITS)) == prefix)
+                    atomicAdd(&s_hist[(unsigned int)(key >> shift) & (BINS - 1)], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned int above = 0;
+                int digit = BINS - 1;
+                for (; digit > 0; --digit) {
+                    const unsigned int here = s_hist[digit];
+                    if (above + here >= need) break;
+                    above += here;
+                }
+                s_prefix = first ? (K)digit : (K)((prefix << TNN_SAMPLE_RADIX_BITS) | (K)digit);
+                s_need = need - above;
+            }
+            __syncthreads();
+            prefix = s_prefix;
+            need = s_need;
+            __syncthreads();
+        }
+        thr = prefix;
+    }
+
+    // ---- W: the columns above the threshold, plus the kept ties (one weight each)
+    T part = (T)0;
+    for (int64_t i = tid; i < V; i += THREADS) {
+        const T z = tempered(x[i], temperature);
+        if (all || Key<T>::of(z) > thr) part += Math<T>::exp_(z - zmax);
+    }
+    part = tnn::wave_sum(part);
+    if (lane == 0) s_val[wave] = part;
+    __syncthreads();
+    T total = (T)0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) total += s_val[w];
+    __syncthreads();
+    if (!all) total += (T)need * Math<T>::exp_(Key<T>::value(thr) - zmax);
+    const T target = uniform[blockIdx.x] * total;
+
+    // ---- the ordered scan: the first kept column whose running sum exceeds the target
+    T carry = (T)0;
+    unsigned int ties = 0;
+    int found = 0x7fffffff, last = -1;
+    for (int64_t tile = 0; tile < V; tile += THREADS * ITEMS) {  // (workgroup-uniform trip count)
+        const int64_t i0 = tile + tid * ITEMS;
+        T w[ITEMS];
+        bool tie[ITEMS], kept[ITEMS];
+        unsigned int mine = 0;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            w[i] = (T)0; tie[i] = false; kept[i] = false;
+            if (i0 + i < V) {
+                const T z = tempered(x[i0 + i], temperature);
+                const K key = Key<T>::of(z);
+                kept[i] = all || key > thr;
+                tie[i] = !all && key == thr;
+                if (kept[i] || tie[i]) w[i] = Math<T>::exp_(z - zmax);
+                mine += tie[i] ? 1u : 0u;
+            }
+        }
+        if (!all) {                                            // rank the ties by index: the `need` lowest are kept
+            unsigned int tile_ties;
+            unsigned int rank = ties + block_excl_scan<unsigned int>(mine, s_cnt, tile_ties);
+#pragma unroll
+            for (int i = 0; i < ITEMS; ++i) {
+                if (tie[i]) {
+                    kept[i] = rank < need;
+                    if (!kept[i]) w[i] = (T)0;
+                    ++rank;
+                }
+            }
+            ties += tile_ties;
+        }
+        T sum = (T)0;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) sum += w[i];
+        T tile_sum;
+        T run = carry + block_excl_scan<T>(sum, s_val, tile_sum);
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) {
+            run += w[i];
+            if (kept[i] && w[i] > (T)0) {
+                last = (int)(i0 + i);
+                if (run > target && found == 0x7fffffff) found = (int)(i0 + i);
+            }
+        }
+        carry += tile_sum;
+    }
+    found = tnn::wave_min(found);
+    last = tnn::wave_max(last);
+    if (lane == 0) { s_idx[wave] = found; s_cnt[wave] = (unsigned int)(last + 1); }
+    __syncthreads();
+    if (tid == 0) {
+        int f = s_idx[0];
+        unsigned int e = s_cnt[0];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) {
+            f = s_idx[w] < f ? s_idx[w] : f;
+            e = s_cnt[w] > e ? s_cnt[w] : e;
+        }
+        out[blockIdx.x] = f != 0x7fffffff ? f : (int)e - 1;
+    }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (TNN_DECODE_VEC - 1)) == 0; }
+inline int64_t item_of(int dtype) { return dtype == TNN_F32 ? 4 : 8; }
+inline int64_t round16(int64_t n) { return (n + 15) / 16 * 16; }
+inline int64_t decode_space(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype) {
+    return splits == 1 ? 0 : round16(B * H * splits * (Dv + 2) * item_of(dtype));
+}
+
+template <typename T>
+void launch_decode(const DecodeArgs& a, bool vec, int R, dim3 grid) {
+    hipStream_t s = tnn::stream();
+    if (vec) hipLaunchKernelGGL((decode_kernel<T, true, 1>), grid, dim3(THREADS), 0, s, a);
+    else if (R == 1) hipLaunchKernelGGL((decode_kernel<T, false, 1>), grid, dim3(THREADS), 0, s, a);
+    else hipLaunchKernelGGL((decode_kernel<T, false, 2>), grid, dim3(THREADS), 0, s, a);
+}
+
+}  // namespace
+
+#define TNN_DECODE_DTYPE(name) \
+    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, name ": dtype %d (float32 and float64 only)", dtype)
+
+extern "C" int tnn_decode_attn_workspace(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype, int64_t* bytes) {
+    TNN_REQUIRE(bytes != nullptr, "tnn_decode_attn_workspace: null result pointer");
+    TNN_DECODE_DTYPE("tnn_decode_attn_workspace");
+    TNN_REQUIRE(B >= 0 && H >= 0 && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM && splits >= 1 && splits <= TNN_DECODE_MAX_SPLITS,
+                "tnn_decode_attn_workspace: B %lld, H %lld, Dv %lld, splits %lld (Dv <= %d, splits <= %d)", (long long)B,
+                (long long)H, (long long)Dv, (long long)splits, TNN_ATTN_MAX_HEAD_DIM, TNN_DECODE_MAX_SPLITS);
+    *bytes = decode_space(B, H, splits, Dv, dtype);
+    return 0;
+}
+
+extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o,
+                               void* workspace, int64_t workspace_bytes, int64_t B, int64_t H, int64_t len, int64_t Tmax,
+                               int64_t D, int64_t Dv, const int64_t* strides, double scale, int64_t splits, int dtype) {
+    TNN_NEED_INIT();
+    TNN_DECODE_DTYPE("tnn_decode_attn");
+    TNN_REQUIRE(B >= 0 && H >= 0 && B * H < 65536 && D >= 1 && D <= TNN_ATTN_MAX_HEAD_DIM && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM,
+                "tnn_decode_attn: B %lld, H %lld, D %lld, Dv %lld (B H < 65536, 1 <= D, Dv <= %d)", (long long)B, (long long)H,
+                (long long)D, (long long)Dv, TNN_ATTN_MAX_HEAD_DIM);
+    TNN_REQUIRE((k_new == nullptr) == (v_new == nullptr), "tnn_decode_attn: k_new and v_new come together or not at all");
+    const bool append = k_new != nullptr;
+    TNN_REQUIRE(Tmax >= 1 && len >= 0 && (append ? len < Tmax : (len >= 1 && len <= Tmax)),
+                "tnn_decode_attn: len %lld with a cache of %lld rows (%s)", (long long)len, (long long)Tmax,
+                append ? "the appended row needs len < Tmax" : "without k_new / v_new: 1 <= len <= Tmax");
+    const int64_t nkeys = len + (append ? 1 : 0), chunks = (nkeys + TNN_DECODE_CHUNK - 1) / TNN_DECODE_CHUNK;
+    const int64_t most = chunks < TNN_DECODE_MAX_SPLITS ? chunks : TNN_DECODE_MAX_SPLITS;
+    TNN_REQUIRE(splits >= 1 && splits <= most, "tnn_decode_attn: splits %lld outside [1, %lld] (%lld chunks of %d keys)",
+                (long long)splits, (long long)most, (long long)chunks, TNN_DECODE_CHUNK);
+    if (B * H == 0) return 0;
+    TNN_REQUIRE(q && k_cache && v_cache && o && strides, "tnn_decode_attn: null operand");
+    const int64_t need = decode_space(B, H, splits, Dv, dtype);
+    TNN_REQUIRE(splits == 1 || (workspace != nullptr && workspace_bytes >= need && aligned16(workspace)),
+                "tnn_decode_attn: workspace of %lld bytes, %lld needed (16-byte aligned)", (long long)workspace_bytes,
+                (long long)need);
+
+    DecodeArgs a = {};
+    a.q = q; a.k_new = k_new; a.v_new = v_new; a.k_cache = k_cache; a.v_cache = v_cache; a.o = o; a.ws = workspace;
+    const int64_t* st = strides;
+    a.sq[0] = st[0]; a.sq[1] = st[1];
+    a.skn[0] = st[3]; a.skn[1] = st[4];
+    a.svn[0] = st[6]; a.svn[1] = st[7];
+    for (int i = 0; i < 3; ++i) { a.skc[i] = st[9 + i]; a.svc[i] = st[12 + i]; }
+    a.so[0] = st[15]; a.so[1] = st[16];
+    a.nkeys = nkeys; a.len = len; a.chunks = chunks; a.splits = splits;
+    a.H = (int)H; a.D = (int)D; a.Dv = (int)Dv; a.scale = scale;
+
+    const int64_t per = TNN_DECODE_VEC / item_of(dtype);
+    bool vec = D % per == 0 && Dv % per == 0 && aligned16(q) && aligned16(k_cache) && aligned16(v_cache) && aligned16(o) &&
+               aligned16(k_new) && aligned16(v_new);
+    for (int i = 0; i < 2 && vec; ++i)
+        vec = a.sq[i] % per == 0 && a.so[i] % per == 0 && (!append || (a.skn[i] % per == 0 && a.svn[i] % per == 0));
+    for (int i = 0; i < 3 && vec; ++i) vec = a.skc[i] % per == 0 && a.svc[i] % per == 0;
+    const int64_t widest = D > Dv ? D : Dv, packs = vec ? widest / per : widest;
+    const int R = packs > 64 ? 2 : 1;
+    const int64_t lanes = (packs + R - 1) / R;
+    a.G = 1; a.log_g = 0;
+    while (a.G < lanes) { a.G <<= 1; ++a.log_g; }
+
+    const dim3 grid((unsigned)splits, (unsigned)(B * H));
+    if (dtype == TNN_F32) launch_decode<float>(a, vec, R, grid);
+    else launch_decode<double>(a, vec, R, grid);
+    TNN_LAUNCH_OK();
+    if (splits > 1) {
+        if (dtype == TNN_F32) hipLaunchKernelGGL(decode_combine_kernel<float>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
+        else hipLaunchKernelGGL(decode_combine_kernel<double>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
+        TNN_LAUNCH_OK();
+    }
+    return 0;
+}
+
+extern "C" int tnn_sample_rows(const void* logits, const void* u, void* out_ids, int64_t M, int64_t V, double temperature,
+                               int64_t top_k, int dtype) {
+    TNN_NEED_INIT();
+    TNN_DECODE_DTYPE("tnn_sample_rows");
+    TNN_REQUIRE(M >= 0 && V >= 1 && V < (1ll << 31), "tnn_sample_rows: M %lld, V %lld (1 <= V < 2^31)", (long long)M, (long long)V);
+    TNN_REQUIRE(temperature >= 0.0 && temperature < INFINITY, "tnn_sample_rows: temperature %g (finite, >= 0)", temperature);
+    TNN_REQUIRE(top_k >= 0, "tnn_sample_rows: top_k %lld (0: every column)", (long long)top_k);
+    if (M == 0) return 0;
+    TNN_REQUIRE(logits && out_ids && (u || temperature == 0.0), "tnn_sample_rows: null operand");
+    const int k = top_k >= V ? 0 : (int)top_k;
+    if (dtype == TNN_F32)
+        hipLaunchKernelGGL(sample_kernel<float>, dim3((unsigned)M), dim3(THREADS), 0, tnn::stream(), static_cast<const float*>(logits),
+                           static_cast<const float*>(u), static_cast<int64_t*>(out_ids), (int)V, (float)temperature, k);
+    else
+        hipLaunchKernelGGL(sample_kernel<double>, dim3((unsigned)M), dim3(THREADS), 0, tnn::stream(), static_cast<const double*>(logits),
+                           static_cast<const double*>(u), static_cast<int64_t*>(out_ids), (int)V, temperature, k);
+    TNN_LAUNCH_OK();
+    return 0;
+}

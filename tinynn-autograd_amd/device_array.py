@@ -29,6 +29,7 @@ from . import _lib
 from . import attention as _at
 from . import batching as _bt
 from . import conv as _cv
+from . import decoding as _dc
 from . import indexing as _ix
 from . import norm as _nm
 from . import tokens as _tk
@@ -1882,6 +1883,97 @@ def cross_entropy_bwd(logits, targets, lse, count, g=1.0, ignore_index=None, red
     rows = asarray(valid.astype(dt).reshape(plan.M, 1) * (1.0 / n if reduction == "mean" else 1.0), dtype=dt)
     g = g if g._hv is not None else g.astype(dt).reshape(1, 1)
     return ((p - asarray(one_hot.astype(dt), dtype=dt)) * rows * g).reshape(plan.logits_shape)
+
+
+# ---------------------------------------------------------------------- kernels: decode attention, sampling (csrc/tnn_decode.hip)
+DECODE_ROUTE = None   # tests / probes: "native" or "composed" overrides the planner's choice (decoding.py)
+
+
+def _decode_cache(a, dt, what):
+    """A cache is written IN PLACE: it must already be a dense device array of the operand dtype (a copy would lose the row)."""
+    if not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != dt:
+        raise TypeError("attention_decode: %s must be a dense device array of dtype %s (it is written in place)" % (what, dt))
+    return a
+
+
+def attention_decode(q, k_cache, v_cache, length, k_new=None, v_new=None, scale=None, layout="bthd", route=None, splits=None):
+    """o [B, H, Dv] = softmax(scale q k^T) v for ONE query per (batch, head) over the live rows of a key / value cache
+    (decoding.py: layouts, the key split, the routes).  q [B, H, D].  With k_new [B, H, D] and v_new [B, H, Dv] the step's own
+    row is written into cache row `length` — the caches are modified in place — and the keys are [0, length]; without them
+    the keys are [0, length).  `length` is a host integer.  Native: ONE tnn_decode_attn call (a second small launch inside
+    it when the keys are split), nothing synchronises; composed: a slice assignment of the new row, then attention() on its
+    composed route over the live prefix.  The workspace of a split call comes from the buffer cache."""
+    if (k_new is None) != (v_new is None):
+        raise ValueError("attention_decode: k_new and v_new come together or not at all")
+    append = k_new is not None
+    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
+    dt = cands[0] if cands else _default_float
+    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
+    q = asarray(q)._as_float(dt)._contig()
+    if append:
+        k_new, v_new = asarray(k_new)._as_float(dt)._contig(), asarray(v_new)._as_float(dt)._contig()
+    lib = _lib.get()
+    plan = _dc.plan_decode(q.shape, k_cache.shape, v_cache.shape, length, append, k_new.shape if append else None,
+                           v_new.shape if append else None, scale, layout, splits, native=lib.has_decode,
+                           float_ok=dt in (np.dtype(np.float32), np.dtype(np.float64)), route=route or DECODE_ROUTE)
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        nbytes = plan.workspace_bytes(dt.itemsize)
+        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+        lib.decode_attn(q._ptr, _ptr_of(k_new), _ptr_of(v_new), k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
+                        *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
+        return out
+    n, b, h = plan.keys, plan.B, plan.H
+    if plan.route == "fwd":                                    # the route that existed before: tnn_attn_fwd with Tq = 1, in place
+        if append:
+            row = (slice(None), plan.length) if layout == "bthd" else (slice(None), slice(None), plan.length)
+            k_cache[row] = k_new
+            v_cache[row] = v_new
+        out, lse = DeviceArray._new(plan.out_shape, dt), DeviceArray._new((b, h, 1), dt)
+        lib.attn_fwd(q._ptr, k_cache._ptr, v_cache._ptr, out._ptr, lse._ptr, b, h, 1, n, plan.D, plan.Dv,
+                     _i64arr(plan.q_strides + plan.kcache_strides + plan.vcache_strides + plan.o_strides), plan.scale, 0,
+                     out._code())
+        return out
+    if layout == "bthd":
+        if append:
+            k_cache[:, plan.length] = k_new
+            v_cache[:, plan.length] = v_new
+        o, _ = attention(q.reshape(b, 1, h, plan.D), k_cache[:, :n], v_cache[:, :n], False, plan.scale, "bthd", "composed")
+    else:
+        if append:
+            k_cache[:, :, plan.length] = k_new
+            v_cache[:, :, plan.length] = v_new
+        o, _ = attention(q.reshape(b, h, 1, plan.D), k_cache[:, :, :n], v_cache[:, :, :n], False, plan.scale, "bhtd", "composed")
+    return o.reshape(plan.out_shape)
+
+
+def sample_rows(logits, u, temperature=1.0, top_k=None, route=None):
+    """ids int64 [M] on the device: one token per row of logits [M, V] from one uniform number u[m] in [0, 1) (decoding.py and
+    include/tnn_decode.h state the rule: greedy at temperature 0, else the inverse CDF of softmax(x / temperature) over the
+    top_k largest).  Native: ONE tnn_sample_rows launch — nothing is read back, the ids can feed embedding() as they are.
+    Composed: the logits (and u) are READ BACK and the rule runs in numpy; that is a host synchronisation and cannot be
+    captured into a graph."""
+    dt, (x,) = _norm_operands(logits)
+    lib = _lib.get()
+    greedy = float(temperature) == 0.0
+    ud = None
+    if not greedy:
+        if u is None:
+            raise ValueError("sample_rows: u is needed unless temperature is 0")
+        ud = asarray(u)._as_float(dt)._contig()
+    plan = _dc.plan_sample(x.shape, None if ud is None else ud.shape, temperature, top_k, dt.itemsize, native=lib.has_decode,
+                           route=route or DECODE_ROUTE)
+    if plan.empty():
+        return zeros((0,), np.int64)
+    if plan.route == "native":
+        out = DeviceArray._new((plan.M,), np.int64)
+        lib.sample_rows(x._ptr, _ptr_of(ud), out._ptr, plan.M, plan.V, plan.temperature, plan.top_k, x._code())
+        return out
+    if _lib.capturing:
+        raise RuntimeError("sample_rows (composed route) reads the logits back to the host, which a graph capture cannot do")
+    return asarray(_dc.sample_host(np.asarray(x), None if ud is None else np.asarray(ud), plan.temperature, plan.top_k))
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)

@@ -4,6 +4,10 @@ and generated here: each sequence repeats a random motif of `period` tokens draw
 token — so every position >= period can be predicted by attending one period back, and the first `period` cannot.
 
     python tinynn-autograd_amd/examples/charlm_run.py [--num_ep 4] [--batch_size 64] [--n_train 2048] [--lr 3e-3] [--seed 0]
+
+--generate N: after training, the first test sequences are continued greedily by N tokens from a prompt of 2 * period tokens
+(generation.generate: a key / value cache, every token chosen on the device), and the share of generated tokens that continue
+the motif is printed.
 """
 
 import argparse
@@ -18,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import tinynn_autograd_amd as tn                                                            # noqa: E402
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
+from tinynn_autograd_amd.generation import generate                                         # noqa: E402
 from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
 from tinynn_autograd_amd.core.losses import CrossEntropyLoss                                # noqa: E402
 from tinynn_autograd_amd.core.model import Model                                            # noqa: E402
@@ -81,6 +86,21 @@ def main(args):
         accuracy = float(hit[:, args.period:].mean())         # the positions whose next token the context determines
         history.append((mean, accuracy))
         print("epoch %d: mean loss %.4f, accuracy on predictable positions %.4f, %.2f s" % (epoch, mean, accuracy, time.time() - t0))
+    args.generation = None              # with --generate: (ids [rows, prompt + N], share of motif continuations)
+    if args.generate <= 0:
+        return history
+    prompt_len = 2 * args.period
+    if prompt_len + args.generate > args.seq:
+        raise ValueError("--generate %d: %d prompt + %d new tokens exceed --seq %d (the learned positions)"
+                         % (args.generate, prompt_len, args.generate, args.seq))
+    rows = test_x[:min(len(test_x), 8)]
+    out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0)
+    motif = rows[:, np.arange(prompt_len, prompt_len + args.generate) % args.period]     # what repeating the motif gives
+    share = float((out[:, prompt_len:] == motif).mean())
+    for row in out:
+        print("  %s | %s" % (" ".join("%2d" % t for t in row[:prompt_len]), " ".join("%2d" % t for t in row[prompt_len:])))
+    print("generated %d tokens for %d sequences: %.4f of them continue the motif" % (args.generate, len(out), share))
+    args.generation = (out, share)
     return history
 
 
@@ -97,6 +117,7 @@ def parse(argv=None):
     parser.add_argument("--heads", default=4, type=int)
     parser.add_argument("--period", default=4, type=int)
     parser.add_argument("--seed", default=0, type=int)
+    parser.add_argument("--generate", default=0, type=int, help="continue the first test sequences greedily by N tokens")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
     return parser.parse_args(argv)
 
