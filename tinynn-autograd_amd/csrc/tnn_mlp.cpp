@@ -8,20 +8,22 @@
 // (core/layers.py:34-35).  grads[n_params] is one extra slot that carries this shard's loss so the
 // data-parallel all-reduce of the gradient arena also sums the loss for free.
 //
-// Per step (L Dense layers, ReLU between them):
-//   forward  : L  x  gemm_bias_act (NN, bias + ReLU fused, ReLU mask kept in the sign bit of 0)
-//   head     : mlp_head = last Dense forward + softmax NLL + its backward in one launch (unsharded);
-//              sharded: gemm_bias_act | softmax_nll_stats | exchange | softmax_nll_fwd_bwd | dense_bwd
-//   (loss    : softmax_nll_fused (sharded: softmax_nll_stats | exchange | softmax_nll_fwd_bwd) or mse_fwd_bwd
-//   backward : L  x  dense_bwd (dW = X^T dZ, db = column-sum dZ, dX = (dZ W^T)*mask in one launch when small)
-//   update   : 1  x  fused Adam / SGD over the whole arena
+// Step forms (L Dense layers, ReLU between them) with their launches per step; select_step / select_sharded_step pick one and
+// the function named here, which carries the form's own comment, issues it (tests/test_mlp_step_trace.py pins every sequence):
+//   step_merged_head          softmax + Adam, <= 128 rows, a head of the multi-workgroup head kernels: 2L - 2 (4 for MNIST)
+//   step_row_blocks           the same heads, 129 .. 1024 rows: 2L - 2
+//   step_one_workgroup_loss   softmax + Adam, a head of the one-workgroup loss kernel: 2L + 1
+//   step_head_fallback        any other softmax net or optimizer: 2L;  step_phases: sum-of-squares loss, the public phases in a row
+//   step_large_adam_epilogue  fp32, >= 2^22 parameters, gradients not kept: Adam in the dW epilogues, no optimizer launch
+//   mlp16_step_fused / _long  bf16, gradients not kept: 4L + 1 (TNN_E_STEP=ct: 3L + 1) / separate launches
+//   sharded_merged_head       data parallel, the merged head on every transport: 2L - 1 + the collectives
+//   sharded_one_workgroup_loss / sharded_allreduce / sharded_bucketed / mlp16_step_zero: the other data-parallel forms
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <vector>
-
-#include <stdlib.h>
 
 #include "tnn_hip.h"
 
@@ -93,16 +95,25 @@ struct Mlp {
 
 inline void* at(char* base, int64_t elem_off, size_t esz) { return base + elem_off * (int64_t)esz; }
 
+// ---------------------------------------------------------------- layer slices
+// the same elements of the parameter, gradient and Adam-moment arenas (bf16 mode: the arenas are fp32, esz = 4)
+struct Slices { void *p, *g, *m, *v; };
+inline Slices slices(const Mlp* h, int64_t off) {
+    return {at(h->params, off, h->esz), at(h->grads, off, h->esz), at(h->m, off, h->esz), at(h->v, off, h->esz)};
+}
+inline Slices weights(const Mlp* h, int l) { return slices(h, h->w_off[l]); }     // W_l [w[l], w[l+1]]
+inline Slices bias(const Mlp* h, int l) { return slices(h, h->b_off[l]); }        // b_l [1, w[l+1]]
+inline void* loss_slot(const Mlp* h) { return at(h->grads, h->n_params, h->esz); }
+// input of layer l: the batch, or the activations of the layer below
+inline const void* layer_in(const Mlp* h, int l, const void* x) { return l == 0 ? x : h->act[l - 1]; }
+
 int mlp_forward(Mlp* h, const void* x, int64_t rows, int n_layers = -1) {
     const void* in = x;
     if (n_layers < 0) n_layers = h->L;
     for (int l = 0; l < n_layers; ++l) {
         bool hidden = l < h->L - 1;
-        STEP_CALL(h, tnn_gemm_bias_act(0, 0, rows, h->w[l + 1], h->w[l], in, h->w[l],
-                                       at(h->params, h->w_off[l], h->esz), h->w[l + 1],
-                                       at(h->params, h->b_off[l], h->esz),
-                                       hidden ? TNN_ACT_RELU : TNN_ACT_NONE, hidden ? 1 : 0, h->act[l],
-                                       h->w[l + 1], h->dtype));
+        STEP_CALL(h, tnn_gemm_bias_act(0, 0, rows, h->w[l + 1], h->w[l], in, h->w[l], weights(h, l).p, h->w[l + 1], bias(h, l).p,
+                                       hidden ? TNN_ACT_RELU : TNN_ACT_NONE, hidden ? 1 : 0, h->act[l], h->w[l + 1], h->dtype));
         in = h->act[l];
     }
     return 0;
@@ -114,7 +125,7 @@ int allreduce_layer_bucket(Mlp* h, int l) {
     const int64_t first = h->w_off[l];
     int64_t count = h->w[l] * h->w[l + 1] + h->w[l + 1];
     if (l == h->L - 1) count = h->n_params + 1 - first;
-    return tnn_allreduce_async(at(h->grads, first, h->esz), count, h->bf16 ? TNN_F32 : h->dtype, TNN_RSUM);
+    return tnn_allreduce_async(weights(h, l).g, count, h->bf16 ? TNN_F32 : h->dtype, TNN_RSUM);
 }
 
 // gradients of every layer from dact[L-1] (set by the loss kernel) down to layer 0
@@ -122,23 +133,89 @@ int allreduce_layer_bucket(Mlp* h, int l) {
 int mlp_backward_layers(Mlp* h, const void* x, int64_t rows, int from_layer = -1, int to_layer = 0, bool bucket = false) {
     if (from_layer < 0) from_layer = h->L - 1;
     for (int l = from_layer; l >= to_layer; --l) {
-        const void* in = l == 0 ? x : h->act[l - 1];
         // dW_l = in^T d, db_l = column-sum d, dZ_{l-1} = (d W_l^T) * [z_{l-1} >= 0]  — one launch per layer
-        STEP_CALL(h, tnn_dense_bwd(rows, h->w[l], h->w[l + 1], in, h->dact[l], at(h->params, h->w_off[l], h->esz),
-                                   at(h->grads, h->w_off[l], h->esz), at(h->grads, h->b_off[l], h->esz),
-                                   l > 0 ? h->dact[l - 1] : nullptr, l > 0 ? h->act[l - 1] : nullptr, h->dtype));
+        STEP_CALL(h, tnn_dense_bwd(rows, h->w[l], h->w[l + 1], layer_in(h, l, x), h->dact[l], weights(h, l).p, weights(h, l).g,
+                                   bias(h, l).g, l > 0 ? h->dact[l - 1] : nullptr, l > 0 ? h->act[l - 1] : nullptr, h->dtype));
         if (bucket) MLP_TRY(allreduce_layer_bucket(h, l));
     }
     return 0;
 }
 
+// ---------------------------------------------------------------- emitters: a launch several step forms issue, written once
+// An emitter only makes the call; its caller counts it under the launch window (STEP_CALL, tnn_mlp_step) or not (MLP_TRY).
+
+// the first layer's backward with the whole Adam step in its launch (its W / b in the dW epilogue, the rest by trailing blocks)
+int emit_bwd_first_adam(Mlp* h, const void* x, int64_t rows) {
+    const int64_t rest_off = h->L > 1 ? h->w_off[1] : h->n_params;
+    const Slices W = weights(h, 0), b = bias(h, 0), rest = slices(h, rest_off);
+    return tnn_dense_bwd_first_adam(rows, h->w[0], h->w[1], x, h->dact[0], h->keep_grads ? W.g : nullptr, b.g, W.p, W.m, W.v,
+                                    b.p, b.m, b.v, rest.p, rest.g, rest.m, rest.v, h->n_params - rest_off, h->lr, h->b1, h->b2,
+                                    h->eps, h->pows, h->dtype);
+}
+
+// the same with the all-reduce of the gradient arena and the loss in it
+int emit_bwd_first_allreduce_adam(Mlp* h, const void* x, int64_t rows, void* loss_out) {
+    return tnn_dense_bwd_first_allreduce_adam(rows, h->w[0], h->w[1], x, h->dact[0], h->grads, h->n_params + 1, h->w_off[0],
+                                              h->b_off[0], h->params, h->m, h->v, h->n_params, h->lr, h->b1, h->b2, h->eps,
+                                              h->pows, h->n_params, loss_out, h->dtype);
+}
+
+// Forward of the hidden layer in front of the classifier, which also leaves the logits in h->zpart: as per-tile partial sums
+// (_partials; _partials_stats: + the shard's {max, sum-exp} per 128-row block at the tail of the launch) or whole, in row panels
+// (_rows_head_stats: one pair per 16-row panel; _merged: + the pairs, behind the merged one in h->stats, merged at the tail).
+// exchange: 0 the tail keeps the shard's pair, 1 exchanges and merges it with the peers', 2 no statistics tail (the head does it)
+#define HEAD_FWD_ARGS(h, rows, in)                                                                                        \
+    rows, h->w[h->L - 1], h->w[h->L - 2], in, h->w[h->L - 2], weights(h, h->L - 2).p, h->w[h->L - 1], bias(h, h->L - 2).p, \
+        TNN_ACT_RELU, 1, h->act[h->L - 2], h->w[h->L - 1], weights(h, h->L - 1).p, h->w[h->L], h->zpart
+int emit_fwd_head_partials(Mlp* h, const void* x, int64_t rows) {
+    return tnn_dense_fwd_head_partials(HEAD_FWD_ARGS(h, rows, layer_in(h, h->L - 2, x)), h->dtype);
+}
+int emit_fwd_head_partials_stats(Mlp* h, int64_t rows, const void* y, int exchange) {
+    return tnn_dense_fwd_head_partials_stats(HEAD_FWD_ARGS(h, rows, h->act[h->L - 3]), bias(h, h->L - 1).p, y, h->ticket,
+                                             h->stats, exchange, h->dtype);
+}
+int emit_fwd_rows_head_stats(Mlp* h, int64_t rows) {
+    return tnn_dense_fwd_rows_head_stats(HEAD_FWD_ARGS(h, rows, h->act[h->L - 3]), bias(h, h->L - 1).p, h->stats, h->dtype);
+}
+inline void* panel_pairs(const Mlp* h) { return (char*)h->stats + 16; }
+int emit_fwd_rows_head_stats_merged(Mlp* h, int64_t rows, int exchange) {
+    return tnn_dense_fwd_rows_head_stats_merged(HEAD_FWD_ARGS(h, rows, h->act[h->L - 3]), bias(h, h->L - 1).p, panel_pairs(h),
+                                                h->ticket, h->stats, exchange, h->dtype);
+}
+#undef HEAD_FWD_ARGS
+
+// The merged head + hidden-backward launch.  Its softmax statistics: reduced inside the launch (emit_head_bwd_tick, <= 128 rows
+// on one GPU), taken from memory (Memory: tnn_mlp_head_bwd_tick_ext; n_pairs < 0: -n_pairs panel pairs, whole logits), or reduced
+// and exchanged with the peers inside the launch (Exchange: tnn_mlp_head_bwd_tick_xchg; n_pairs 0: from the partial logits)
+int emit_head_bwd_tick(Mlp* h, int64_t rows, const void* y, void* loss) {
+    const int L = h->L;
+    return tnn_mlp_head_bwd_tick(rows, h->w[L - 2], h->w[L - 1], h->w[L], h->act[L - 3], weights(h, L - 2).p, h->act[L - 2],
+                                 weights(h, L - 1).p, bias(h, L - 1).p, y, h->zpart, h->act[L - 1], h->dact[L - 1], h->stats, loss,
+                                 weights(h, L - 1).g, bias(h, L - 1).g, weights(h, L - 2).g, bias(h, L - 2).g, h->dact[L - 3],
+                                 h->dtype, h->pows, h->b1, h->b2);
+}
+enum class HeadStats { Memory, Exchange };
+int emit_head_bwd_tick_from(Mlp* h, HeadStats from, int64_t rows, int64_t m_global, const void* y, const void* pairs, int n_pairs,
+                            void* loss) {
+    const int L = h->L;
+#define HEAD_BWD_ARGS                                                                                                              \
+    rows, m_global, h->w[L - 2], h->w[L - 1], h->w[L], h->act[L - 3], weights(h, L - 2).p, h->act[L - 2], weights(h, L - 1).p,      \
+        bias(h, L - 1).p, y, h->zpart, pairs, n_pairs, h->act[L - 1], h->dact[L - 1], nullptr, loss, weights(h, L - 1).g,           \
+        bias(h, L - 1).g, weights(h, L - 2).g, bias(h, L - 2).g, h->dact[L - 3], h->dtype, h->pows, h->b1, h->b2
+    return from == HeadStats::Exchange ? tnn_mlp_head_bwd_tick_xchg(HEAD_BWD_ARGS) : tnn_mlp_head_bwd_tick_ext(HEAD_BWD_ARGS);
+#undef HEAD_BWD_ARGS
+}
+
 // ---------------------------------------------------------------- bf16 mode
 inline void* at16(char* base, int64_t elem_off) { return base + elem_off * 2; }
+inline void* w16_of(const Mlp* h, int l) { return at16(h->w16, h->w_off[l]); }     // bf16 working copy of W_l [in,out]
+inline void* b16_of(const Mlp* h, int l) { return at16(h->w16, h->b_off[l]); }
+// the K-contiguous left operand of dW_l: the layer's input transposed
+inline void* layer_inT16(const Mlp* h, int l) { return l == 0 ? h->xT16 : h->actT16[l - 1]; }
 
 int mlp16_sync(Mlp* h) {      // refresh the bf16 working copies from the fp32 master parameters
     MLP_TRY(tnn_cast_bf16(h->params, h->w16, h->n_params, 1));
-    for (int l = 0; l < h->L; ++l)
-        MLP_TRY(tnn_transpose_bf16(at16(h->w16, h->w_off[l]), h->wT16[l], h->w[l], h->w[l + 1]));
+    for (int l = 0; l < h->L; ++l) MLP_TRY(tnn_transpose_bf16(w16_of(h, l), h->wT16[l], h->w[l], h->w[l + 1]));
     return 0;
 }
 
@@ -151,14 +228,41 @@ int mlp16_forward(Mlp* h, const void* x16, int64_t rows, bool emit_t = false) {
         // z_l = a_{l-1} W_l + b_l : A = a [rows, in] (K = in), B = W_l^T [out, in]
         if (emit_t && hidden)
             STEP_CALL(h, tnn_gemm_bf16_nt_t(rows, h->w[l + 1], h->w[l], in, h->w[l], h->wT16[l], h->w[l], h->act[l], h->w[l + 1],
-                                       at(h->params, h->b_off[l], 4), TNN_ACT_RELU, 1, nullptr, 0, h->actT16[l], rows));
+                                       bias(h, l).p, TNN_ACT_RELU, 1, nullptr, 0, h->actT16[l], rows));
         else
-            STEP_CALL(h, tnn_gemm_bf16_nt(rows, h->w[l + 1], h->w[l], in, h->w[l], h->wT16[l], h->w[l], h->act[l],
-                                     h->w[l + 1], TNN_BF16, at(h->params, h->b_off[l], 4),
-                                     hidden ? TNN_ACT_RELU : TNN_ACT_NONE, hidden ? 1 : 0, nullptr, 0));
+            STEP_CALL(h, tnn_gemm_bf16_nt(rows, h->w[l + 1], h->w[l], in, h->w[l], h->wT16[l], h->w[l], h->act[l], h->w[l + 1],
+                                     TNN_BF16, bias(h, l).p, hidden ? TNN_ACT_RELU : TNN_ACT_NONE, hidden ? 1 : 0, nullptr, 0));
         in = h->act[l];
     }
     return 0;
+}
+
+// dz_{l-1} = (dz_l W_l^T) * mask : A = dz_l [rows, out] (K = out), B = W_l [in, out]   (l > 0)
+int emit16_dz_prev(Mlp* h, int l, int64_t rows) {
+    return tnn_gemm_bf16_nt(rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], w16_of(h, l), h->w[l + 1], h->dact[l - 1],
+                            h->w[l], TNN_BF16, nullptr, TNN_ACT_NONE, 0, h->act[l - 1], h->w[l]);
+}
+
+// K-contiguous operands of dW_l = in^T dz, one transpose launch each: in^T [w[l], rows] and dz^T [w[l+1], rows]
+int emit16_dw_operands(Mlp* h, int l, const void* x16, int64_t rows) {
+    MLP_TRY(tnn_transpose_bf16(layer_in(h, l, x16), layer_inT16(h, l), rows, h->w[l]));
+    return tnn_transpose_bf16(h->dact[l], h->dactT16[l], rows, h->w[l + 1]);
+}
+
+// Adam on the fp32 masters of b_l, gradient from grad (refreshes the bias' bf16 copy)
+int emit16_adam_bias(Mlp* h, int l, const void* grad) {
+    const Slices b = bias(h, l);
+    return tnn_adam_master_bf16_2d(b.p, grad, b.m, b.v, b16_of(h, l), nullptr, 1, h->w[l + 1], h->lr, h->b1, h->b2, h->eps,
+                                   h->pows, 0);
+}
+
+// Adam on one layer from the gradient arena: W (also refreshing W^T for the forward GEMM) then b.  advance: first call of the
+// step (advances the beta powers)
+int emit16_adam_layer(Mlp* h, int l, bool advance) {
+    const Slices W = weights(h, l);
+    MLP_TRY(tnn_adam_master_bf16_2d(W.p, W.g, W.m, W.v, w16_of(h, l), h->wT16[l], h->w[l], h->w[l + 1], h->lr, h->b1, h->b2,
+                                    h->eps, h->pows, advance ? 1 : 0));
+    return emit16_adam_bias(h, l, bias(h, l).g);
 }
 
 // The single-GPU bf16 step with the weight gradients consumed where they are produced (tnn_mlp_keep_grads(h, 0)): which form?
@@ -198,41 +302,38 @@ int mlp16_step_form(const Mlp* h, int64_t rows) {
 // Same arithmetic, element for element, in every form (transposes are exact, the bias sums keep their order).
 int mlp16_step_fused(Mlp* h, const void* x16, const void* y16, int64_t rows, void* loss_out, bool ct) {
     const int L = h->L;
-    auto f32 = [](void* base, int64_t off) { return (void*)((float*)base + off); };
     MLP_TRY(mlp16_forward(h, x16, rows, ct));
-    STEP_CALL(h, tnn_mse_bf16_prep(h->act[L - 1], y16, rows, h->w[L], rows, at(h->grads, h->n_params, 4), loss_out, h->dact[L - 1],
+    STEP_CALL(h, tnn_mse_bf16_prep(h->act[L - 1], y16, rows, h->w[L], rows, loss_slot(h), loss_out, h->dact[L - 1],
                                    h->dactT16[L - 1], ct ? x16 : nullptr, h->w[0], ct ? h->xT16 : nullptr, h->prep_ws, h->ticket,
                                    h->pows, h->b1, h->b2));
     for (int l = L - 1; l >= 0; --l) {
-        const void* in = l == 0 ? x16 : h->act[l - 1];
-        void* inT = l == 0 ? h->xT16 : h->actT16[l - 1];
-        const int64_t wo = h->w_off[l];
+        const void* in = layer_in(h, l, x16);
+        void* inT = layer_inT16(h, l);
         if (!ct) {
             if (l < L - 1) STEP_CALL(h, tnn_transpose2_bf16(in, inT, rows, h->w[l], h->dact[l], h->dactT16[l], rows, h->w[l + 1]));
             else STEP_CALL(h, tnn_transpose_bf16(in, inT, rows, h->w[l]));
         }
         if (l > 0) {
             if (ct)
-                STEP_CALL(h, tnn_gemm_bf16_nt_t(rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], at16(h->w16, wo), h->w[l + 1],
+                STEP_CALL(h, tnn_gemm_bf16_nt_t(rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], w16_of(h, l), h->w[l + 1],
                                                 h->dact[l - 1], h->w[l], nullptr, TNN_ACT_NONE, 0, h->act[l - 1], h->w[l],
                                                 h->dactT16[l - 1], rows));
             else
-                STEP_CALL(h, tnn_gemm_bf16_nt(rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], at16(h->w16, wo), h->w[l + 1],
-                                              h->dact[l - 1], h->w[l], TNN_BF16, nullptr, TNN_ACT_NONE, 0, h->act[l - 1], h->w[l]));
+                STEP_CALL(h, emit16_dz_prev(h, l, rows));
         }
         // (W_0's [in, out] bf16 copy has no reader inside a step — dX stops at the input —: not written, 2 of 28 B/param of
         // that layer; tnn_mlp_bf16_weights re-derives it from the masters on request)
-        STEP_CALL(h, tnn_gemm_bf16_nt_adam(h->w[l], h->w[l + 1], rows, inT, rows, h->dactT16[l], rows, nullptr, f32(h->params, wo),
-                                           f32(h->m, wo), f32(h->v, wo), l == 0 ? nullptr : at16(h->w16, wo), h->wT16[l], h->lr,
-                                           h->b1, h->b2, h->eps, h->pows));
+        const Slices W = weights(h, l);
+        STEP_CALL(h, tnn_gemm_bf16_nt_adam(h->w[l], h->w[l + 1], rows, inT, rows, h->dactT16[l], rows, nullptr, W.p, W.m, W.v,
+                                           l == 0 ? nullptr : w16_of(h, l), h->wT16[l], h->lr, h->b1, h->b2, h->eps, h->pows));
     }
     const void* dz[16];
     int64_t cols[16];
     void *db[16], *bp[16], *bm[16], *bv[16], *bw[16];
     for (int l = 0; l < L; ++l) {
-        const int64_t bo = h->b_off[l];
+        const Slices b = bias(h, l);
         dz[l] = h->dact[l]; cols[l] = h->w[l + 1];
-        db[l] = f32(h->grads, bo); bp[l] = f32(h->params, bo); bm[l] = f32(h->m, bo); bv[l] = f32(h->v, bo); bw[l] = at16(h->w16, bo);
+        db[l] = b.g; bp[l] = b.p; bm[l] = b.m; bv[l] = b.v; bw[l] = b16_of(h, l);
     }
     STEP_CALL(h, tnn_bias_bf16_adam_multi(L, dz, rows, cols, db, bp, bm, bv, bw, h->lr, h->b1, h->b2, h->eps, h->pows));
     h->w16_first_stale = true;
@@ -244,49 +345,45 @@ int mlp16_step_fused(Mlp* h, const void* x16, const void* y16, int64_t rows, voi
 int mlp16_backward(Mlp* h, const void* x16, const void* y16, int64_t rows, int64_t m_global, void* loss_out,
                    bool bucket = false, bool fused_adam = false, bool tick = false) {
     const int L = h->L;
-    void* loss_slot = at(h->grads, h->n_params, 4);
     if (h->loss_kind != 1) {
         tnn::set_error("bf16 trainer: only the sum-of-squares loss is implemented");
         return 2;
     }
     // tick: one thread of the loss launch advances Adam's beta powers, its reduction files the loss to loss_out too
-    MLP_TRY(tnn_mse_bf16_tick(h->act[L - 1], y16, rows * h->w[L], m_global, loss_slot, tick ? loss_out : nullptr, h->dact[L - 1],
+    MLP_TRY(tnn_mse_bf16_tick(h->act[L - 1], y16, rows * h->w[L], m_global, loss_slot(h), tick ? loss_out : nullptr, h->dact[L - 1],
                               tick ? h->pows : nullptr, h->b1, h->b2));
     if (tick) loss_out = nullptr;
     for (int l = L - 1; l >= 0; --l) {
-        const void* in = l == 0 ? x16 : h->act[l - 1];
-        void* inT = l == 0 ? h->xT16 : h->actT16[l - 1];
-        // K-contiguous operands of dW_l = in^T dz: in^T [w[l], rows] and dz^T [w[l+1], rows]
-        MLP_TRY(tnn_transpose_bf16(in, inT, rows, h->w[l]));
-        MLP_TRY(tnn_transpose_bf16(h->dact[l], h->dactT16[l], rows, h->w[l + 1]));
-        // dz_{l-1} = (dz_l W_l^T) * mask : A = dz_l [rows, out] (K = out), B = W_l [in, out]
-        auto dz_prev = [&]() -> int {
-            if (l == 0) return 0;
-            return tnn_gemm_bf16_nt(rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], at16(h->w16, h->w_off[l]),
-                                    h->w[l + 1], h->dact[l - 1], h->w[l], TNN_BF16, nullptr, TNN_ACT_NONE, 0,
-                                    h->act[l - 1], h->w[l]);
-        };
+        MLP_TRY(emit16_dw_operands(h, l, x16, rows));
+        const Slices W = weights(h, l), b = bias(h, l);
         if (fused_adam) {
-            const int64_t wo = h->w_off[l], bo = h->b_off[l];
-            auto f32 = [](void* base, int64_t off) { return (void*)((float*)base + off); };
-            MLP_TRY(dz_prev());
-            MLP_TRY(tnn_gemm_bf16_nt_adam(h->w[l], h->w[l + 1], rows, inT, rows, h->dactT16[l], rows,
-                                          h->keep_grads ? f32(h->grads, wo) : nullptr, f32(h->params, wo), f32(h->m, wo),
-                                          f32(h->v, wo), at16(h->w16, wo), h->wT16[l], h->lr, h->b1, h->b2, h->eps, h->pows));
+            if (l > 0) MLP_TRY(emit16_dz_prev(h, l, rows));
+            MLP_TRY(tnn_gemm_bf16_nt_adam(h->w[l], h->w[l + 1], rows, layer_inT16(h, l), rows, h->dactT16[l], rows,
+                                          h->keep_grads ? W.g : nullptr, W.p, W.m, W.v, w16_of(h, l), h->wT16[l], h->lr, h->b1,
+                                          h->b2, h->eps, h->pows));
             // db_l + Adam on b_l in one launch
-            MLP_TRY(tnn_bias_bf16_adam(h->dact[l], rows, h->w[l + 1], f32(h->grads, bo), f32(h->params, bo), f32(h->m, bo),
-                                       f32(h->v, bo), at16(h->w16, bo), h->lr, h->b1, h->b2, h->eps, h->pows));
+            MLP_TRY(tnn_bias_bf16_adam(h->dact[l], rows, h->w[l + 1], b.g, b.p, b.m, b.v, b16_of(h, l), h->lr, h->b1, h->b2,
+                                       h->eps, h->pows));
             continue;
         }
-        MLP_TRY(tnn_gemm_bf16_nt(h->w[l], h->w[l + 1], rows, inT, rows, h->dactT16[l], rows,
-                                 at(h->grads, h->w_off[l], 4), h->w[l + 1], TNN_F32, nullptr, TNN_ACT_NONE, 0,
-                                 nullptr, 0));
-        MLP_TRY(tnn_colsum_bf16(h->dact[l], at(h->grads, h->b_off[l], 4), rows, h->w[l + 1]));
+        MLP_TRY(tnn_gemm_bf16_nt(h->w[l], h->w[l + 1], rows, layer_inT16(h, l), rows, h->dactT16[l], rows, W.g, h->w[l + 1],
+                                 TNN_F32, nullptr, TNN_ACT_NONE, 0, nullptr, 0));
+        MLP_TRY(tnn_colsum_bf16(h->dact[l], b.g, rows, h->w[l + 1]));
         if (bucket) MLP_TRY(allreduce_layer_bucket(h, l));
-        MLP_TRY(dz_prev());
+        if (l > 0) MLP_TRY(emit16_dz_prev(h, l, rows));
     }
-    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot, 4));
+    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot(h), 4));
     return 0;
+}
+
+// bf16 trainer, single GPU, weight gradients not wanted in the arena (tnn_mlp_keep_grads(h, 0)): forward | beta
+// powers | backward with Adam in the dW epilogues — no optimizer launch over the weights, no weight-gradient
+// round trip through HBM (8 of the 36 bytes per parameter and step; measured 8192 x 8192 x 512: 385-405 us against
+// 450-495 for GEMM + optimizer).  With the gradient ALSO stored the fused launch is slower than the two (517 us):
+// keep_grads stays on the separate launches.  (Form 0 of mlp16_step_form; forms 1 and 2: mlp16_step_fused.)
+int mlp16_step_long(Mlp* h, const void* x16, const void* y16, int64_t rows, void* loss_out) {
+    MLP_TRY(mlp16_forward(h, x16, rows));
+    return mlp16_backward(h, x16, y16, rows, rows, loss_out, false, true, true);
 }
 
 int mlp16_update(Mlp* h) {
@@ -295,16 +392,7 @@ int mlp16_update(Mlp* h) {
         return 2;
     }
     // per layer: W (also refreshing W^T for the forward GEMM) then b; the beta powers advance once, up front
-    auto f32 = [](void* base, int64_t off) { return (void*)((float*)base + off); };
-    for (int l = 0; l < h->L; ++l) {
-        const int64_t wo = h->w_off[l], bo = h->b_off[l];
-        MLP_TRY(tnn_adam_master_bf16_2d(f32(h->params, wo), f32(h->grads, wo), f32(h->m, wo), f32(h->v, wo),
-                                        at16(h->w16, wo), h->wT16[l], h->w[l], h->w[l + 1], h->lr, h->b1, h->b2,
-                                        h->eps, h->pows, l == 0));
-        MLP_TRY(tnn_adam_master_bf16_2d(f32(h->params, bo), f32(h->grads, bo), f32(h->m, bo), f32(h->v, bo),
-                                        at16(h->w16, bo), nullptr, 1, h->w[l + 1], h->lr, h->b1, h->b2, h->eps,
-                                        h->pows, 0));
-    }
+    for (int l = 0; l < h->L; ++l) MLP_TRY(emit16_adam_layer(h, l, l == 0));
     return 0;
 }
 
@@ -336,53 +424,44 @@ int mlp16_step_zero(Mlp* h, const void* x16, const void* y16, int64_t rows, int 
         MLP_TRY(tnn_malloc((size_t)(nb + 1) * 4, (void**)&h->bias_g));
     }
     const int64_t nb = h->bias_g_off[L];
-    auto f32 = [](void* base, int64_t off) { return (void*)((float*)base + off); };
     MLP_TRY(mlp16_forward(h, x16, rows));
     MLP_TRY(tnn_mse_bf16_tick(h->act[L - 1], y16, rows * h->w[L], rows * world, h->bias_g + nb, nullptr, h->dact[L - 1], h->pows,
                               h->b1, h->b2));
     int rc = 0, chains = 0;
     for (int l = L - 1; l >= 0 && !rc; --l) {
-        const void* in = l == 0 ? x16 : h->act[l - 1];
-        void* inT = l == 0 ? h->xT16 : h->actT16[l - 1];
         const int64_t wo = h->w_off[l];
-        rc = tnn_transpose_bf16(in, inT, rows, h->w[l]);
-        if (!rc) rc = tnn_transpose_bf16(h->dact[l], h->dactT16[l], rows, h->w[l + 1]);
+        rc = emit16_dw_operands(h, l, x16, rows);
         // dz_{l-1} reads the bf16 W_l that this layer's all-gather rewrites: it is enqueued BEFORE the chain opens
-        if (!rc && l > 0)
-            rc = tnn_gemm_bf16_nt(rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], at16(h->w16, wo), h->w[l + 1],
-                                  h->dact[l - 1], h->w[l], TNN_BF16, nullptr, TNN_ACT_NONE, 0, h->act[l - 1], h->w[l]);
+        if (!rc && l > 0) rc = emit16_dz_prev(h, l, rows);
         if (!rc)
-            rc = tnn_gemm_bf16_nt(h->w[l], h->w[l + 1], rows, inT, rows, h->dactT16[l], rows, at16(h->g16, wo), h->w[l + 1],
-                                  TNN_BF16, nullptr, TNN_ACT_NONE, 0, nullptr, 0);
+            rc = tnn_gemm_bf16_nt(h->w[l], h->w[l + 1], rows, layer_inT16(h, l), rows, h->dactT16[l], rows, at16(h->g16, wo),
+                                  h->w[l + 1], TNN_BF16, nullptr, TNN_ACT_NONE, 0, nullptr, 0);
         if (!rc) rc = tnn_bias_bf16_adam(h->dact[l], rows, h->w[l + 1], h->bias_g + h->bias_g_off[l], nullptr, nullptr, nullptr,
                                          nullptr, h->lr, h->b1, h->b2, h->eps, nullptr);
         if (rc) break;
         const int64_t n_shard = h->w[l] / world * h->w[l + 1], so = wo + (int64_t)rank * n_shard;
+        const Slices shard = slices(h, so);
         rc = tnn_comm_chain_begin();
         if (rc) break;
         rc = tnn_reduce_scatter(at16(h->g16, wo), at16(h->g16, so), n_shard, TNN_BF16);
         if (!rc)
-            rc = tnn_adam_master_g16(f32(h->params, so), at16(h->g16, so), f32(h->m, so), f32(h->v, so), at16(h->w16, so),
-                                     n_shard, h->lr, h->b1, h->b2, h->eps, h->pows);
-        if (!rc) rc = tnn_allgather(at16(h->w16, so), at16(h->w16, wo), n_shard, TNN_BF16);
+            rc = tnn_adam_master_g16(shard.p, at16(h->g16, so), shard.m, shard.v, at16(h->w16, so), n_shard, h->lr, h->b1, h->b2,
+                                     h->eps, h->pows);
+        if (!rc) rc = tnn_allgather(at16(h->w16, so), w16_of(h, l), n_shard, TNN_BF16);
         const int rc_end = tnn_comm_chain_end();
         if (!rc) rc = rc_end;
         ++chains;
     }
     // bias gradients + loss: one small all-reduce on the library stream, the same Adam on every rank
     if (!rc) rc = tnn_allreduce(h->bias_g, nb + 1, TNN_F32, TNN_RSUM);
-    for (int l = 0; l < L && !rc; ++l) {
-        const int64_t bo = h->b_off[l];
-        rc = tnn_adam_master_bf16_2d(f32(h->params, bo), h->bias_g + h->bias_g_off[l], f32(h->m, bo), f32(h->v, bo),
-                                     at16(h->w16, bo), nullptr, 1, h->w[l + 1], h->lr, h->b1, h->b2, h->eps, h->pows, 0);
-    }
+    for (int l = 0; l < L && !rc; ++l) rc = emit16_adam_bias(h, l, h->bias_g + h->bias_g_off[l]);
     // W_l^T for the next forward, layer by layer as the chains land (issue order = last layer first)
     for (int l = L - 1; l >= 0 && !rc && chains > 0; --l, --chains) {
         rc = tnn_comm_wait_oldest();
-        if (!rc) rc = tnn_transpose_bf16(at16(h->w16, h->w_off[l]), h->wT16[l], h->w[l], h->w[l + 1]);
+        if (!rc) rc = tnn_transpose_bf16(w16_of(h, l), h->wT16[l], h->w[l], h->w[l + 1]);
     }
     if (rc) { (void)tnn_comm_join(); return rc; }
-    MLP_TRY(tnn_memcpy_d2d(at(h->grads, h->n_params, 4), h->bias_g + nb, 4));
+    MLP_TRY(tnn_memcpy_d2d(loss_slot(h), h->bias_g + nb, 4));
     if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, h->bias_g + nb, 4));
     h->masters_world = world > 1 ? world : 0;
     return 0;
@@ -417,21 +496,25 @@ int mlp16_gather_masters(Mlp* h) {
 // (tnn_dense_fwd_head_partials_stats) — the exchange needs ONE pair per rank.  Measured, same box, us per step at 256 / 512 /
 // 1024 rows: row-panel forward 26.9 / 34.7 / 45.5, counter tail 29.6 / 38.6 / 54.8, the 7-launch form below 35.4 / 41.4 / 52.7
 // (profiles/r03_rows_sweep.txt; the switches that selected the forms for that sweep are gone).
-bool head_fits_row_blocks(const Mlp* h, int64_t rows, bool sharded) {
+// the heads that launch takes: the tuned 128 -> 10 head, or any head the generic merged kernel takes (tnn_mlp_head_bwd_fits:
+// hidden width a multiple of 16 up to 256, <= 16 classes — the reference's own 30 -> 10, padded to 32)
+bool head_fits_stats_from_memory(const Mlp* h) {
     const int L = h->L;
-    const int64_t row_blocks_max = 1024;             // 8 blocks of 128: the forward tail's counters and pair slots (h->ticket)
-    (void)sharded;
-    // the tuned 128 -> 10 head, or any head the generic merged kernel takes (tnn_mlp_head_bwd_fits: hidden width a multiple of 16
-    // up to 256, <= 16 classes — the reference's own 30 -> 10, padded to 32)
     const bool head_ok = h->w[L - 1] % 16 == 0 && h->w[L - 1] >= 16 && h->w[L - 1] <= 256 && h->w[L] >= 1 && h->w[L] <= 16;
     return h->dtype == TNN_F32 && !h->bf16 && h->opt_kind == 1 && h->loss_kind == 0 && L >= 3 && head_ok &&
-           h->w[L - 2] % 16 == 0 && rows > 128 && rows <= row_blocks_max && rows <= 1024 && h->zpart != nullptr;
+           h->w[L - 2] % 16 == 0 && h->zpart != nullptr;
+}
+const int64_t kRowBlocksMax = 1024;             // 8 blocks of 128: the forward tail's counters and pair slots (h->ticket)
+
+bool head_fits_row_blocks(const Mlp* h, int64_t rows) {
+    return head_fits_stats_from_memory(h) && rows > 128 && rows <= kRowBlocksMax;
 }
 
 // the data-parallel step's merged form (statistics from memory at every row count): the same heads, 1 .. 1024 rows per rank
-bool head_fits_sharded(const Mlp* h, int64_t rows) {
-    return rows <= 128 ? head_fits_row_blocks(h, rows + 128, true) : head_fits_row_blocks(h, rows, true);
-}
+bool head_fits_sharded(const Mlp* h, int64_t rows) { return head_fits_stats_from_memory(h) && rows <= kRowBlocksMax; }
+
+// the tuned 128 -> 10 head, whose hidden layer has a row-panel forward (any other head: the counter tail, one merged pair)
+bool head_is_tuned(const Mlp* h) { return h->w[h->L - 1] == 128 && h->w[h->L] == 10; }
 
 // limits of the single-workgroup loss kernel (tnn_softmax_nll_fused_tick)
 bool head_fits_one_workgroup(const Mlp* h, int64_t rows) {
@@ -444,23 +527,15 @@ bool head_fits_one_workgroup(const Mlp* h, int64_t rows) {
 // Adam on ONE layer's parameters (W_l and b_l are contiguous in the arenas).  advance: first call of the step
 // (advances the beta powers); loss_out: also file the (already reduced) loss.
 int adam_layer(Mlp* h, int l, bool advance, void* loss_out) {
-    const int64_t wo = h->w_off[l], bo = h->b_off[l];
-    void* loss_slot = at(h->grads, h->n_params, h->esz);
     if (h->bf16) {
-        auto f32 = [](void* base, int64_t off) { return (void*)((float*)base + off); };
-        MLP_TRY(tnn_adam_master_bf16_2d(f32(h->params, wo), f32(h->grads, wo), f32(h->m, wo), f32(h->v, wo),
-                                        at16(h->w16, wo), h->wT16[l], h->w[l], h->w[l + 1], h->lr, h->b1, h->b2,
-                                        h->eps, h->pows, advance ? 1 : 0));
-        MLP_TRY(tnn_adam_master_bf16_2d(f32(h->params, bo), f32(h->grads, bo), f32(h->m, bo), f32(h->v, bo),
-                                        at16(h->w16, bo), nullptr, 1, h->w[l + 1], h->lr, h->b1, h->b2, h->eps,
-                                        h->pows, 0));
-        if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot, 4));
+        MLP_TRY(emit16_adam_layer(h, l, advance));
+        if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot(h), 4));
         return 0;
     }
+    const Slices W = weights(h, l);
     const int64_t count = h->w[l] * h->w[l + 1] + h->w[l + 1];
-    return tnn_adam_ex(at(h->params, wo, h->esz), at(h->grads, wo, h->esz), at(h->m, wo, h->esz), at(h->v, wo, h->esz),
-                       count, h->lr, h->b1, h->b2, h->eps, h->pows, nullptr, h->dtype, advance ? 1 : 0,
-                       loss_out ? loss_slot : nullptr, loss_out);
+    return tnn_adam_ex(W.p, W.g, W.m, W.v, count, h->lr, h->b1, h->b2, h->eps, h->pows, nullptr, h->dtype, advance ? 1 : 0,
+                       loss_out ? loss_slot(h) : nullptr, loss_out);
 }
 
 int check_rows(Mlp* h, int64_t rows, const char* fn) {
@@ -468,6 +543,370 @@ int check_rows(Mlp* h, int64_t rows, const char* fn) {
     if (rows <= 0 || rows > h->max_rows) {
         tnn::set_error("%s: rows %lld outside (0, %lld]", fn, (long long)rows, (long long)h->max_rows);
         return 2;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- the public phases
+int mlp_forward_stats(Mlp* h, const void* x, int64_t rows, void* stats) {
+    if (h->bf16) return mlp16_forward(h, x, rows);
+    MLP_TRY(mlp_forward(h, x, rows));
+    if (h->loss_kind == 0)
+        STEP_CALL(h, tnn_softmax_nll_stats(h->act[h->L - 1], rows, h->w[h->L], stats ? stats : h->stats, h->dtype));
+    return 0;
+}
+
+int mlp_backward_impl(Mlp* h, const void* x, const void* y, int64_t rows, int64_t m_global, const void* stats, void* loss_out,
+                      bool bucket) {
+    MLP_TRY(check_rows(h, rows, "tnn_mlp_backward"));
+    if (h->bf16) return mlp16_backward(h, x, y, rows, m_global, loss_out, bucket);
+    const int L = h->L;
+    if (h->loss_kind == 0)
+        STEP_CALL(h, tnn_softmax_nll_fwd_bwd(h->act[L - 1], y, rows, h->w[L], m_global,
+                                             stats ? stats : h->stats, loss_slot(h), h->dact[L - 1], h->dtype));
+    else
+        STEP_CALL(h, tnn_mse_fwd_bwd(h->act[L - 1], y, rows * h->w[L], m_global, loss_slot(h), h->dact[L - 1], h->dtype));
+    MLP_TRY(mlp_backward_layers(h, x, rows, -1, 0, bucket));
+    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot(h), h->esz));
+    return 0;
+}
+
+int mlp_update(Mlp* h) {
+    if (h->bf16) return mlp16_update(h);
+    if (h->opt_kind == 0)
+        STEP_CALL(h, tnn_sgd(h->params, h->grads, h->n_params, h->lr, h->dtype));
+    else if (h->opt_kind >= 2)   // Momentum / RMSProp / Adagrad / Adadelta: m, v are the two state vectors; b1, b2 = a, b
+        STEP_CALL(h, tnn_optim_step(h->opt_kind - 2, h->params, h->grads, h->m, h->v, nullptr, h->n_params, h->lr,
+                                    h->b1, h->b2, h->eps, h->dtype));
+    else
+        STEP_CALL(h, tnn_adam(h->params, h->grads, h->m, h->v, h->n_params, h->lr, h->b1, h->b2, h->eps, h->pows, nullptr, h->dtype));
+    return 0;
+}
+
+// ---------------------------------------------------------------- tnn_mlp_step: which form, then the forms
+enum class StepForm { Bf16Fused, Bf16Long, LargeAdamEpilogue, Phases, MergedHead, RowBlocks, OneWorkgroupLoss, HeadFallback };
+struct Step {
+    StepForm form;
+    bool ct;           // Bf16Fused: a^T / dz^T from the GEMM epilogues (TNN_E_STEP=ct)
+    bool merge_bwd;    // MergedHead: the head launch also carries the backward of the hidden layer in front of it
+};
+
+int select_step(const Mlp* h, int64_t rows, Step* step) {
+    const int L = h->L;
+    const auto pick = [step](StepForm form, bool ct = false, bool merge_bwd = false) { *step = {form, ct, merge_bwd}; return 0; };
+    if (h->bf16 && h->opt_kind == 1 && h->loss_kind == 1 && !h->keep_grads) {
+        const int form = mlp16_step_form(h, rows);
+        return pick(form ? StepForm::Bf16Fused : StepForm::Bf16Long, form == 2);
+    }
+    if (!h->bf16 && h->dtype == TNN_F32 && h->opt_kind == 1 && !h->keep_grads && h->n_params >= (1 << 22))
+        return pick(StepForm::LargeAdamEpilogue);
+    if (h->loss_kind != 0) return pick(StepForm::Phases);
+    int head_multi = 0, head_bwd = 0;
+    if (!h->bf16 && h->opt_kind == 1 && L >= 2)
+        MLP_TRY(tnn_mlp_head_fits(rows, h->w[L - 1], h->w[L], h->dtype, &head_multi));
+    // any other head the merged head + hidden-backward launch takes (generic kernel: hidden widths multiples of 16 up to 256,
+    // <= 16 classes): the same 2L - 2 launch step
+    if (!head_multi && !h->bf16 && h->opt_kind == 1 && L >= 3 && h->zpart != nullptr)
+        MLP_TRY(tnn_mlp_head_bwd_fits(rows, h->w[L - 2], h->w[L - 1], h->w[L], h->dtype, &head_bwd));
+    if (head_multi || head_bwd) return pick(StepForm::MergedHead, false, head_bwd || (L >= 3 && h->w[L - 2] % 16 == 0));
+    if (head_fits_row_blocks(h, rows)) return pick(StepForm::RowBlocks);
+    if (h->opt_kind == 1 && head_fits_one_workgroup(h, rows)) return pick(StepForm::OneWorkgroupLoss);
+    return pick(StepForm::HeadFallback);
+}
+
+// large fp32 nets, single GPU, weight gradients not wanted in the arena: Adam in the epilogue of every dW GEMM
+// (tnn_gemm_tn_adam).  The fp32 products are MFMA-bound, so the optimizer's 24 B per parameter ride under them and
+// the separate pass over the arena disappears.  dz_{l-1} is computed BEFORE dW_l: it reads the W_l the epilogue
+// rewrites.
+// Launches per step: L forward | loss (2; Adam's beta powers advanced by a thread of it, the loss filed to loss_out by
+// its reduction) | per layer: dz_{l-1} (l > 0) and ONE launch for dW_l + Adam on W_l + db_l + Adam on b_l
+// (tnn_gemm_tn_adam_bias) — 7 for the two-layer 4096-wide net of configs[2] (15 with the column reductions, bias
+// optimizer launches, beta-power tick and loss copy as launches of their own).
+int step_large_adam_epilogue(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out) {
+    const int L = h->L;
+    MLP_TRY(mlp_forward_stats(h, x, rows, nullptr));
+    if (h->loss_kind == 0) {
+        MLP_TRY(tnn_softmax_nll_fwd_bwd(h->act[L - 1], y, rows, h->w[L], rows, h->stats, loss_slot(h), h->dact[L - 1], h->dtype));
+        MLP_TRY(tnn_adam_tick(h->pows, h->b1, h->b2));
+        if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot(h), h->esz));
+    } else {
+        MLP_TRY(tnn_mse_fwd_bwd_tick(h->act[L - 1], y, rows * h->w[L], rows, loss_slot(h), loss_out, h->dact[L - 1], h->dtype,
+                                     h->pows, h->b1, h->b2));
+    }
+    for (int l = L - 1; l >= 0; --l) {
+        const Slices W = weights(h, l), b = bias(h, l);
+        if (l > 0)
+            MLP_TRY(tnn_gemm_mask(0, 1, rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], W.p, h->w[l + 1], h->act[l - 1],
+                                  h->w[l], h->dact[l - 1], h->w[l], h->dtype));
+        MLP_TRY(tnn_gemm_tn_adam_bias(h->w[l], h->w[l + 1], rows, layer_in(h, l, x), h->w[l], h->dact[l], h->w[l + 1], nullptr,
+                                      W.p, W.m, W.v, b.g, b.p, b.m, b.v, h->lr, h->b1, h->b2, h->eps, h->pows, h->dtype));
+    }
+    return 0;
+}
+
+// sum-of-squares loss: the public phases in a row
+int step_phases(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out) {
+    MLP_TRY(mlp_forward_stats(h, x, rows, nullptr));
+    MLP_TRY(mlp_backward_impl(h, x, y, rows, rows, nullptr, loss_out, false));
+    return mlp_update(h);
+}
+
+// The softmax forms below: stats + loss + dz in one launch; the loss goes straight to loss_out (e.g. one slot of a per-step
+// loss history) or, by default, to the slot behind the gradient arena
+inline void* loss_dst(const Mlp* h, void* loss_out) { return loss_out ? loss_out : loss_slot(h); }
+
+// 2L - 1 launches (5 for the MNIST net; 2L - 2 = 4 with the merge below): forward of the hidden layers | the classifier head as ONE multi-workgroup
+// launch (last Dense forward + loss + last Dense backward + Adam's beta powers) | backward of the hidden layers,
+// the first layer's carrying the whole optimizer
+// the hidden layer in front of the classifier also emits the logits as per-tile partial sums (its activations
+// are in registers there), so no workgroup of the head has to redo a W
+int step_merged_head(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out, bool merge_bwd) {
+    const int L = h->L;
+    MLP_TRY(mlp_forward(h, x, rows, L - 2));
+    STEP_CALL(h, emit_fwd_head_partials(h, x, rows));
+    if (merge_bwd) {
+        // 2L - 2 launches (4 for the MNIST net): the head's launch also carries the backward of the hidden layer in
+        // front of it — its tiles derive their slice of that layer's dz from the partial logits themselves
+        STEP_CALL(h, emit_head_bwd_tick(h, rows, y, loss_dst(h, loss_out)));
+        MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
+    } else {
+        const Slices W = weights(h, L - 1), b = bias(h, L - 1);
+        STEP_CALL(h, tnn_mlp_head_tick(rows, h->w[L - 1], h->w[L], h->act[L - 2], W.p, b.p, y, h->zpart, h->act[L - 1],
+                                       h->dact[L - 1], h->stats, loss_dst(h, loss_out), W.g, b.g, h->dact[L - 2], h->dtype, h->pows,
+                                       h->b1, h->b2));
+        MLP_TRY(mlp_backward_layers(h, x, rows, L - 2, 1));
+    }
+    STEP_CALL(h, emit_bwd_first_adam(h, x, rows));
+    return 0;
+}
+
+// 129 .. 1024 rows, 2L - 2 launches (4 for the MNIST net) like the <= 128-row step: the hidden layer's forward leaves the
+// whole-batch {max, sum-exp} as pairs in memory, the merged head launch reads them
+// and walks the rows in blocks of 128 (dW / db / loss accumulated in registers), the first layer's backward carries
+// the optimizer.  (Before: 7 launches — three forward, a one-workgroup loss, three backward: 35.4 us at 256 rows.)
+int step_row_blocks(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out) {
+    const int L = h->L;
+    MLP_TRY(mlp_forward(h, x, rows, L - 2));
+    // one GPU: the hidden layer's forward in its row-panel form — a workgroup owns 16 whole rows, finishes their logits and
+    // their softmax statistics itself and leaves one {max, sum-exp} pair per panel (no arrival counter, no re-read of
+    // partial logits at the tail of the launch); the merged launch merges the pairs (n_pairs < 0: whole logits)
+    const int n_panels = (int)((rows + 15) / 16);
+    if (head_is_tuned(h))
+        STEP_CALL(h, emit_fwd_rows_head_stats(h, rows));
+    else
+        STEP_CALL(h, emit_fwd_head_partials_stats(h, rows, y, 0));
+    STEP_CALL(h, emit_head_bwd_tick_from(h, HeadStats::Memory, rows, rows, y, h->stats, head_is_tuned(h) ? -n_panels : 1,
+                                         loss_dst(h, loss_out)));
+    MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
+    STEP_CALL(h, emit_bwd_first_adam(h, x, rows));
+    return 0;
+}
+
+// forward | loss (+ Adam's beta powers advanced by its thread 0) | backward, the last launch of which also
+// carries the optimizer
+int step_one_workgroup_loss(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out) {
+    const int L = h->L;
+    MLP_TRY(mlp_forward(h, x, rows));
+    STEP_CALL(h, tnn_softmax_nll_fused_tick(h->act[L - 1], y, rows, h->w[L], rows, 0, h->stats, loss_dst(h, loss_out),
+                                            h->dact[L - 1], h->dtype, h->pows, h->b1, h->b2));
+    // backward of layers L-1 .. 1, then the first layer's backward with the whole Adam step folded into its
+    // launch (its own W / b in the dW epilogue, every other layer's parameters by trailing blocks): 2L + 1 launches
+    MLP_TRY(mlp_backward_layers(h, x, rows, -1, 1));
+    STEP_CALL(h, emit_bwd_first_adam(h, x, rows));
+    return 0;
+}
+
+// hidden layers forward; then the classifier head (last Dense forward + loss + its backward: tnn_mlp_head);
+// then one launch per remaining layer backward; then the optimizer
+int step_head_fallback(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out) {
+    const int L = h->L;
+    const Slices W = weights(h, L - 1), b = bias(h, L - 1);
+    MLP_TRY(mlp_forward(h, x, rows, L - 1));
+    STEP_CALL(h, tnn_mlp_head(rows, h->w[L - 1], h->w[L], layer_in(h, L - 1, x), W.p, b.p, y, h->act[L - 1], h->dact[L - 1],
+                              h->stats, loss_dst(h, loss_out), W.g, b.g, L > 1 ? h->dact[L - 2] : nullptr, h->dtype));
+    MLP_TRY(mlp_backward_layers(h, x, rows, L - 2));
+    return mlp_update(h);
+}
+
+// ---------------------------------------------------------------- tnn_mlp_step_sharded: which form, then the forms
+// One data-parallel step, every phase enqueued from here on the library stream (no host work in between):
+//   forward + shard {max, sum-exp}  ->  C2 all-gather + log-sum-exp merge  ->  loss + backward with the GLOBAL
+//   batch size  ->  C1 in-place all-reduce of grads[0 : n_params + 1] (the loss rides along)  ->  update
+enum class ShardedForm { Bf16Zero, MergedHead, OneWorkgroupLoss, Bucketed, Allreduce };
+struct ShardedStep {
+    ShardedForm form;
+    int rank = 0, world = 1;
+    int p2p_on = 0;
+    bool row_panels = false;   // MergedHead: the hidden layer's forward in its row-panel form
+};
+
+int select_sharded_step(const Mlp* h, int64_t rows, int rank, int world, ShardedStep* step) {
+    *step = {ShardedForm::Allreduce, rank, world};
+    if (zero_step_fits(h, world)) {
+        step->form = ShardedForm::Bf16Zero;
+        return 0;
+    }
+    MLP_TRY(tnn_p2p_status(nullptr, &step->p2p_on, nullptr));
+    // (the tuned 128 -> 10 head or any head of the generic merged kernel; <= 128 rows per rank in one block, 129 .. 1024 in
+    // blocks of 128)
+    // large arenas (config C: 134 MB, config E: 1 GB of fp32 gradients) take the per-layer buckets further down whatever
+    // their head: one all-reduce per layer on the communication stream, overlapping the remaining backward
+    // (TNN_BUCKET_BYTES moves the switch-over point; default 4 MiB — below it the arena is one latency-bound message)
+    static const size_t bucket_bytes = getenv("TNN_BUCKET_BYTES") ? (size_t)atoll(getenv("TNN_BUCKET_BYTES")) : ((size_t)4 << 20);
+    const bool bucketed = (size_t)(h->n_params + 1) * h->esz > bucket_bytes;
+    if (!bucketed && head_fits_sharded(h, rows)) {
+        step->form = ShardedForm::MergedHead;
+        // more than 128 rows of the tuned 128 -> 10 head: the hidden layer's forward in its ROW-PANEL form (a workgroup finishes
+        // 16 whole rows: logits + their statistics), the panels' pairs merged [+ exchanged] by the last workgroup of the launch
+        // (tnn_dense_fwd_rows_head_stats_merged; pairs live behind the merged one in h->stats); otherwise the tiled forward whose
+        // tail re-reads the partial logits per 128-row block behind arrival counters
+        step->row_panels = rows > 128 && head_is_tuned(h);
+    } else if (!bucketed && step->p2p_on && h->dtype == TNN_F32 && h->opt_kind == 1 && head_fits_one_workgroup(h, rows)) {
+        step->form = ShardedForm::OneWorkgroupLoss;
+    } else if (bucketed) {
+        step->form = ShardedForm::Bucketed;
+    }
+    return 0;
+}
+
+// Peer-to-peer transport (round 6): the statistics exchange is DEFERRED into the head launch — the forward launch is the
+// single-GPU one (no acknowledgement wait, arrival ticket, system-scope re-read of the partial logits or exchange at its
+// tail: 8.4 -> 5.2 us at 128 rows), the head launch's workgroups reduce the shard's pair as they do on one GPU, one of
+// them pushes it to the peers and all merge the ranks' pairs from their own tagged slots (tnn_mlp_head_bwd_tick_xchg).
+// <= 128 rows (any head the merged launch takes), or the tuned head's row-panel form above 128 rows; a generic head with
+// more than 128 rows keeps the counter tail.  TNN_DP_XCHG=0 selects the round-5 form (A/B measurements).
+// (every workgroup of that head launch waits for the peers: tnn_mlp_head_bwd_xchg_fits also checks that the ranks whose
+// launches share THIS GPU — the tests' groups; never more than one in a one-process-per-GPU job — fit it together)
+// Asked behind the hidden layers' forward launches, where the step has always asked it.
+int select_stats_exchange(const Mlp* h, const ShardedStep& s, int64_t rows, bool* xchg) {
+    const int L = h->L;
+    static const bool xchg_allowed = !(getenv("TNN_DP_XCHG") && atoi(getenv("TNN_DP_XCHG")) == 0);
+    int xchg_fits = 0;
+    if (s.p2p_on && xchg_allowed && (rows <= 128 || s.row_panels))
+        MLP_TRY(tnn_mlp_head_bwd_xchg_fits(rows, h->w[L - 2], h->w[L - 1], h->w[L], h->dtype, &xchg_fits));
+    *xchg = xchg_fits != 0;
+    return 0;
+}
+
+// Classifier head of the one-launch form (<= 128 rows per rank: every weak-scaling point, config D at 8 ranks) —
+// 2L - 1 launches (5 for the MNIST net) + the collectives, ONE form for every transport:
+//   forward of the hidden layers; the LAST workgroup of the last one to finish also reduces the shard's {max, sum-exp}
+//   from the partial logits and, on the peer-to-peer transport, exchanges and merges them (tnn_dense_fwd_head_
+//   partials_stats: no statistics launch, nobody waits for a peer inside the head launch, no residency requirement)
+//   | RCCL only: tnn_allgather of the pairs | head + hidden layer's backward taking the pair(s) from memory
+//   (tnn_mlp_head_bwd_tick_ext; advances Adam's beta powers) | remaining backward | all-reduce + Adam
+// xchg (select_stats_exchange): the forward launch has no statistics tail (exchange = 2) and the head launch reduces, exchanges
+// and merges the pairs itself.
+int sharded_merged_head(Mlp* h, const ShardedStep& s, const void* x, const void* y, int64_t rows, void* loss_out) {
+    const int L = h->L;
+    const int n_panels = (int)((rows + 15) / 16);
+    MLP_TRY(mlp_forward(h, x, rows, L - 2));
+    bool xchg = false;
+    MLP_TRY(select_stats_exchange(h, s, rows, &xchg));
+    const int exchange = xchg ? 2 : s.p2p_on ? 1 : 0;
+    if (s.row_panels)
+        MLP_TRY(emit_fwd_rows_head_stats_merged(h, rows, exchange));
+    else
+        MLP_TRY(emit_fwd_head_partials_stats(h, rows, y, exchange));
+    if (xchg) {
+        MLP_TRY(emit_head_bwd_tick_from(h, HeadStats::Exchange, rows, rows * s.world, y, s.row_panels ? panel_pairs(h) : nullptr,
+                                        s.row_panels ? -n_panels : 0, loss_slot(h)));
+    } else {
+        const void* pairs = h->stats;
+        int n_pairs = 1;
+        if (!s.p2p_on) {
+            MLP_TRY(tnn_allgather(h->stats, h->stats_all, 2, h->dtype));
+            pairs = h->stats_all;
+            n_pairs = s.world;
+        }
+        if (s.row_panels) n_pairs = -n_pairs;              // whole logits (without the bias) instead of per-tile partials
+        MLP_TRY(emit_head_bwd_tick_from(h, HeadStats::Memory, rows, rows * s.world, y, pairs, n_pairs, loss_slot(h)));
+    }
+    // remaining backward; the first layer's in one launch with the gradient all-reduce and Adam (peer-to-peer transport:
+    // its tiles go straight into the owners' receive slots; RCCL: the launches that replaces)
+    MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
+    return emit_bwd_first_allreduce_adam(h, x, rows, loss_out);
+}
+
+// xGMI peer-to-peer transport and a head that fits one workgroup — 8 launches, like the single-GPU step:
+//   forward | loss kernel that exchanges the shards' {max, sum-exp} itself (stats + C2 + merge + loss + dz)
+//   and advances Adam's beta powers | backward | all-reduce whose last stage applies Adam and files the loss
+int sharded_one_workgroup_loss(Mlp* h, const ShardedStep& s, const void* x, const void* y, int64_t rows, void* loss_out) {
+    const int L = h->L;
+    MLP_TRY(mlp_forward(h, x, rows));
+    MLP_TRY(tnn_softmax_nll_fused_tick(h->act[L - 1], y, rows, h->w[L], rows * s.world, 1, h->stats, loss_slot(h),
+                                       h->dact[L - 1], h->dtype, h->pows, h->b1, h->b2));
+    MLP_TRY(mlp_backward_layers(h, x, rows));
+    return tnn_allreduce_adam(h->grads, h->n_params + 1, h->params, h->m, h->v, h->n_params, h->lr, h->b1, h->b2,
+                              h->eps, h->pows, 0, h->dtype, h->n_params, loss_out);
+}
+
+// forward + the GLOBAL batch's softmax statistics in h->stats: shard statistics, all-gather, log-sum-exp merge
+int sharded_forward_global_stats(Mlp* h, const ShardedStep& s, const void* x, int64_t rows) {
+    MLP_TRY(mlp_forward_stats(h, x, rows, nullptr));
+    if (h->loss_kind == 0) {
+        MLP_TRY(tnn_allgather(h->stats, h->stats_all, 2, h->dtype));
+        MLP_TRY(tnn_lse_merge(h->stats_all, s.world, h->stats, h->dtype));
+    }
+    return 0;
+}
+
+// large arenas: one all-reduce per layer on the communication stream, overlapping the remaining backward
+int sharded_bucketed(Mlp* h, const ShardedStep& s, const void* x, const void* y, int64_t rows, void* loss_out) {
+    MLP_TRY(sharded_forward_global_stats(h, s, x, rows));
+    // any failure from here to the optimizer drains the bucket events already issued (tnn_comm_join) before the
+    // error is returned, so the next step never waits on this one's leftovers
+    int rc = mlp_backward_impl(h, x, y, rows, rows * s.world, h->stats, nullptr, true);
+    if (rc) { (void)tnn_comm_join(); return rc; }
+    if (h->opt_kind == 1) {
+        // Adam layer by layer in bucket order (last layer first): layer l's update starts when ITS bucket has
+        // landed, while the earlier layers' buckets are still on the links
+        for (int l = h->L - 1; l >= 0; --l) {
+            rc = tnn_comm_wait_oldest();
+            if (!rc) rc = adam_layer(h, l, l == h->L - 1, l == h->L - 1 ? loss_out : nullptr);
+            if (rc) { (void)tnn_comm_join(); return rc; }
+        }
+        return 0;
+    }
+    MLP_TRY(tnn_comm_join());
+    MLP_TRY(mlp_update(h));
+    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot(h), h->esz));
+    return 0;
+}
+
+// the whole gradient arena (+ the loss) in one all-reduce behind the backward pass, then the optimizer
+int sharded_allreduce(Mlp* h, const ShardedStep& s, const void* x, const void* y, int64_t rows, void* loss_out) {
+    MLP_TRY(sharded_forward_global_stats(h, s, x, rows));
+    MLP_TRY(mlp_backward_impl(h, x, y, rows, rows * s.world, h->stats, nullptr, false));
+    if (!h->bf16 && h->opt_kind == 1)
+        return tnn_allreduce_adam(h->grads, h->n_params + 1, h->params, h->m, h->v, h->n_params, h->lr, h->b1, h->b2,
+                                  h->eps, h->pows, 1, h->dtype, h->n_params, loss_out);
+    // the arenas of a bf16 trainer are fp32 (master weights, gradients, optimizer state)
+    MLP_TRY(tnn_allreduce(h->grads, h->n_params + 1, h->bf16 ? TNN_F32 : h->dtype, TNN_RSUM));
+    MLP_TRY(mlp_update(h));
+    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot(h), h->esz));
+    return 0;
+}
+
+int step_sharded_impl(Mlp* h, const void* x, const void* y, int64_t rows, void* loss_out) {
+    MLP_TRY(check_rows(h, rows, "tnn_mlp_step_sharded"));
+    h->call_idx = 0;
+    int rank = 0, world = 1;
+    MLP_TRY(tnn_comm_world(&rank, &world));
+    if (h->stats_all_world != world) {
+        tnn_free(h->stats_all);
+        h->stats_all = nullptr;
+        MLP_TRY(tnn_malloc((size_t)world * 2 * 8, &h->stats_all));
+        h->stats_all_world = world;
+    }
+    ShardedStep s;
+    MLP_TRY(select_sharded_step(h, rows, rank, world, &s));
+    switch (s.form) {
+        case ShardedForm::Bf16Zero: return mlp16_step_zero(h, x, y, rows, s.rank, s.world, loss_out);
+        case ShardedForm::MergedHead: return sharded_merged_head(h, s, x, y, rows, loss_out);
+        case ShardedForm::OneWorkgroupLoss: return sharded_one_workgroup_loss(h, s, x, y, rows, loss_out);
+        case ShardedForm::Bucketed: return sharded_bucketed(h, s, x, y, rows, loss_out);
+        case ShardedForm::Allreduce: return sharded_allreduce(h, s, x, y, rows, loss_out);
     }
     return 0;
 }
@@ -631,39 +1070,11 @@ int tnn_mlp_forward(void* handle, const void* x, int64_t rows, void* logits) {
     return 0;
 }
 
-static int mlp_forward_stats(Mlp* h, const void* x, int64_t rows, void* stats);
-
 int tnn_mlp_forward_stats(void* handle, const void* x, int64_t rows, void* stats) {
     Mlp* h = (Mlp*)handle;
     MLP_TRY(check_rows(h, rows, "tnn_mlp_forward_stats"));
     h->call_idx = 0;
     return mlp_forward_stats(h, x, rows, stats);
-}
-
-static int mlp_forward_stats(Mlp* h, const void* x, int64_t rows, void* stats) {
-    if (h->bf16) return mlp16_forward(h, x, rows);
-    MLP_TRY(mlp_forward(h, x, rows));
-    if (h->loss_kind == 0)
-        STEP_CALL(h, tnn_softmax_nll_stats(h->act[h->L - 1], rows, h->w[h->L], stats ? stats : h->stats,
-                                           h->dtype));
-    return 0;
-}
-
-static int mlp_backward_impl(Mlp* h, const void* x, const void* y, int64_t rows, int64_t m_global,
-                             const void* stats, void* loss_out, bool bucket) {
-    MLP_TRY(check_rows(h, rows, "tnn_mlp_backward"));
-    if (h->bf16) return mlp16_backward(h, x, y, rows, m_global, loss_out, bucket);
-    const int L = h->L;
-    void* loss_slot = at(h->grads, h->n_params, h->esz);
-    if (h->loss_kind == 0)
-        STEP_CALL(h, tnn_softmax_nll_fwd_bwd(h->act[L - 1], y, rows, h->w[L], m_global,
-                                             stats ? stats : h->stats, loss_slot, h->dact[L - 1], h->dtype));
-    else
-        STEP_CALL(h, tnn_mse_fwd_bwd(h->act[L - 1], y, rows * h->w[L], m_global, loss_slot, h->dact[L - 1],
-                                     h->dtype));
-    MLP_TRY(mlp_backward_layers(h, x, rows, -1, 0, bucket));
-    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot, h->esz));
-    return 0;
 }
 
 int tnn_mlp_backward(void* handle, const void* x, const void* y, int64_t rows, int64_t m_global,
@@ -672,8 +1083,6 @@ int tnn_mlp_backward(void* handle, const void* x, const void* y, int64_t rows, i
     return mlp_backward_impl((Mlp*)handle, x, y, rows, m_global, stats, loss_out, false);
 }
 
-static int mlp_update(Mlp* h);
-
 int tnn_mlp_update(void* handle) {
     Mlp* h = (Mlp*)handle;
     if (!h) { tnn::set_error("tnn_mlp_update: NULL handle"); return 2; }
@@ -681,376 +1090,32 @@ int tnn_mlp_update(void* handle) {
     return mlp_update(h);
 }
 
-static int mlp_update(Mlp* h) {
-    if (h->bf16) return mlp16_update(h);
-    if (h->opt_kind == 0)
-        STEP_CALL(h, tnn_sgd(h->params, h->grads, h->n_params, h->lr, h->dtype));
-    else if (h->opt_kind >= 2)   // Momentum / RMSProp / Adagrad / Adadelta: m, v are the two state vectors; b1, b2 = a, b
-        STEP_CALL(h, tnn_optim_step(h->opt_kind - 2, h->params, h->grads, h->m, h->v, nullptr, h->n_params, h->lr,
-                                    h->b1, h->b2, h->eps, h->dtype));
-    else
-        STEP_CALL(h, tnn_adam(h->params, h->grads, h->m, h->v, h->n_params, h->lr, h->b1, h->b2, h->eps,
-                              h->pows, nullptr, h->dtype));
-    return 0;
-}
-
 int tnn_mlp_step(void* handle, const void* x, const void* y, int64_t rows, void* loss_out) {
     Mlp* h = (Mlp*)handle;
     MLP_TRY(check_rows(h, rows, "tnn_mlp_step"));
     h->call_idx = 0;
-    if (h->bf16 && h->opt_kind == 1 && h->loss_kind == 1 && !h->keep_grads) {
-        // bf16 trainer, single GPU, weight gradients not wanted in the arena (tnn_mlp_keep_grads(h, 0)): forward | beta
-        // powers | backward with Adam in the dW epilogues — no optimizer launch over the weights, no weight-gradient
-        // round trip through HBM (8 of the 36 bytes per parameter and step; measured 8192 x 8192 x 512: 385-405 us against
-        // 450-495 for GEMM + optimizer).  With the gradient ALSO stored the fused launch is slower than the two (517 us):
-        // keep_grads stays on the separate launches.
-        if (const int form = mlp16_step_form(h, rows)) return mlp16_step_fused(h, x, y, rows, loss_out, form == 2);
-        MLP_TRY(mlp16_forward(h, x, rows));
-        return mlp16_backward(h, x, y, rows, rows, loss_out, false, true, true);
+    Step s;
+    MLP_TRY(select_step(h, rows, &s));
+    switch (s.form) {
+        case StepForm::Bf16Fused: return mlp16_step_fused(h, x, y, rows, loss_out, s.ct);
+        case StepForm::Bf16Long: return mlp16_step_long(h, x, y, rows, loss_out);
+        case StepForm::LargeAdamEpilogue: return step_large_adam_epilogue(h, x, y, rows, loss_out);
+        case StepForm::Phases: return step_phases(h, x, y, rows, loss_out);
+        case StepForm::MergedHead: return step_merged_head(h, x, y, rows, loss_out, s.merge_bwd);
+        case StepForm::RowBlocks: return step_row_blocks(h, x, y, rows, loss_out);
+        case StepForm::OneWorkgroupLoss: return step_one_workgroup_loss(h, x, y, rows, loss_out);
+        case StepForm::HeadFallback: return step_head_fallback(h, x, y, rows, loss_out);
     }
-    if (!h->bf16 && h->dtype == TNN_F32 && h->opt_kind == 1 && !h->keep_grads && h->n_params >= (1 << 22)) {
-        // large fp32 nets, single GPU, weight gradients not wanted in the arena: Adam in the epilogue of every dW GEMM
-        // (tnn_gemm_tn_adam).  The fp32 products are MFMA-bound, so the optimizer's 24 B per parameter ride under them and
-        // the separate pass over the arena disappears.  dz_{l-1} is computed BEFORE dW_l: it reads the W_l the epilogue
-        // rewrites.
-        // Launches per step: L forward | loss (2; Adam's beta powers advanced by a thread of it, the loss filed to loss_out by
-        // its reduction) | per layer: dz_{l-1} (l > 0) and ONE launch for dW_l + Adam on W_l + db_l + Adam on b_l
-        // (tnn_gemm_tn_adam_bias) — 7 for the two-layer 4096-wide net of configs[2] (15 with the column reductions, bias
-        // optimizer launches, beta-power tick and loss copy as launches of their own).
-        const int L = h->L;
-        void* loss_slot = at(h->grads, h->n_params, h->esz);
-        MLP_TRY(mlp_forward_stats(h, x, rows, nullptr));
-        if (h->loss_kind == 0) {
-            MLP_TRY(tnn_softmax_nll_fwd_bwd(h->act[L - 1], y, rows, h->w[L], rows, h->stats, loss_slot, h->dact[L - 1], h->dtype));
-            MLP_TRY(tnn_adam_tick(h->pows, h->b1, h->b2));
-            if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot, h->esz));
-        } else {
-            MLP_TRY(tnn_mse_fwd_bwd_tick(h->act[L - 1], y, rows * h->w[L], rows, loss_slot, loss_out, h->dact[L - 1], h->dtype,
-                                         h->pows, h->b1, h->b2));
-        }
-        for (int l = L - 1; l >= 0; --l) {
-            const void* in = l == 0 ? x : h->act[l - 1];
-            const int64_t wo = h->w_off[l], bo = h->b_off[l];
-            if (l > 0)
-                MLP_TRY(tnn_gemm_mask(0, 1, rows, h->w[l], h->w[l + 1], h->dact[l], h->w[l + 1], at(h->params, wo, 4),
-                                      h->w[l + 1], h->act[l - 1], h->w[l], h->dact[l - 1], h->w[l], h->dtype));
-            MLP_TRY(tnn_gemm_tn_adam_bias(h->w[l], h->w[l + 1], rows, in, h->w[l], h->dact[l], h->w[l + 1], nullptr,
-                                          at(h->params, wo, 4), at(h->m, wo, 4), at(h->v, wo, 4), at(h->grads, bo, 4),
-                                          at(h->params, bo, 4), at(h->m, bo, 4), at(h->v, bo, 4), h->lr, h->b1, h->b2, h->eps,
-                                          h->pows, h->dtype));
-        }
-        return 0;
-    }
-    if (h->loss_kind != 0) {
-        MLP_TRY(mlp_forward_stats(h, x, rows, nullptr));
-        MLP_TRY(mlp_backward_impl(h, x, y, rows, rows, nullptr, loss_out, false));
-        return mlp_update(h);
-    }
-    // unsharded softmax head: stats + loss + dz in one launch; the loss goes straight to loss_out
-    // (e.g. one slot of a per-step loss history) or, by default, to the slot behind the gradient arena
-    const int L = h->L;
-    void* loss_dst = loss_out ? loss_out : at(h->grads, h->n_params, h->esz);
-    int head_multi = 0, head_bwd = 0;
-    if (!h->bf16 && h->opt_kind == 1 && L >= 2)
-        MLP_TRY(tnn_mlp_head_fits(rows, h->w[L - 1], h->w[L], h->dtype, &head_multi));
-    // any other head the merged head + hidden-backward launch takes (generic kernel: hidden widths multiples of 16 up to 256,
-    // <= 16 classes): the same 2L - 2 launch step
-    if (!head_multi && !h->bf16 && h->opt_kind == 1 && L >= 3 && h->zpart != nullptr)
-        MLP_TRY(tnn_mlp_head_bwd_fits(rows, h->w[L - 2], h->w[L - 1], h->w[L], h->dtype, &head_bwd));
-    if (head_multi || head_bwd) {
-        // 2L - 1 launches (5 for the MNIST net; 2L - 2 = 4 with the merge below): forward of the hidden layers | the classifier head as ONE multi-workgroup
-        // launch (last Dense forward + loss + last Dense backward + Adam's beta powers) | backward of the hidden layers,
-        // the first layer's carrying the whole optimizer
-        // the hidden layer in front of the classifier also emits the logits as per-tile partial sums (its activations
-        // are in registers there), so no workgroup of the head has to redo a W
-        MLP_TRY(mlp_forward(h, x, rows, L - 2));
-        STEP_CALL(h, tnn_dense_fwd_head_partials(rows, h->w[L - 1], h->w[L - 2], L > 2 ? h->act[L - 3] : x, h->w[L - 2],
-                                                 at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                 at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                 h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                 h->dtype));
-        if (head_bwd || (L >= 3 && h->w[L - 2] % 16 == 0)) {
-            // 2L - 2 launches (4 for the MNIST net): the head's launch also carries the backward of the hidden layer in
-            // front of it — its tiles derive their slice of that layer's dz from the partial logits themselves
-            STEP_CALL(h, tnn_mlp_head_bwd_tick(rows, h->w[L - 2], h->w[L - 1], h->w[L], h->act[L - 3],
-                                               at(h->params, h->w_off[L - 2], h->esz), h->act[L - 2],
-                                               at(h->params, h->w_off[L - 1], h->esz), at(h->params, h->b_off[L - 1], h->esz),
-                                               y, h->zpart, h->act[L - 1], h->dact[L - 1], h->stats, loss_dst,
-                                               at(h->grads, h->w_off[L - 1], h->esz), at(h->grads, h->b_off[L - 1], h->esz),
-                                               at(h->grads, h->w_off[L - 2], h->esz), at(h->grads, h->b_off[L - 2], h->esz),
-                                               h->dact[L - 3], h->dtype, h->pows, h->b1, h->b2));
-            MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
-        } else {
-            STEP_CALL(h, tnn_mlp_head_tick(rows, h->w[L - 1], h->w[L], h->act[L - 2],
-                                           at(h->params, h->w_off[L - 1], h->esz), at(h->params, h->b_off[L - 1], h->esz), y,
-                                           h->zpart, h->act[L - 1], h->dact[L - 1], h->stats, loss_dst,
-                                           at(h->grads, h->w_off[L - 1], h->esz), at(h->grads, h->b_off[L - 1], h->esz),
-                                           h->dact[L - 2], h->dtype, h->pows, h->b1, h->b2));
-            MLP_TRY(mlp_backward_layers(h, x, rows, L - 2, 1));
-        }
-        const int64_t rest = h->w_off[1];
-        STEP_CALL(h, tnn_dense_bwd_first_adam(rows, h->w[0], h->w[1], x, h->dact[0],
-                                              h->keep_grads ? at(h->grads, h->w_off[0], h->esz) : nullptr,
-                                              at(h->grads, h->b_off[0], h->esz), at(h->params, h->w_off[0], h->esz),
-                                              at(h->m, h->w_off[0], h->esz), at(h->v, h->w_off[0], h->esz),
-                                              at(h->params, h->b_off[0], h->esz), at(h->m, h->b_off[0], h->esz),
-                                              at(h->v, h->b_off[0], h->esz), at(h->params, rest, h->esz),
-                                              at(h->grads, rest, h->esz), at(h->m, rest, h->esz),
-                                              at(h->v, rest, h->esz), h->n_params - rest, h->lr, h->b1, h->b2, h->eps,
-                                              h->pows, h->dtype));
-        return 0;
-    }
-    if (head_fits_row_blocks(h, rows, false)) {
-        // 129 .. 1024 rows, 2L - 2 launches (4 for the MNIST net) like the <= 128-row step: the hidden layer's forward leaves the
-        // whole-batch {max, sum-exp} as pairs in memory, the merged head launch reads them
-        // and walks the rows in blocks of 128 (dW / db / loss accumulated in registers), the first layer's backward carries
-        // the optimizer.  (Before: 7 launches — three forward, a one-workgroup loss, three backward: 35.4 us at 256 rows.)
-        MLP_TRY(mlp_forward(h, x, rows, L - 2));
-        // one GPU: the hidden layer's forward in its row-panel form — a workgroup owns 16 whole rows, finishes their logits and
-        // their softmax statistics itself and leaves one {max, sum-exp} pair per panel (no arrival counter, no re-read of
-        // partial logits at the tail of the launch); the merged launch merges the pairs (n_pairs < 0: whole logits)
-        const int n_panels = (int)((rows + 15) / 16);
-        const bool tuned_head = h->w[L - 1] == 128 && h->w[L] == 10;       // (any other head: the counter tail, one merged pair)
-        if (tuned_head && h->w[L - 2] % 4 == 0)
-            STEP_CALL(h, tnn_dense_fwd_rows_head_stats(rows, h->w[L - 1], h->w[L - 2], h->act[L - 3], h->w[L - 2],
-                                                       at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                       at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                       h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                       at(h->params, h->b_off[L - 1], h->esz), h->stats, h->dtype));
-        else
-            STEP_CALL(h, tnn_dense_fwd_head_partials_stats(rows, h->w[L - 1], h->w[L - 2], h->act[L - 3], h->w[L - 2],
-                                                           at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                           at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                           h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                           at(h->params, h->b_off[L - 1], h->esz), y, h->ticket, h->stats, 0,
-                                                           h->dtype));
-        STEP_CALL(h, tnn_mlp_head_bwd_tick_ext(rows, rows, h->w[L - 2], h->w[L - 1], h->w[L], h->act[L - 3],
-                                               at(h->params, h->w_off[L - 2], h->esz), h->act[L - 2],
-                                               at(h->params, h->w_off[L - 1], h->esz), at(h->params, h->b_off[L - 1], h->esz),
-                                               y, h->zpart, h->stats, (tuned_head && h->w[L - 2] % 4 == 0) ? -n_panels : 1,
-                                               h->act[L - 1], h->dact[L - 1], nullptr, loss_dst,
-                                               at(h->grads, h->w_off[L - 1], h->esz), at(h->grads, h->b_off[L - 1], h->esz),
-                                               at(h->grads, h->w_off[L - 2], h->esz), at(h->grads, h->b_off[L - 2], h->esz),
-                                               h->dact[L - 3], h->dtype, h->pows, h->b1, h->b2));
-        MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
-        const int64_t rest = h->w_off[1];
-        STEP_CALL(h, tnn_dense_bwd_first_adam(rows, h->w[0], h->w[1], x, h->dact[0],
-                                              h->keep_grads ? at(h->grads, h->w_off[0], h->esz) : nullptr,
-                                              at(h->grads, h->b_off[0], h->esz), at(h->params, h->w_off[0], h->esz),
-                                              at(h->m, h->w_off[0], h->esz), at(h->v, h->w_off[0], h->esz),
-                                              at(h->params, h->b_off[0], h->esz), at(h->m, h->b_off[0], h->esz),
-                                              at(h->v, h->b_off[0], h->esz), at(h->params, rest, h->esz),
-                                              at(h->grads, rest, h->esz), at(h->m, rest, h->esz),
-                                              at(h->v, rest, h->esz), h->n_params - rest, h->lr, h->b1, h->b2, h->eps,
-                                              h->pows, h->dtype));
-        return 0;
-    }
-    if (h->opt_kind == 1 && head_fits_one_workgroup(h, rows)) {
-        // forward | loss (+ Adam's beta powers advanced by its thread 0) | backward, the last launch of which also
-        // carries the optimizer
-        MLP_TRY(mlp_forward(h, x, rows));
-        STEP_CALL(h, tnn_softmax_nll_fused_tick(h->act[L - 1], y, rows, h->w[L], rows, 0, h->stats, loss_dst,
-                                                h->dact[L - 1], h->dtype, h->pows, h->b1, h->b2));
-        // backward of layers L-1 .. 1, then the first layer's backward with the whole Adam step folded into its
-        // launch (its own W / b in the dW epilogue, every other layer's parameters by trailing blocks): 2L + 1 launches
-        MLP_TRY(mlp_backward_layers(h, x, rows, -1, 1));
-        const int64_t rest = L > 1 ? h->w_off[1] : h->n_params;
-        STEP_CALL(h, tnn_dense_bwd_first_adam(rows, h->w[0], h->w[1], x, h->dact[0],
-                                              h->keep_grads ? at(h->grads, h->w_off[0], h->esz) : nullptr,
-                                              at(h->grads, h->b_off[0], h->esz), at(h->params, h->w_off[0], h->esz),
-                                              at(h->m, h->w_off[0], h->esz), at(h->v, h->w_off[0], h->esz),
-                                              at(h->params, h->b_off[0], h->esz), at(h->m, h->b_off[0], h->esz),
-                                              at(h->v, h->b_off[0], h->esz), at(h->params, rest, h->esz),
-                                              at(h->grads, rest, h->esz), at(h->m, rest, h->esz),
-                                              at(h->v, rest, h->esz), h->n_params - rest, h->lr, h->b1, h->b2, h->eps,
-                                              h->pows, h->dtype));
-        return 0;
-    }
-    // hidden layers forward; then the classifier head (last Dense forward + loss + its backward: tnn_mlp_head);
-    // then one launch per remaining layer backward; then the optimizer
-    MLP_TRY(mlp_forward(h, x, rows, L - 1));
-    STEP_CALL(h, tnn_mlp_head(rows, h->w[L - 1], h->w[L], L > 1 ? h->act[L - 2] : x,
-                              at(h->params, h->w_off[L - 1], h->esz), at(h->params, h->b_off[L - 1], h->esz), y,
-                              h->act[L - 1], h->dact[L - 1], h->stats, loss_dst,
-                              at(h->grads, h->w_off[L - 1], h->esz), at(h->grads, h->b_off[L - 1], h->esz),
-                              L > 1 ? h->dact[L - 2] : nullptr, h->dtype));
-    MLP_TRY(mlp_backward_layers(h, x, rows, L - 2));
-    return mlp_update(h);
+    return 0;
 }
-
-static int step_sharded_impl(void* handle, const void* x, const void* y, int64_t rows, void* loss_out);
 
 int tnn_mlp_step_sharded(void* handle, const void* x, const void* y, int64_t rows, void* loss_out) {
     // every update launched inside is tied to the peer-to-peer transport's health: if a peer barrier timed out, the
     // collectives were discarded on the device and so are the optimizer launches behind them (tnn_p2p_guard_updates)
     (void)tnn_p2p_guard_updates(1);
-    const int rc = step_sharded_impl(handle, x, y, rows, loss_out);
+    const int rc = step_sharded_impl((Mlp*)handle, x, y, rows, loss_out);
     (void)tnn_p2p_guard_updates(0);
     return rc;
-}
-
-static int step_sharded_impl(void* handle, const void* x, const void* y, int64_t rows, void* loss_out) {
-    // One data-parallel step, every phase enqueued from here on the library stream (no host work in between):
-    //   forward + shard {max, sum-exp}  ->  C2 all-gather + log-sum-exp merge  ->  loss + backward with the GLOBAL
-    //   batch size  ->  C1 in-place all-reduce of grads[0 : n_params + 1] (the loss rides along)  ->  update
-    Mlp* h = (Mlp*)handle;
-    MLP_TRY(check_rows(h, rows, "tnn_mlp_step_sharded"));
-    h->call_idx = 0;
-    int rank = 0, world = 1;
-    MLP_TRY(tnn_comm_world(&rank, &world));
-    if (h->stats_all_world != world) {
-        tnn_free(h->stats_all);
-        h->stats_all = nullptr;
-        MLP_TRY(tnn_malloc((size_t)world * 2 * 8, &h->stats_all));
-        h->stats_all_world = world;
-    }
-    if (zero_step_fits(h, world)) return mlp16_step_zero(h, x, y, rows, rank, world, loss_out);
-    int p2p_on = 0;
-    MLP_TRY(tnn_p2p_status(nullptr, &p2p_on, nullptr));
-    const int L = h->L;
-    void* loss_slot = at(h->grads, h->n_params, h->esz);
-    // (the tuned 128 -> 10 head or any head of the generic merged kernel; <= 128 rows per rank in one block, 129 .. 1024 in
-    // blocks of 128)
-    // large arenas (config C: 134 MB, config E: 1 GB of fp32 gradients) take the per-layer buckets further down whatever
-    // their head: one all-reduce per layer on the communication stream, overlapping the remaining backward
-    // (TNN_BUCKET_BYTES moves the switch-over point; default 4 MiB — below it the arena is one latency-bound message)
-    static const size_t bucket_bytes = getenv("TNN_BUCKET_BYTES") ? (size_t)atoll(getenv("TNN_BUCKET_BYTES")) : ((size_t)4 << 20);
-    const bool bucketed = (size_t)(h->n_params + 1) * h->esz > bucket_bytes;
-    if (!bucketed && head_fits_sharded(h, rows)) {
-        // Classifier head of the one-launch form (<= 128 rows per rank: every weak-scaling point, config D at 8 ranks) —
-        // 2L - 1 launches (5 for the MNIST net) + the collectives, ONE form for every transport:
-        //   forward of the hidden layers; the LAST workgroup of the last one to finish also reduces the shard's {max, sum-exp}
-        //   from the partial logits and, on the peer-to-peer transport, exchanges and merges them (tnn_dense_fwd_head_
-        //   partials_stats: no statistics launch, nobody waits for a peer inside the head launch, no residency requirement)
-        //   | RCCL only: tnn_allgather of the pairs | head + hidden layer's backward taking the pair(s) from memory
-        //   (tnn_mlp_head_bwd_tick_ext; advances Adam's beta powers) | remaining backward | all-reduce + Adam
-        MLP_TRY(mlp_forward(h, x, rows, L - 2));
-        // more than 128 rows of the tuned 128 -> 10 head: the hidden layer's forward in its ROW-PANEL form (a workgroup finishes
-        // 16 whole rows: logits + their statistics), the panels' pairs merged [+ exchanged] by the last workgroup of the launch
-        // (tnn_dense_fwd_rows_head_stats_merged; pairs live behind the merged one in h->stats); otherwise the tiled forward whose
-        // tail re-reads the partial logits per 128-row block behind arrival counters
-        const bool row_panels = rows > 128 && h->w[L - 1] == 128 && h->w[L] == 10 && h->w[L - 2] % 4 == 0;
-        // Peer-to-peer transport (round 6): the statistics exchange is DEFERRED into the head launch — the forward launch is the
-        // single-GPU one (no acknowledgement wait, arrival ticket, system-scope re-read of the partial logits or exchange at its
-        // tail: 8.4 -> 5.2 us at 128 rows), the head launch's workgroups reduce the shard's pair as they do on one GPU, one of
-        // them pushes it to the peers and all merge the ranks' pairs from their own tagged slots (tnn_mlp_head_bwd_tick_xchg).
-        // <= 128 rows (any head the merged launch takes), or the tuned head's row-panel form above 128 rows; a generic head with
-        // more than 128 rows keeps the counter tail.  TNN_DP_XCHG=0 selects the round-5 form (A/B measurements).
-        // (every workgroup of that head launch waits for the peers: tnn_mlp_head_bwd_xchg_fits also checks that the ranks whose
-        // launches share THIS GPU — the tests' groups; never more than one in a one-process-per-GPU job — fit it together)
-        static const bool xchg_allowed = !(getenv("TNN_DP_XCHG") && atoi(getenv("TNN_DP_XCHG")) == 0);
-        int xchg_fits = 0;
-        if (p2p_on && xchg_allowed && (rows <= 128 || row_panels))
-            MLP_TRY(tnn_mlp_head_bwd_xchg_fits(rows, h->w[L - 2], h->w[L - 1], h->w[L], h->dtype, &xchg_fits));
-        if (xchg_fits) {
-            const int n_panels = (int)((rows + 15) / 16);
-            if (row_panels)
-                MLP_TRY(tnn_dense_fwd_rows_head_stats_merged(rows, h->w[L - 1], h->w[L - 2], h->act[L - 3], h->w[L - 2],
-                                                             at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                             at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                             h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                             at(h->params, h->b_off[L - 1], h->esz), (char*)h->stats + 16, h->ticket,
-                                                             h->stats, 2, h->dtype));
-            else
-                MLP_TRY(tnn_dense_fwd_head_partials_stats(rows, h->w[L - 1], h->w[L - 2], h->act[L - 3], h->w[L - 2],
-                                                          at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                          at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                          h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                          at(h->params, h->b_off[L - 1], h->esz), y, h->ticket, h->stats, 2, h->dtype));
-            MLP_TRY(tnn_mlp_head_bwd_tick_xchg(rows, rows * world, h->w[L - 2], h->w[L - 1], h->w[L], h->act[L - 3],
-                                               at(h->params, h->w_off[L - 2], h->esz), h->act[L - 2],
-                                               at(h->params, h->w_off[L - 1], h->esz), at(h->params, h->b_off[L - 1], h->esz),
-                                               y, h->zpart, row_panels ? (char*)h->stats + 16 : nullptr, row_panels ? -n_panels : 0,
-                                               h->act[L - 1], h->dact[L - 1], nullptr, loss_slot,
-                                               at(h->grads, h->w_off[L - 1], h->esz), at(h->grads, h->b_off[L - 1], h->esz),
-                                               at(h->grads, h->w_off[L - 2], h->esz), at(h->grads, h->b_off[L - 2], h->esz),
-                                               h->dact[L - 3], h->dtype, h->pows, h->b1, h->b2));
-            MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
-            return tnn_dense_bwd_first_allreduce_adam(rows, h->w[0], h->w[1], x, h->dact[0], h->grads, h->n_params + 1,
-                                                      h->w_off[0], h->b_off[0], h->params, h->m, h->v, h->n_params, h->lr,
-                                                      h->b1, h->b2, h->eps, h->pows, h->n_params, loss_out, h->dtype);
-        }
-        if (row_panels)
-            MLP_TRY(tnn_dense_fwd_rows_head_stats_merged(rows, h->w[L - 1], h->w[L - 2], h->act[L - 3], h->w[L - 2],
-                                                         at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                         at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                         h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                         at(h->params, h->b_off[L - 1], h->esz), (char*)h->stats + 16, h->ticket,
-                                                         h->stats, p2p_on ? 1 : 0, h->dtype));
-        else
-            MLP_TRY(tnn_dense_fwd_head_partials_stats(rows, h->w[L - 1], h->w[L - 2], h->act[L - 3], h->w[L - 2],
-                                                      at(h->params, h->w_off[L - 2], h->esz), h->w[L - 1],
-                                                      at(h->params, h->b_off[L - 2], h->esz), TNN_ACT_RELU, 1, h->act[L - 2],
-                                                      h->w[L - 1], at(h->params, h->w_off[L - 1], h->esz), h->w[L], h->zpart,
-                                                      at(h->params, h->b_off[L - 1], h->esz), y, h->ticket, h->stats,
-                                                      p2p_on ? 1 : 0, h->dtype));
-        const void* pairs = h->stats;
-        int n_pairs = 1;
-        if (!p2p_on) {
-            MLP_TRY(tnn_allgather(h->stats, h->stats_all, 2, h->dtype));
-            pairs = h->stats_all;
-            n_pairs = world;
-        }
-        if (row_panels) n_pairs = -n_pairs;              // whole logits (without the bias) instead of per-tile partials
-        MLP_TRY(tnn_mlp_head_bwd_tick_ext(rows, rows * world, h->w[L - 2], h->w[L - 1], h->w[L], h->act[L - 3],
-                                          at(h->params, h->w_off[L - 2], h->esz), h->act[L - 2],
-                                          at(h->params, h->w_off[L - 1], h->esz), at(h->params, h->b_off[L - 1], h->esz),
-                                          y, h->zpart, pairs, n_pairs, h->act[L - 1], h->dact[L - 1], nullptr, loss_slot,
-                                          at(h->grads, h->w_off[L - 1], h->esz), at(h->grads, h->b_off[L - 1], h->esz),
-                                          at(h->grads, h->w_off[L - 2], h->esz), at(h->grads, h->b_off[L - 2], h->esz),
-                                          h->dact[L - 3], h->dtype, h->pows, h->b1, h->b2));
-        // remaining backward; the first layer's in one launch with the gradient all-reduce and Adam (peer-to-peer transport:
-        // its tiles go straight into the owners' receive slots; RCCL: the launches that replaces)
-        MLP_TRY(mlp_backward_layers(h, x, rows, L - 3, 1));
-        return tnn_dense_bwd_first_allreduce_adam(rows, h->w[0], h->w[1], x, h->dact[0], h->grads, h->n_params + 1,
-                                                  h->w_off[0], h->b_off[0], h->params, h->m, h->v, h->n_params, h->lr,
-                                                  h->b1, h->b2, h->eps, h->pows, h->n_params, loss_out, h->dtype);
-    }
-    if (!bucketed && p2p_on && h->dtype == TNN_F32 && h->opt_kind == 1 && head_fits_one_workgroup(h, rows)) {
-        // xGMI peer-to-peer transport and a head that fits one workgroup — 8 launches, like the single-GPU step:
-        //   forward | loss kernel that exchanges the shards' {max, sum-exp} itself (stats + C2 + merge + loss + dz)
-        //   and advances Adam's beta powers | backward | all-reduce whose last stage applies Adam and files the loss
-        MLP_TRY(mlp_forward(h, x, rows));
-        MLP_TRY(tnn_softmax_nll_fused_tick(h->act[L - 1], y, rows, h->w[L], rows * world, 1, h->stats, loss_slot,
-                                           h->dact[L - 1], h->dtype, h->pows, h->b1, h->b2));
-        MLP_TRY(mlp_backward_layers(h, x, rows));
-        return tnn_allreduce_adam(h->grads, h->n_params + 1, h->params, h->m, h->v, h->n_params, h->lr, h->b1, h->b2,
-                                  h->eps, h->pows, 0, h->dtype, h->n_params, loss_out);
-    }
-    MLP_TRY(mlp_forward_stats(h, x, rows, nullptr));
-    if (h->loss_kind == 0) {
-        MLP_TRY(tnn_allgather(h->stats, h->stats_all, 2, h->dtype));
-        MLP_TRY(tnn_lse_merge(h->stats_all, world, h->stats, h->dtype));
-    }
-    if (bucketed) {
-        // any failure from here to the optimizer drains the bucket events already issued (tnn_comm_join) before the
-        // error is returned, so the next step never waits on this one's leftovers
-        int rc = mlp_backward_impl(h, x, y, rows, rows * world, h->stats, nullptr, true);
-        if (rc) { (void)tnn_comm_join(); return rc; }
-        if (h->opt_kind == 1) {
-            // Adam layer by layer in bucket order (last layer first): layer l's update starts when ITS bucket has
-            // landed, while the earlier layers' buckets are still on the links
-            for (int l = h->L - 1; l >= 0; --l) {
-                rc = tnn_comm_wait_oldest();
-                if (!rc) rc = adam_layer(h, l, l == h->L - 1, l == h->L - 1 ? loss_out : nullptr);
-                if (rc) { (void)tnn_comm_join(); return rc; }
-            }
-            return 0;
-        }
-        MLP_TRY(tnn_comm_join());
-        MLP_TRY(mlp_update(h));
-        if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot, h->esz));
-        return 0;
-    }
-    MLP_TRY(mlp_backward_impl(h, x, y, rows, rows * world, h->stats, nullptr, false));
-    if (!h->bf16 && h->opt_kind == 1)
-        return tnn_allreduce_adam(h->grads, h->n_params + 1, h->params, h->m, h->v, h->n_params, h->lr, h->b1, h->b2,
-                                  h->eps, h->pows, 1, h->dtype, h->n_params, loss_out);
-    // the arenas of a bf16 trainer are fp32 (master weights, gradients, optimizer state)
-    MLP_TRY(tnn_allreduce(h->grads, h->n_params + 1, h->bf16 ? TNN_F32 : h->dtype, TNN_RSUM));
-    MLP_TRY(mlp_update(h));
-    if (loss_out) MLP_TRY(tnn_memcpy_d2d(loss_out, loss_slot, h->esz));
-    return 0;
 }
 
 int tnn_mlp_launch_window(void* handle, int first, int count, int* calls_in_last_step) {
