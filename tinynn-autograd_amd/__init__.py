@@ -60,6 +60,8 @@ from . import dist
 from . import fused
 from . import graph
 from .graph import capture
+from . import dropout
+from . import rng
 from .fused import MLPTrainer, trainer_from_net
 
 __version__ = "0.1.0"

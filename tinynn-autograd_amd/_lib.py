@@ -59,6 +59,10 @@ from ._decode_signatures import _DECODE_SIGNATURES            # noqa: E402  (inc
 
 DECODE_SYMBOLS = sorted(_DECODE_SIGNATURES)
 
+from ._dropout_signatures import _DROPOUT_SIGNATURES          # noqa: E402  (include/tnn_dropout.h: libtnn_hip.so only)
+
+DROPOUT_SYMBOLS = sorted(_DROPOUT_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -120,13 +124,16 @@ class _Lib(object):
         # from take, a one-hot product, max / exp / sum / log and the advanced-index gather
         # and decode attention and token sampling (include/tnn_decode.h): under the twin device_array appends by a slice
         # assignment and runs the composed attention over the live prefix; sampling reads the logits back
+        # and the random generator and dropout (include/tnn_dropout.h): under the twin rng.Generator keeps its state in two
+        # host integers and device_array draws the mask with the planner's numpy generator (dropout.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
                                     (_ATTN_SIGNATURES, "tnn_attn.h", "attention"),
                                     (_NORM_SIGNATURES, "tnn_norm.h", "normalisation"),
                                     (_TOKEN_SIGNATURES, "tnn_token.h", "embedding / cross-entropy"),
-                                    (_DECODE_SIGNATURES, "tnn_decode.h", "decode attention / sampling")):
+                                    (_DECODE_SIGNATURES, "tnn_decode.h", "decode attention / sampling"),
+                                    (_DROPOUT_SIGNATURES, "tnn_dropout.h", "random generator / dropout")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -143,6 +150,7 @@ class _Lib(object):
         self.has_norm = hasattr(self.cdll, "tnn_norm_fwd")
         self.has_token = hasattr(self.cdll, "tnn_embed_fwd")
         self.has_decode = hasattr(self.cdll, "tnn_decode_attn")
+        self.has_dropout = hasattr(self.cdll, "tnn_dropout_fwd")
 
     @staticmethod
     def _absent(name, what):

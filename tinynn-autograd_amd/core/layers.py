@@ -9,7 +9,9 @@ node plus a broadcast-add node (`fused=False` restores the literal `inputs @ w +
 Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / ops.max_pool2d_), enough for a LeNet, and
 `MultiHeadAttention` (ops.attention_), whose parameter dict order is MHA_PARAM_ORDER; `LayerNorm` / `RMSNorm`
 (ops.layer_norm_ / ops.rms_norm_; "gamma" then "beta"), `GELU`, and `TransformerBlock`, a pre-norm block built from them whose
-ONE flat parameter dict has the order BLOCK_PARAM_ORDER; `Embedding` (ops.embedding_; "tok" then "pos", EMBED_PARAM_ORDER).
+ONE flat parameter dict has the order BLOCK_PARAM_ORDER; `Embedding` (ops.embedding_; "tok" then "pos", EMBED_PARAM_ORDER);
+`Dropout` (ops.dropout_), the one layer that reads the TRAIN / TEST flag, and the `dropout` argument of `TransformerBlock` and
+`Embedding`.
 """
 
 from . import ops
@@ -27,8 +29,8 @@ BLOCK_PARAM_ORDER = (("ln1.gamma", "ln1.beta") + tuple("attn." + name for name i
 
 
 class Layer(object):
-    """Base class: a name, a parameter dict (empty for activations) and the TRAIN/TEST flag nobody reads
-    (core/layers.py:21-22)."""
+    """Base class: a name, a parameter dict (empty for activations) and the TRAIN/TEST flag (core/layers.py:21-22, SURVEY F8;
+    nobody reads it in the reference — here dropout does)."""
 
     def __init__(self, name):
         self.name = name
@@ -329,6 +331,36 @@ class GELU(Activation):
         return ops.gelu_(x, approximate=self.approximate)
 
 
+def _check_rate(p):
+    from ..dropout import threshold_of
+    threshold_of(p)                          # ValueError outside [0, 1)
+    return float(p)
+
+
+class Dropout(Layer):
+    """Dropout with rate `p`: in the TRAIN phase every element is zeroed with probability p and the kept ones are scaled by
+    1 / (1 - p); in the TEST phase (`is_training` False) and for p == 0 the layer is the identity and launches nothing.  The
+    mask comes from `generator` (rng.Generator; None: rng.default_generator — seed it with rng.manual_seed) and is never
+    stored: the backward launch regenerates it.  `fused=False` runs the composed route (a host-drawn mask, the existing
+    multiply and masked select), which cannot be captured into a graph."""
+
+    def __init__(self, p=0.5, generator=None, fused=True):
+        super().__init__("Dropout")
+        self.p, self.generator, self.fused = _check_rate(p), generator, fused
+        self.inputs = None
+
+    def active(self):
+        return self.is_training and self.p > 0.0
+
+    def forward(self, inputs, residual=None):
+        """residual: a tensor of the input's shape that is added to the result by the same launch (the identity cases add it
+        through the ordinary add)."""
+        self.inputs = inputs
+        if not self.active():
+            return inputs if residual is None else residual + inputs
+        return ops.dropout_(inputs, self.p, residual, generator=self.generator, route=None if self.fused else "composed")
+
+
 class TransformerBlock(Layer):
     """Pre-norm transformer block over [B, T, E] inputs:
 
@@ -341,10 +373,16 @@ class TransformerBlock(Layer):
     fc2.w fc2.b.  The parameters are created — and the host RNG is drawn from — in that order, so Net.get_parameters, the
     optimizer's flatten order and Model.step see the block as one layer.  The dict is what counts: every forward hands its
     tensors to the parts, so Net.set_parameters works unchanged.  E (`num_in`) may be omitted and is then read off the first
-    batch.  `fused=False` puts every part on its composed route."""
+    batch.  `fused=False` puts every part on its composed route.
 
-    def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True):
+    dropout > 0: h = x + drop(MHA(LN1(x))) and out = h + drop(MLP(LN2(h))) in the TRAIN phase, both through the fused residual
+    form of ops.dropout_ — its launch REPLACES the block's residual add — drawing from `generator` (None: the default
+    generator of rng.py).  With dropout == 0 (the default) and in the TEST phase the block runs exactly its launches without
+    the argument."""
+
+    def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True, dropout=0.0, generator=None):
         super().__init__("TransformerBlock")
+        self.drop = Dropout(dropout, generator=generator, fused=fused)
         self.num_heads, self.hidden, self.causal, self.eps, self.fused = int(num_heads), hidden, bool(causal), float(eps), fused
         if self.num_heads < 1:
             raise ValueError("TransformerBlock: num_heads must be >= 1, got %r" % (num_heads,))
@@ -387,10 +425,16 @@ class TransformerBlock(Layer):
             part, name = key.split(".")
             parts[part].params[name] = self.params[key]
         normed = parts["ln1"].forward(inputs)
-        h = inputs + parts["attn"].forward(normed, cache=cache)
+        h = self.drop.forward(parts["attn"].forward(normed, cache=cache), residual=inputs)     # (inactive: inputs + attn)
         z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))
         z = ops.gelu_(z, approximate="tanh", route=None if self.fused else "composed")
-        return h + ops.reshape(parts["fc2"].forward(z), (b, t, e))
+        return self.drop.forward(ops.reshape(parts["fc2"].forward(z), (b, t, e)), residual=h)
+
+    def set_phase(self, phase):
+        super().set_phase(phase)
+        self.drop.set_phase(phase)
+        for part in (self.parts or {}).values():
+            part.set_phase(phase)
 
 
 class Embedding(Layer):
@@ -399,10 +443,13 @@ class Embedding(Layer):
     then "pos" (EMBED_PARAM_ORDER; "pos" exists only with max_len), created — and drawn from the host RNG — in THAT order, both
     with `w_init`.  The gradient of "tok" ACCUMULATES over repeated ids; the row `padding_idx` receives none.  The ids never
     get a gradient.  `fused=False` runs the composed route (a row gather; a one-hot product backward that reads the ids on the
-    host)."""
+    host).  dropout > 0: dropout on the output in the TRAIN phase (ops.dropout_, from `generator`; None: the default generator
+    of rng.py); 0, the default, adds no launch."""
 
-    def __init__(self, vocab, width, max_len=None, padding_idx=None, w_init=NormalInit(0.0, 0.02), fused=True):
+    def __init__(self, vocab, width, max_len=None, padding_idx=None, w_init=NormalInit(0.0, 0.02), fused=True, dropout=0.0,
+                 generator=None):
         super().__init__("Embedding")
+        self.drop = Dropout(dropout, generator=generator, fused=fused)
         self.vocab, self.width, self.max_len, self.fused = int(vocab), int(width), max_len, fused
         if self.vocab < 1 or self.width < 1 or (max_len is not None and int(max_len) < 1):
             raise ValueError("Embedding: vocab, width and max_len must be >= 1, got %r, %r, %r" % (vocab, width, max_len))
@@ -436,5 +483,10 @@ class Embedding(Layer):
         pos = self.params.get("pos")
         if pos is not None and offset:
             pos = ops.getitem_(pos, slice(offset, offset + int(inputs.shape[1])))
-        return ops.embedding_(self.params["tok"], inputs, pos, padding_idx=self.padding_idx,
-                              route=None if self.fused else "composed")
+        out = ops.embedding_(self.params["tok"], inputs, pos, padding_idx=self.padding_idx,
+                             route=None if self.fused else "composed")
+        return self.drop.forward(out) if self.drop.active() else out
+
+    def set_phase(self, phase):
+        super().set_phase(phase)
+        self.drop.set_phase(phase)

@@ -11,7 +11,8 @@ Extra fused nodes used by this package's own layers/losses (parity-tested agains
 convolution and max pooling, csrc/tnn_conv.hip; the reference has neither), `attention_` (fused scaled-dot-product attention,
 csrc/tnn_attn.hip; likewise), `layer_norm_` / `rms_norm_` / `gelu_` (csrc/tnn_norm.hip; likewise), `embedding_` /
 `cross_entropy_` (csrc/tnn_token.hip; likewise — `embedding_` is the gather whose vjp ACCUMULATES over repeated ids, which
-`getitem_`'s does not).
+`getitem_`'s does not), `dropout_` (csrc/tnn_dropout.hip; likewise — its mask comes from the device random generator of rng.py
+and is regenerated, not stored, for the vjp).
 """
 
 import math
@@ -721,6 +722,35 @@ def gelu_(x, approximate="none", route=None, **unknown):
     return build_unary_ops_tensor(x, lambda g: da.gelu_bwd(xv, g, approximate=approximate, route=route), out)
 
 
+def dropout_(x, p, residual=None, generator=None, route=None, first=0, **unknown):
+    """Dropout node: keep ? x / (1 - p) : 0 elementwise, plus `residual` (a tensor of x's shape) when there is one — the fused
+    residual form, in which ONE launch replaces a block's residual add.  The keep decision of an element is the 24-bit draw of
+    its stream index (first + its row-major position) of ONE call of `generator` (rng.Generator; None: rng.default_generator)
+    against round(p 2^24): dropout.py states the generator exactly.  float32 and float64.
+
+    p == 0 returns x itself (or x + residual through add_) without any new launch and without consuming a call.  Otherwise
+    forward is a one-thread ticket launch and ONE tnn_dropout_fwd launch, backward ONE tnn_dropout_bwd launch that regenerates
+    the mask from the forward's ticket — so it is right after later draws and inside a replayed graph; the residual's gradient
+    is the incoming gradient itself.  Under the CPU test twin and with route="composed" (or device_array.DROPOUT_ROUTE) the
+    mask is drawn on the host with the planner's generator and applied by the existing multiply, masked select and add; that
+    route raises inside an open graph capture.  This node applies dropout whenever it is called: the TRAIN / TEST decision
+    belongs to the layers.  Out of scope: bf16, per-sample or ragged masks — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("dropout_: unsupported arguments %s" % sorted(unknown))
+    from ..dropout import threshold_of
+    if threshold_of(p) == 0 and float(p) == 0.0:
+        return x if residual is None else add_(residual, x)
+    out, mask = da.dropout(x.values, p, None if residual is None else residual.values, generator=generator, route=route,
+                           first=first)
+
+    def d_x(g):
+        return da.dropout_bwd(g, mask)
+
+    if residual is None:
+        return build_unary_ops_tensor(x, d_x, out)
+    return build_binary_ops_tensor(x, residual, d_x, lambda g: da.asarray(g), out)
+
+
 def _index_values(obj, limit, what, also=None):
     """ids / targets given as a Tensor, a DeviceArray or numpy -> a dense int64 device array; host values are range-checked
     once, here (IndexError); they never require a gradient."""
@@ -1132,6 +1162,13 @@ def gelu(obj, approximate="none", **unknown):
     if unknown:
         raise TypeError("gelu: unsupported arguments %s" % sorted(unknown))
     return gelu_(as_tensor(obj), approximate=approximate)
+
+
+def dropout(obj, p=0.5, residual=None, generator=None, **unknown):
+    """not in the reference: see dropout_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("dropout: unsupported arguments %s" % sorted(unknown))
+    return dropout_(as_tensor(obj), p, _opt_tensor(residual), generator=generator)
 
 
 def embedding(obj, ids, pos=None, padding_idx=None, **unknown):

@@ -28,8 +28,8 @@ Routes
               in float64) — a host synchronisation per call, so it cannot be captured into a graph.  What runs under the CPU
               test twin and the second, independent implementation the GPU tests compare the kernels with.
 
-Out of scope: ragged batches, grouped-query heads, chunked prefill (it needs a bottom-right causal rule), top-p, bf16, a
-device random generator (u is drawn on the host).
+Out of scope: ragged batches, grouped-query heads, chunked prefill (it needs a bottom-right causal rule), top-p, bf16.
+(u is an operand: generation.generate draws it on the host, or on the device with an rng.Generator.)
 """
 
 import math

@@ -30,6 +30,7 @@ from . import attention as _at
 from . import batching as _bt
 from . import conv as _cv
 from . import decoding as _dc
+from . import dropout as _dp
 from . import indexing as _ix
 from . import norm as _nm
 from . import tokens as _tk
@@ -1697,6 +1698,99 @@ def gelu_bwd(x, dy, approximate="none", route=None, dx_out=None):
     t = _gelu_inner(x)
     slope = (t + 1.0) * 0.5 + (x * 0.5) * (1.0 - t * t) * ((x * x) * (3.0 * _GELU_A) + 1.0) * _GELU_C
     return dy * slope
+
+
+# ---------------------------------------------------------------------- kernels: random generator, dropout (csrc/tnn_dropout.hip)
+DROPOUT_ROUTE = None  # tests / probes: "native" or "composed" overrides the planner's choice (dropout.py)
+
+
+class DropoutMask(object):
+    """What dropout_bwd needs of ONE dropout call.  Native: the 16-byte ticket of the forward launch (the mask is regenerated
+    from it, never stored).  Composed: the uploaded boolean keep mask."""
+    __slots__ = ("plan", "dtype", "ticket", "keep")
+
+    def __init__(self, plan, dtype, ticket=None, keep=None):
+        self.plan, self.dtype, self.ticket, self.keep = plan, dtype, ticket, keep
+
+    def scale(self):
+        """s: the plan's scale rounded ONCE to the operand dtype, as a Python float (exact)."""
+        return float(self.dtype.type(self.plan.scale))
+
+
+def _dropout_dest(out, shape, dt, what):
+    if out is None:
+        return DeviceArray._new(shape, dt)
+    dest = _grad_dest(out, shape, dt)
+    if dest is None:
+        raise ValueError("%s: `out` must be a dense %s device array of %d elements" % (what, dt.name, _prod(shape)))
+    return dest
+
+
+def dropout(x, p, residual=None, generator=None, route=None, first=0, out=None):
+    """(y, mask): y = keep ? x * s : +0 with s = 1 / (1 - p) rounded once to the operand dtype, plus `residual` (same shape)
+    when there is one — product and sum rounded separately.  An element is kept iff the 24-bit draw of its stream index
+    first + j (row-major j) is >= round(p 2^24) (dropout.py states the generator); the call consumes ONE value of the
+    generator's `calls` (rng.Generator; None: rng.default_generator).  `mask` is what dropout_bwd takes.
+
+    p == 0: nothing is drawn and nothing new is launched — (x, None), or (x + residual, None) through the existing add.
+    Native: a one-thread ticket launch and ONE tnn_dropout_fwd data launch; capturable.  Composed (dropout.py: the CPU test
+    twin, route="composed"): the generator's state is read (host integers, or a read-back), the keep mask is drawn on the host
+    with the planner's generator and uploaded, the existing scalar multiply, masked select (mul_mask — a select, so a dropped
+    element is +0 whatever x holds) and add apply it, and the state is advanced — so it raises inside an open graph capture.
+    Both routes give identical bits and leave the generator in the same state.  out: a dense array the result is written
+    into; it may be x or the residual."""
+    from . import rng as _rng
+    gen = _rng.default_generator if generator is None else generator
+    dt, (x, residual) = _norm_operands(x, residual)
+    plan = _dp.plan_dropout(x.shape, p, dt, first=first, native=_lib.get().has_dropout, route=route or DROPOUT_ROUTE)
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("dropout: the residual must have x's shape %s, got %s" % (x.shape, residual.shape))
+    if plan.threshold == 0 and plan.p == 0.0:
+        if out is not None:
+            raise ValueError("dropout: p == 0 writes nothing — `out` is not supported")
+        return (x if residual is None else residual + x), None
+    if plan.route == "native":
+        state = gen.device_state()
+        ticket = DeviceArray._new((2,), np.int64)
+        y = _dropout_dest(out, x.shape, dt, "dropout")
+        _lib.get().dropout_fwd(state._ptr, ticket._ptr, x._ptr, _ptr_of(residual), y._ptr, plan.first, plan.n, plan.threshold,
+                               plan.scale, y._code())
+        return y, DropoutMask(plan, dt, ticket=ticket)
+    if _lib.capturing:
+        raise RuntimeError("dropout: the composed route draws its mask on the host and cannot be captured into a graph")
+    seed, calls = gen.state()
+    keep = asarray(_dp.keep_mask(seed, calls, plan.first, plan.n, plan.threshold).reshape(x.shape))
+    gen.advance(seed, calls)
+    mask = DropoutMask(plan, dt, keep=keep)
+    y = mul_mask(x * mask.scale(), keep)
+    if residual is not None:
+        y = residual + y
+    if out is not None:
+        dest = _dropout_dest(out, x.shape, dt, "dropout")
+        dest.reshape(x.shape)[...] = y
+        y = dest
+    return y, mask
+
+
+def dropout_bwd(dy, mask, dx_out=None):
+    """dx = keep ? dy * s : +0 for the `mask` a dropout call returned (None — p was 0 — gives dy back).  Native: ONE
+    tnn_dropout_bwd launch that regenerates the forward's mask from its ticket, whatever the generator has drawn since.  The
+    residual's gradient is dy itself.  dx_out: a dense array the result is written into; it may be dy."""
+    if mask is None:
+        return dy
+    dt, shape = mask.dtype, mask.plan.shape
+    dy = asarray(dy)._as_float(dt)
+    if dy.shape != shape:
+        dy = dy._broadcast_to(shape)
+    dy = dy._contig()
+    if mask.ticket is not None:
+        dx = _grad_dest(dx_out, shape, dt)
+        if dx is None:
+            dx = DeviceArray._new(shape, dt)
+        plan = mask.plan
+        _lib.get().dropout_bwd(mask.ticket._ptr, dy._ptr, dx._ptr, plan.first, plan.n, plan.threshold, plan.scale, dx._code())
+        return dx
+    return mul_mask(dy * mask.scale(), mask.keep)
 
 
 # ---------------------------------------------------------------------- kernels: embedding, per-row cross-entropy (csrc/tnn_token.hip)

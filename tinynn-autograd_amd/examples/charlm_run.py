@@ -8,6 +8,9 @@ token — so every position >= period can be predicted by attending one period b
 --generate N: after training, the first test sequences are continued greedily by N tokens from a prompt of 2 * period tokens
 (generation.generate: a key / value cache, every token chosen on the device), and the share of generated tokens that continue
 the motif is printed.
+
+--dropout P: dropout with rate P on the embedding's output and on both residual branches of every block (the fused residual
+form of ops.dropout_), drawn from the device generator of rng.py, which --seed seeds; 0, the default, adds no launch.
 """
 
 import argparse
@@ -21,6 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import tinynn_autograd_amd as tn                                                            # noqa: E402
+from tinynn_autograd_amd import rng                                                         # noqa: E402
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
 from tinynn_autograd_amd.generation import generate                                         # noqa: E402
 from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
@@ -50,9 +54,10 @@ def make_data(rs, count, seq, vocab, period):
 
 def build(args):
     fused = not args.composed
-    net = Net([Embedding(args.vocab, args.width, max_len=args.seq, fused=fused),
-               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused),
-               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused),
+    drop = args.dropout
+    net = Net([Embedding(args.vocab, args.width, max_len=args.seq, fused=fused, dropout=drop),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     loss_layer = CrossEntropyLoss(fused=fused)
     return Model(net=net, loss=loss_layer, optimizer=Adam(lr=args.lr)), loss_layer
@@ -61,6 +66,7 @@ def build(args):
 def main(args):
     if args.seed >= 0:
         np.random.seed(args.seed)
+    rng.manual_seed(max(args.seed, 0))                    # the device generator the dropout masks come from (host bookkeeping only)
     rs = np.random.RandomState(max(args.seed, 0))
     train_x, train_y = make_data(rs, args.n_train, args.seq, args.vocab, args.period)
     test_x, test_y = make_data(rs, args.n_test, args.seq, args.vocab, args.period)
@@ -117,6 +123,7 @@ def parse(argv=None):
     parser.add_argument("--heads", default=4, type=int)
     parser.add_argument("--period", default=4, type=int)
     parser.add_argument("--seed", default=0, type=int)
+    parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")
     parser.add_argument("--generate", default=0, type=int, help="continue the first test sequences greedily by N tokens")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
     return parser.parse_args(argv)

@@ -7,13 +7,13 @@ With the cache a step costs one row through every layer: the prompt runs once th
 whose k and v are slice-assigned into the cache), then every new token runs three projections of ONE row per attention
 layer and ops.attention_decode_ over the cached prefix — O(P + N) per layer instead of O((P + N)^2).
 
-The loop stays on the device.  The uniform numbers u [N, B] are drawn on the host (there is no device random generator)
-and uploaded ONCE; every sampled id is written into a device [B, P + N] buffer by ops.sample_rows_ and feeds the next
-step's Embedding as device ids; there is ONE read-back, at the end.  On the native route nothing synchronises with the host
+The loop stays on the device.  The uniform numbers u [N, B] are drawn on the host and uploaded ONCE — or, with
+`generator=` (rng.Generator), filled on the device by ONE Generator.uniform call, with no host draw and no upload; every
+sampled id is written into a device [B, P + N] buffer by ops.sample_rows_ and feeds the next step's Embedding as device ids; there is ONE read-back, at the end.  On the native route nothing synchronises with the host
 between the first and the last new token.  (On the composed route — the CPU test twin — sample_rows reads the logits back.)
 
 Out of scope: ragged batches (every sequence of the batch has the same length), grouped-query heads, chunked prefill (it
-needs a bottom-right causal rule), top-p, bf16, a device random generator, graph capture of the token loop.
+needs a bottom-right causal rule), top-p, bf16, graph capture of the token loop.
 """
 
 import inspect
@@ -108,11 +108,14 @@ def _forward(layers, ids, offset, cache):
     return x
 
 
-def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=None, u=None, seed=None, cache=True):
+def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=None, u=None, seed=None, cache=True,
+             generator=None):
     """Continue `prompt_ids` [B, P] (integers) by `max_new_tokens` tokens -> numpy int64 [B, P + N].
 
     temperature 0: greedy; otherwise token n of sequence b is the inverse CDF of softmax(logits / temperature) over the top_k
     largest (None: all) at u[n, b].  u: [N, B] numbers in [0, 1), given, or drawn from np.random.RandomState(seed).
+    generator: an rng.Generator — u is then its uniform((N, B)) in the dtype of the logits, ONE device fill that consumes one
+    call of the generator (stream element n B + b is u[n, b]); it excludes `u` and `seed`, and temperature 0 draws nothing.
     cache=True: a KVCache — the prompt runs once, every new token costs one row per layer.  cache=False: the whole growing
     prefix runs through the net every step — the independent route, and what the CPU test twin compares with.
     The net runs in phase TEST; the previous phase is restored.  P + N beyond an Embedding's max_len raises before any launch."""
@@ -130,7 +133,9 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
         if limit is not None and _takes(layer, "offset") and P + N > int(limit):
             raise ValueError("generate: %d prompt + %d new tokens exceed the embedding's max_len %d" % (P, N, int(limit)))
     temperature = float(temperature)
-    if temperature != 0.0:
+    if generator is not None and (u is not None or seed is not None):
+        raise ValueError("generate: `generator` draws u on the device — it excludes `u` and `seed`")
+    if temperature != 0.0 and generator is None:
         if u is None:
             u = np.random.RandomState(seed).random_sample((N, B))
         u = np.asarray(u, dtype=np.float64)
@@ -156,7 +161,9 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
             logits = _forward(layers, Tensor(ids), offset, kv)
             vocab = int(logits.shape[-1])
             last = ops.getitem_(ops.reshape(logits, (B, t, vocab)), (slice(None), t - 1))
-            if temperature != 0.0 and u_dev is None:
+            if temperature != 0.0 and u_dev is None and generator is not None:
+                u_dev = generator.uniform((N, B), last.values.dtype)       # (r 2^-24: exact in either dtype, below 1)
+            elif temperature != 0.0 and u_dev is None:
                 dt = last.values.dtype                         # (rounding to float32 must not produce 1.0)
                 u_dev = da.asarray(np.minimum(u.astype(dt), np.nextafter(dt.type(1), dt.type(0))))
             picked = ops.sample_rows_(last, None if u_dev is None else u_dev[n], temperature=temperature, top_k=top_k)
