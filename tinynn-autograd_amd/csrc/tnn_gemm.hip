@@ -734,6 +734,157 @@ __device__ __forceinline__ float adam_apply(const AdamEpi& ad, float ic1, float 
 __device__ unsigned long long g_step_trace[4 * 1024 * 4];        // tnn_internal.h: TNN_STEP_STAMP
 #endif
 
+// One operand of a weight-gradient tile in TN form ([K][ld], the tile's own index contiguous), read through buffer loads:
+// lane (i16, grp) owns k = 4 grp + row for the `row`s it is asked for (16 c + j) and the column `col`.  A k >= K, or a lane
+// whose column is outside the matrix (ok == false), gets the offset 0xffffffff and the hardware returns 0 — no exec-mask
+// branch around the load and nothing read outside the operand.  32-bit offsets: tn_extents_ok() at the dispatch site.
+struct TnFrag {
+    __amdgpu_buffer_rsrc_t rsrc;
+    uint32_t K, ld4, lane, k0;
+    bool ok;
+    __device__ __forceinline__ TnFrag(const float* p, int64_t K_, int64_t ld, int64_t extent, int grp, int64_t col, bool ok_)
+        : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (uint32_t)((K_ - 1) * ld + extent) * 4u, 0x00020000)),
+          K((uint32_t)K_), ld4((uint32_t)ld * 4u), lane((uint32_t)grp * 4u * (uint32_t)ld * 4u + (uint32_t)col * 4u),
+          k0((uint32_t)grp * 4u), ok(ok_) {}
+    __device__ __forceinline__ float load(const uint32_t row, const uint32_t byte_off) const {
+        uint32_t off = (ok & (row + k0 < K)) ? lane + row * ld4 + byte_off : 0xffffffffu;
+        asm("" : "+v"(off));      // opaque: left visible, the select is turned into a branch over two loads
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+    }
+};
+inline bool tn_extents_ok(const GemmArgs& g) {
+    return g.K * g.lda * 4 < (int64_t(1) << 31) && g.K * g.ldb * 4 < (int64_t(1) << 31);
+}
+
+// The K walk of those tiles: wave `wid` (wave-uniform) owns chunks wid, wid + WAVES, ... and takes them TN_MAXC at a time:
+// load(u, c) requests chunk c into fragment slot u, for every chunk of the batch, before mma(u) — the MFMAs and column-sum
+// adds of slot u — runs for the first of them.  A chunk that does not exist is skipped in both phases (wave-uniform branches).
+// Four chunks of a 16 x 32 tile are 48 fragment registers.  SINGLE: nchunks <= WAVES * TN_MAXC is the caller's contract.
+constexpr int TN_MAXC = 4;
+template <int WAVES, bool SINGLE, class L, class S, class M>
+__device__ __forceinline__ void tn_batches(const int wid, const int nchunks, L&& load, S&& loads_out, M&& mma) {
+    for (int c0 = wid; c0 < nchunks; c0 += WAVES * TN_MAXC) {
+        const int live = (nchunks - c0 + WAVES - 1) / WAVES;
+#pragma unroll
+        for (int u = 0; u < TN_MAXC; ++u)
+            if (u < live) load(u, c0 + u * WAVES);
+        __builtin_amdgcn_sched_barrier(0);                // no MFMA (and its wait) moves up between the loads
+        loads_out(c0 == wid);
+#pragma unroll
+        for (int u = 0; u < TN_MAXC; ++u)
+            if (u < live) mma(u);
+        if constexpr (SINGLE) break;
+    }
+}
+
+// Adam over the flat range [0, ad.fn) (the other layers' parameters) by the trailing workgroups of a dW0 launch: workgroup
+// `block` of `nblocks`, THREADS threads each.  Every load of a thread's batch is requested before anything waits on `pows`
+// (a scalar load and two f64 divisions) — with adam_flat_blocks() workgroups a range of the MNIST net's size is ONE 16-byte
+// load per array and thread, one round trip in all.  16-byte loads and stores when all four arrays are 16-byte aligned (the
+// n % 4 ragged end goes to the first threads of workgroup 0, requested up front as well), 4-byte ones otherwise; above the
+// cap on workgroups a thread requests FLAT_TRIPS trips' loads at a time.  An index past the end is clamped for the load (no
+// branch, nothing read outside the arrays) and skipped for the store.  The four arrays never overlap (ABI contract).
+constexpr int FLAT_MAX_BLOCKS = 64;
+inline int adam_flat_blocks(const void* p, const void* g, const void* m, const void* v, int64_t n, int threads) {
+    if (n <= 0) return 0;
+    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                       reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+    const int64_t units = vec ? (n + 3) / 4 : n;
+    return (int)std::min<int64_t>((units + threads - 1) / threads, FLAT_MAX_BLOCKS);
+}
+
+// adam_apply with its two multiply-adds spelled out, for the flat range: left to the compiler, g * g - v is fused in one
+// place and packed with g - m as a separate multiply and subtract in another (the 1 - 3 ragged elements were), one ulp apart.
+// These are the instructions the scalar loop this replaces was compiled to.
+__device__ __forceinline__ void adam_apply_to(const AdamEpi& ad, float ic1, float ic2, float g, float& m, float& v, float& p) {
+    m = __builtin_fmaf(1.f - ad.b1, g - m, m);
+    v = __builtin_fmaf(1.f - ad.b2, __builtin_fmaf(g, g, -v), v);
+    p = p + (-ad.lr * (m * ic1) / (sqrtf(v * ic2) + ad.eps));
+}
+__device__ __forceinline__ void adam_apply_to(const AdamEpi& ad, float ic1, float ic2, const f32x4& g, f32x4& m, f32x4& v, f32x4& p) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float mq = m[q], vq = v[q], pq = p[q];
+        adam_apply_to(ad, ic1, ic2, g[q], mq, vq, pq);
+        m[q] = mq;
+        v[q] = vq;
+        p[q] = pq;
+    }
+}
+
+// units [t, t + nth, ...) < n of width V (float or f32x4), TRIPS of them requested at a time; the reciprocals are computed
+// behind the first batch of loads
+template <class V, int TRIPS, bool STAMPS>
+__device__ __forceinline__ void adam_flat_walk(const AdamEpi& ad, V* __restrict__ fp, const V* __restrict__ fg, V* __restrict__ fm,
+                                               V* __restrict__ fv, const int64_t n, const int64_t t, const int64_t nth,
+                                               float& ic1, float& ic2) {
+    if (t >= n) return;
+    V p[TRIPS], g[TRIPS], m[TRIPS], v[TRIPS];
+    auto request = [&](const int64_t i0) {
+#pragma unroll
+        for (int u = 0; u < TRIPS; ++u) {
+            const int64_t i = i0 + u * nth, ic = i < n ? i : i0;
+            p[u] = fp[ic]; g[u] = fg[ic]; m[u] = fm[ic]; v[u] = fv[ic];
+        }
+    };
+    int64_t i0 = t;
+    request(i0);
+    __builtin_amdgcn_sched_barrier(0);                    // the loads are out before anything waits on pows
+    if constexpr (STAMPS) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1);
+    ic1 = (float)(1.0 / (1.0 - ad.pows[0]));
+    ic2 = (float)(1.0 / (1.0 - ad.pows[1]));
+    for (;;) {
+#pragma unroll
+        for (int u = 0; u < TRIPS; ++u) {
+            const int64_t i = i0 + u * nth;
+            if (i >= n) continue;
+            adam_apply_to(ad, ic1, ic2, g[u], m[u], v[u], p[u]);
+            fp[i] = p[u];
+            fm[i] = m[u];
+            fv[i] = v[u];
+        }
+        i0 += nth * TRIPS;
+        if (i0 >= n) break;
+        request(i0);
+    }
+}
+
+template <int THREADS, bool STAMPS>
+__device__ __forceinline__ void adam_flat_range(const AdamEpi& ad, const int block, const int nblocks) {
+    constexpr int FLAT_TRIPS = 2;
+    const int64_t n = ad.fn, t = (int64_t)block * THREADS + threadIdx.x, nth = (int64_t)nblocks * THREADS;
+    const bool vec = ((reinterpret_cast<uintptr_t>(ad.fp) | reinterpret_cast<uintptr_t>(ad.fg) | reinterpret_cast<uintptr_t>(ad.fm) |
+                       reinterpret_cast<uintptr_t>(ad.fv)) & 15) == 0;
+    float ic1 = 0.f, ic2 = 0.f;
+    if constexpr (STAMPS) TNN_STEP_STAMP(g_step_trace, 3, 0);
+    if (vec) {
+        const int64_t nv = n / 4, ri = nv * 4 + t;
+        const bool ragged = ri < n;                        // t < n % 4: the first threads of workgroup 0
+        float r_p = 0.f, r_g = 0.f, r_m = 0.f, r_v = 0.f;
+        if (ragged) { r_p = ad.fp[ri]; r_g = ad.fg[ri]; r_m = ad.fm[ri]; r_v = ad.fv[ri]; }
+        adam_flat_walk<f32x4, FLAT_TRIPS, STAMPS>(ad, reinterpret_cast<f32x4*>(ad.fp), reinterpret_cast<const f32x4*>(ad.fg),
+                                                  reinterpret_cast<f32x4*>(ad.fm), reinterpret_cast<f32x4*>(ad.fv), nv, t, nth, ic1, ic2);
+        if (ragged) {
+            if (t >= nv) {                                 // n < 4: no vector of its own in front
+                ic1 = (float)(1.0 / (1.0 - ad.pows[0]));
+                ic2 = (float)(1.0 / (1.0 - ad.pows[1]));
+            }
+            adam_apply_to(ad, ic1, ic2, r_g, r_m, r_v, r_p);
+            ad.fp[ri] = r_p;
+            ad.fm[ri] = r_m;
+            ad.fv[ri] = r_v;
+        }
+    } else {
+        adam_flat_walk<float, 2 * FLAT_TRIPS, STAMPS>(ad, ad.fp, ad.fg, ad.fm, ad.fv, n, t, nth, ic1, ic2);
+    }
+    if constexpr (STAMPS) TNN_STEP_STAMP(g_step_trace, 3, 2);
+    // s_waitcnt vmcnt(0): the kernel's two roles are laid out as one control-flow graph, and a load this role had left
+    // unawaited would count as possibly outstanding in the tile code — which then waits for its Adam state in front of the
+    // fragment loads, a whole round trip (seen in the gfx950 assembly).  Costs a wave that is about to end nothing.
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+    if constexpr (STAMPS) TNN_STEP_STAMP(g_step_trace, 3, 3);
+}
+
 template <bool AKC, bool BKC, int WAVES, bool ADAM = false, bool TO_LDS = false>
 __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict__ colsum, int block,
                                            float (*red)[4][64], float (*bsum)[64], const AdamEpi* ad = nullptr,
@@ -771,47 +922,69 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
             ab_p = ad->pb[n0 + tid]; ab_m = ad->mb[n0 + tid]; ab_v = ad->vb[n0 + tid];
         }
     }
-    for (int c = wid; c < nchunks; c += WAVES) {
-        const int64_t k = (int64_t)c * 16 + grp * 4;
-        float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (AKC) {
-            const float* p = g.A + am * g.lda + k;
-            if (a_ok) {
-                if (g.vecA && k + 3 < g.K) {
-                    float4 v = *reinterpret_cast<const float4*>(p);
-                    a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
-                } else {
+    if constexpr (ADAM) {
+        // the first layer's weight gradient (TN form): all of a wave's chunks requested before its first MFMA, as in dw_tile_wide
+        static_assert(!AKC && !BKC, "the Adam epilogue belongs to dW = X^T dZ");
+        const TnFrag fa(g.A, g.K, g.lda, g.M, grp, am, a_ok), fb(g.B, g.K, g.ldb, g.N, grp, bn, b_ok);
+        const int swid = __builtin_amdgcn_readfirstlane(wid);
+        float a[TN_MAXC][4], b[TN_MAXC][4];
+        tn_batches<WAVES, false>(
+            swid, nchunks,
+            [&](const int u, const int c) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) if (k + j < g.K) a[j] = p[j];
+                for (int j = 0; j < 4; ++j) {
+                    a[u][j] = fa.load((uint32_t)c * 16u + (uint32_t)j, 0u);
+                    b[u][j] = fb.load((uint32_t)c * 16u + (uint32_t)j, 0u);
+                }
+            },
+            [&](const bool first) { if (first) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); },   // (first batch's operands + the Adam state)
+            [&](const int u) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
+                bs += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
+            });
+    } else {
+        for (int c = wid; c < nchunks; c += WAVES) {
+            const int64_t k = (int64_t)c * 16 + grp * 4;
+            float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (AKC) {
+                const float* p = g.A + am * g.lda + k;
+                if (a_ok) {
+                    if (g.vecA && k + 3 < g.K) {
+                        float4 v = *reinterpret_cast<const float4*>(p);
+                        a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (k + j < g.K) a[j] = p[j];
+                    }
+                }
+            } else {
+                if (a_ok) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if (k + j < g.K) a[j] = g.A[(k + j) * g.lda + am];
                 }
             }
-        } else {
-            if (a_ok) {
+            if constexpr (BKC) {
+                const float* p = g.B + bn * g.ldb + k;
+                if (b_ok) {
+                    if (g.vecB && k + 3 < g.K) {
+                        float4 v = *reinterpret_cast<const float4*>(p);
+                        b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
+                    } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) if (k + j < g.K) a[j] = g.A[(k + j) * g.lda + am];
-            }
-        }
-        if constexpr (BKC) {
-            const float* p = g.B + bn * g.ldb + k;
-            if (b_ok) {
-                if (g.vecB && k + 3 < g.K) {
-                    float4 v = *reinterpret_cast<const float4*>(p);
-                    b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
-                } else {
+                        for (int j = 0; j < 4; ++j) if (k + j < g.K) b[j] = p[j];
+                    }
+                }
+            } else {
+                if (b_ok) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) if (k + j < g.K) b[j] = p[j];
+                    for (int j = 0; j < 4; ++j) if (k + j < g.K) b[j] = g.B[(k + j) * g.ldb + bn];
                 }
             }
-        } else {
-            if (b_ok) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) if (k + j < g.K) b[j] = g.B[(k + j) * g.ldb + bn];
-            }
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
+            bs += (b[0] + b[1]) + (b[2] + b[3]);
         }
-        if constexpr (ADAM) { if (c == wid) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); }      // (first chunk's operands + the Adam state)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
-        bs += (b[0] + b[1]) + (b[2] + b[3]);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc[r];
@@ -930,26 +1103,34 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     float bs0 = 0.f, bs1 = 0.f;
     if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);
-    for (int c = wid; c < nchunks; c += WAVES) {
-        const int64_t k = (int64_t)c * 16 + grp * 4;
-        float a[4] = {0.f, 0.f, 0.f, 0.f}, b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f};
+    // K loop: a wave requests the fragments of ALL its chunks (batches of up to TN_MAXC) before its first MFMA — one load round
+    // trip per batch instead of one per chunk.  Buffer loads: a row k >= K (or a row of A past M) gets the offset 0xffffffff
+    // and reads 0, no exec-mask branch; chunks that do not exist cost neither loads nor MFMAs (tn_batches).  Chunk order, the
+    // two accumulator chains and the column-sum adds are those of the chunk-per-trip loop this replaces: the same bits.
+    const TnFrag fa(g.A, g.K, g.lda, g.M, grp, am, a_ok), fb(g.B, g.K, g.ldb, g.N, grp, bn, true);
+    const int swid = __builtin_amdgcn_readfirstlane(wid);
+    float a[TN_MAXC][4], b0[TN_MAXC][4], b1[TN_MAXC][4];
+    tn_batches<WAVES, true>(                              // at most 16 chunks on 4 waves (dispatch sites): one batch
+        swid, nchunks,
+        [&](const int u, const int c) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (k + j < g.K) {
-                if (a_ok) a[j] = g.A[(k + j) * g.lda + am];
-                b0[j] = g.B[(k + j) * g.ldb + bn];
-                b1[j] = g.B[(k + j) * g.ldb + bn + 16];
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t row = (uint32_t)c * 16u + (uint32_t)j;         // + 4 grp: this lane's k
+                a[u][j] = fa.load(row, 0u);
+                b0[u][j] = fb.load(row, 0u);
+                b1[u][j] = fb.load(row, 64u);
             }
-        }
-        if constexpr (ADAM) { if (c == wid) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); }
+        },
+        [&](const bool first) { if constexpr (ADAM) { if (first) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); } },
+        [&](const int u) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b0[j], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b1[j], acc1, 0, 0, 0);
-        }
-        bs0 += (b0[0] + b0[1]) + (b0[2] + b0[3]);
-        bs1 += (b1[0] + b1[1]) + (b1[2] + b1[3]);
-    }
+            for (int j = 0; j < 4; ++j) {
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b0[u][j], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b1[u][j], acc1, 0, 0, 0);
+            }
+            bs0 += (b0[u][0] + b0[u][1]) + (b0[u][2] + b0[u][3]);
+            bs1 += (b1[u][0] + b1[u][1]) + (b1[u][2] + b1[u][3]);
+        });
 #pragma unroll
     for (int r = 0; r < 4; ++r) { red[wid][r][lane] = acc0[r]; red[wid][4 + r][lane] = acc1[r]; }
     bsum[wid][0][lane] = bs0;
@@ -1514,8 +1695,10 @@ void pick_xcd_cut(GemmArgs& g) {
 bool small_fast_ok(const GemmArgs& g, int transA, int transB) {
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const bool akc = !transA, bkc = transB != 0;
-    // measured on the MNIST layers: NN fwd1 3.41 -> 2.87 us, fwd0 4.50 -> 4.26; the TN products (both operands read
-    // with 4-B loads either way) 3.98 -> 4.24 — they keep the plain loop
+    // measured on the MNIST layers: NN fwd1 3.41 -> 2.87 us, fwd0 4.50 -> 4.26.  The plain TN products keep the chunk-per-trip
+    // loop; the first layer's weight gradient with Adam (dw_tile_wide, small_tile<.., ADAM>) has its own up-front form, which
+    // skips the MFMAs of chunks that do not exist: dense_bwd0_adam_kernel 5.4 -> 4.9 us at 128 rows, 6.5 -> 5.7 at 256 (kernel
+    // trace), step 20.09 -> 19.80 / 25.81 -> 25.13 us (profiles/bwd0_roundtrips_ab.txt)
     if (!akc && !bkc) return false;
     if (akc && !(al(g.A) && g.lda % 4 == 0 && g.K % 4 == 0)) return false;
     if (bkc && !(al(g.B) && g.ldb % 4 == 0 && g.K % 4 == 0)) return false;
@@ -1537,14 +1720,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_bwd0_adam_kernel(GemmArgs gw
         else small_tile<false, false, WAVES, true>(gw, db, (int)blockIdx.x, red, reinterpret_cast<float(*)[64]>(bsum), &ad);
         return;
     }
-    const float ic1 = (float)(1.0 / (1.0 - ad.pows[0])), ic2 = (float)(1.0 / (1.0 - ad.pows[1]));
-    const int64_t nth = (int64_t)(gridDim.x - n_dw) * blockDim.x;
-    for (int64_t i = (int64_t)(blockIdx.x - n_dw) * blockDim.x + threadIdx.x; i < ad.fn; i += nth) {
-        float m = ad.fm[i], v = ad.fv[i];
-        ad.fp[i] = adam_apply(ad, ic1, ic2, ad.fg[i], m, v, ad.fp[i]);
-        ad.fm[i] = m;
-        ad.fv[i] = v;
-    }
+    adam_flat_range<WAVES * 64, true>(ad, (int)blockIdx.x - n_dw, (int)gridDim.x - n_dw);
 }
 
 // Backward of the FIRST Dense layer + gradient all-reduce + Adam in ONE launch (data-parallel step on the xGMI peer-to-peer
@@ -1851,14 +2027,7 @@ __global__ __launch_bounds__(512) void gemm_mid_f32_kernel(GemmArgs g, float* __
     constexpr uint32_t OOB = 0xffffffffu;
     if constexpr (ADAM) {
         if ((int)blockIdx.x >= n_tiles) {               // trailing workgroups: Adam over the other layers' flat range
-            const float ic1 = (float)(1.0 / (1.0 - ad.pows[0])), ic2 = (float)(1.0 / (1.0 - ad.pows[1]));
-            const int64_t nth = (int64_t)(gridDim.x - n_tiles) * blockDim.x;
-            for (int64_t i = (int64_t)(blockIdx.x - n_tiles) * blockDim.x + threadIdx.x; i < ad.fn; i += nth) {
-                float m = ad.fm[i], v = ad.fv[i];
-                ad.fp[i] = adam_apply(ad, ic1, ic2, ad.fg[i], m, v, ad.fp[i]);
-                ad.fm[i] = m;
-                ad.fv[i] = v;
-            }
+            adam_flat_range<512, false>(ad, (int)blockIdx.x - n_tiles, (int)gridDim.x - n_tiles);
             return;
         }
     }
@@ -2351,7 +2520,7 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
         gw.A = (const float*)x; gw.B = (const float*)dz; gw.C = (float*)dw;
         gw.M = n_in; gw.N = n_out; gw.K = rows; gw.lda = n_in; gw.ldb = n_out; gw.ldc = n_out;
         gw.alpha = 1.f; gw.beta = 0.f; gw.epi = EPI_AXPBY;
-        if (use_small_path(gw)) {
+        if (use_small_path(gw) && tn_extents_ok(gw)) {
             const bool mid = use_mid_path(gw, 1, 0);                 // bs >= 512: 32 x 32 tiles (gemm_mid_f32_kernel)
             if (mid) mid_geometry(gw);
             else { gw.tiles_m = (int)((gw.M + 15) / 16); gw.tiles_n = (int)((gw.N + 15) / 16); gw.splits = 1; }
@@ -2367,14 +2536,14 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
             const int nchunks = (int)((gw.K + 15) / 16);
             hipStream_t s = tnn::stream();
             if (mid) {
-                const int extra = ad.fn > 0 ? (int)std::min<int64_t>((ad.fn + 511) / 512, 64) : 0;
+                const int extra = adam_flat_blocks(ad.fp, ad.fg, ad.fm, ad.fv, ad.fn, 512);
                 hipLaunchKernelGGL((gemm_mid_f32_kernel<false, false, true>), n_dw + extra, 512, 0, s, gw, (float*)db, ad, n_dw);
                 TNN_LAUNCH_OK();
                 return 0;
             }
 #define TNN_BWD0(W)                                                                                         \
     do {                                                                                                    \
-        const int extra = ad.fn > 0 ? (int)std::min<int64_t>((ad.fn + W * 64 - 1) / (W * 64), 64) : 0;      \
+        const int extra = adam_flat_blocks(ad.fp, ad.fg, ad.fm, ad.fv, ad.fn, W * 64);                      \
         hipLaunchKernelGGL((dense_bwd0_adam_kernel<W>), n_dw + extra, W * 64, 0, s, gw, (float*)db, ad, n_dw); \
     } while (0)
             // 16 x 32 tiles (dw_tile_wide): half the workgroups, at most two per CU for the MNIST net's 784 x 256 gradient
@@ -2382,13 +2551,16 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
                 gw.tiles_n = (int)(gw.N / 32);
                 pick_xcd_cut(gw);
                 const int n_wide = gw.tiles_m * gw.tiles_n;
-                const int extra = ad.fn > 0 ? (int)std::min<int64_t>((ad.fn + 255) / 256, 64) : 0;
+                const int extra = adam_flat_blocks(ad.fp, ad.fg, ad.fm, ad.fv, ad.fn, 256);
                 hipLaunchKernelGGL((dense_bwd0_adam_kernel<4, true>), n_wide + extra, 256, 0, s, gw, (float*)db, ad, n_wide);
                 TNN_LAUNCH_OK();
                 return 0;
             }
-            // measured at bs 128 (8 chunks): 4 waves with two chunks each 21.5 us/step, 8 waves with one chunk each 22.2, 16
-            // waves 23.7 — the launch's 784 workgroups cost more per wave than the second load round trip saves
+            // 4 waves up to 16 chunks: a wave requests all its chunks (up to four) in ONE load round trip (tn_batches), so more
+            // waves buy no shorter chain of round trips, only more waves to place.  With 392 wide tiles the up-front form took
+            // the tile workgroups' last store from 3.17 to 2.71 us after the launch's first entry at 128 rows
+            // (profiles/bwd0_roundtrips_stamps.txt); the flat-range workgroups end at 1.75 us, never last.  (Round 4, 784
+            // workgroups, chunk per trip: 4 waves 21.5 us/step, 8 waves 22.2, 16 waves 23.7.)
             const int waves = nchunks <= 16 ? 4 : nchunks <= 48 ? 8 : 16;
             // (one WAVE per tile over the whole K, four tiles per workgroup — a quarter of the waves for the dispatcher to place —
             // was built and measured in round 4: bit-identical, 22.5 instead of 21.4 us/step; the per-wave chain of 64 loads
@@ -2454,7 +2626,7 @@ int tnn_dense_bwd_first_allreduce_adam(int64_t rows, int64_t n_in, int64_t n_out
         tnn::p2p::LaunchCtx ctx;
         // one launch: the latency kernel's 4-wave form (<= 256 rows per rank), every float4 of the layer's blocks whole and
         // inside one slice, the transport up and large enough
-        if (aligned && use_small_path(gw) && !use_mid_path(gw, 1, 0) && rows <= 256 && n_out % 4 == 0 && w_off % 4 == 0 &&
+        if (aligned && use_small_path(gw) && tn_extents_ok(gw) && !use_mid_path(gw, 1, 0) && rows <= 256 && n_out % 4 == 0 && w_off % 4 == 0 &&
             b_off % 4 == 0 && (!scalar_dst || scalar_index >= n_params) &&
             tnn::p2p_can_allreduce(n_reduce, dtype, TNN_RSUM) && tnn::p2p_launch_ctx(&ctx)) {
             if (int rc = tnn::p2p_refuse_if_failed("tnn_dense_bwd_first_allreduce_adam")) return rc;

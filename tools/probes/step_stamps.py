@@ -4,7 +4,8 @@ launches from the debug library (`make -C tinynn-autograd_amd/csrc trace`, -DTNN
     TNN_LIB_PATH=tinynn-autograd_amd/lib/libtnn_hip_trace.so python3 tools/probes/step_stamps.py > profiles/r06_stepA_stamps.txt
 For every launch, over its workgroups and 40 traced steps, relative to the launch's first workgroup entry (10 ns steps):
     entry | operands in registers (s_waitcnt vmcnt(0) behind the product's loads) | last MFMA + cross-wave sum read back | last store acknowledged
-and how many workgroups the launch has against the 256 CUs.  (The stamps cost a few hundred ns per launch: the sum of the traced
+and how many workgroups the launch has against the 256 CUs.  The last launch's flat-range Adam workgroups (behind its tiles) are
+printed as a role of their own: entry | loads landed | last update computed | last store acknowledged.  (The stamps cost a few hundred ns per launch: the sum of the traced
 launches is longer than the untraced step; the STAGES are what this is for.)"""
 import ctypes
 import os
@@ -82,6 +83,18 @@ for k in range(4):
         byx = [np.median(dur[:, x::8]) for x in range(8)]
         print("    dx tiles, median duration by XCD (index mod 8):", " ".join("%.2f" % v for v in byx))
     if k == 3:
+        # the flat-range Adam workgroups behind the tiles (W1 / b1 / W2 / b2: one 16-byte vector per thread) as a role of their own
+        nf = (34186 // 4 + 1 + 255) // 256
+        fl = tr[:, k, n:n + nf, :]
+        if (fl[:, :, 0] > 0).all():
+            frel = (fl - t0) / 100.0
+            print("    (%d flat-range Adam workgroups, against the first TILE entry:" % nf)
+            for s_, label in enumerate(("entry", "loads landed", "last update computed", "last store acknowledged")):
+                v = frel[:, :, s_]
+                print("        %-26s min %6.2f   med %6.2f   max %6.2f" % (label, np.median(v.min(axis=1)), np.median(v), np.median(v.max(axis=1))))
+            print("    )")
+        else:
+            print("    (flat-range Adam workgroups: not stamped by this library)")
         done = rel[:, :, 3].mean(axis=0)
         order = np.argsort(done)
         print("    slowest workgroups (index: end):", ", ".join("%d: %.2f" % (i, done[i]) for i in order[-8:]))
