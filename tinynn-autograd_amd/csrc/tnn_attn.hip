@@ -24,12 +24,12 @@
 
 #include <math.h>
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_attn.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using tnn::f32x4;
 
 constexpr int BQ = TNN_ATTN_BLOCK_Q, BKV = TNN_ATTN_BLOCK_K, WR = TNN_ATTN_WAVE_ROWS;
 static_assert(BQ == BKV && BQ == 4 * WR && TNN_ATTN_MFMA_K == 4, "the kernels assume 64 x 64 blocks of four 16-row waves");
@@ -501,13 +501,13 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_f64(AttnArgs a) {
 Opnd operand(const void* base, const int64_t* s, int dtype) {
     Opnd o;
     o.sb = s[0]; o.sh = s[1]; o.sr = s[2];
-    o.vec = dtype == TNN_F32 && (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (o.sb & 3) == 0 && (o.sh & 3) == 0 && (o.sr & 3) == 0;
+    o.vec = dtype == TNN_F32 && tnn::aligned16(base) && (o.sb & 3) == 0 && (o.sh & 3) == 0 && (o.sr & 3) == 0;
     return o;
 }
 
 int check_geometry(const char* who, int64_t B, int64_t H, int64_t Tq, int64_t Tk, int64_t D, int64_t Dv,
                    const int64_t* strides, int nstrides, int dtype) {
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, "%s: dtype %d (float32 / float64 only)", who, dtype);
+    TNN_REQUIRE_FLOAT(who);
     TNN_REQUIRE(B >= 0 && H >= 0 && Tq >= 0, "%s: negative extent", who);
     TNN_REQUIRE(Tk >= 1, "%s: Tk = %lld (softmax over no keys)", who, (long long)Tk);
     TNN_REQUIRE(D >= 1 && Dv >= 1 && D <= TNN_ATTN_MAX_HEAD_DIM && Dv <= TNN_ATTN_MAX_HEAD_DIM,

@@ -20,13 +20,13 @@
 // four elements inside the row); everything else is read element by element under the same bounds checks.
 // float64: one thread per element of C (the exact-test mode; correctness, not speed).
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_bmm.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using tnn::f32x4;
+using tnn::f32x16;
 
 constexpr int kMaxB = TNN_BMM_MAX_BATCH_DIMS;
 
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(256) void bmm_f64_kernel(BmmArgs g) {
     } while (0)
 
 bool vec_ok(const void* base, int64_t ld, const int64_t* bs) {
-    if ((reinterpret_cast<uintptr_t>(base) & 15) != 0 || (ld & 3) != 0) return false;
+    if (!tnn::aligned16(base) || (ld & 3) != 0) return false;
     for (int d = 0; d < kMaxB; ++d)
         if ((bs[d] & 3) != 0) return false;
     return true;
@@ -281,7 +281,7 @@ extern "C" int tnn_gemm_batched(int transA, int transB, int64_t M, int64_t N, in
                                 int nbatch, const int64_t* batch_shape, const int64_t* a_bstride, const int64_t* b_bstride,
                                 int dtype, int form) {
     TNN_NEED_INIT();
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, "tnn_gemm_batched: dtype %d (float32 / float64 only)", dtype);
+    TNN_REQUIRE_FLOAT("tnn_gemm_batched");
     TNN_REQUIRE(M >= 0 && N >= 0 && K >= 0, "tnn_gemm_batched: negative extent");
     TNN_REQUIRE(nbatch >= 0 && nbatch <= kMaxB, "tnn_gemm_batched: %d batch dimensions (at most %d)", nbatch, kMaxB);
     TNN_REQUIRE(nbatch == 0 || (batch_shape && a_bstride && b_bstride), "tnn_gemm_batched: batch arrays missing");

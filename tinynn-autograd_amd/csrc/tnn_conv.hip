@@ -26,13 +26,13 @@
 // Pooling: one thread per output pixel forward (first maximum in row-major order, its offset recorded), one thread per INPUT
 // pixel backward (sums the few windows that recorded it, in a fixed order).
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_conv.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using tnn::f32x4;
+using tnn::f32x16;
 
 enum { FWD = 0, BWD_DATA = 1, BWD_FILTER = 2 };
 
@@ -405,7 +405,6 @@ int fill_pool(PoolArgs& g, const char* who, int64_t planes, int64_t H, int64_t W
 
 }  // namespace
 
-#define TNN_CONV_DTYPE(who) TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, who ": dtype %d (float32 / float64 only)", dtype)
 #define TNN_CONV_FORM(who) \
     TNN_REQUIRE(form >= TNN_CONV_FORM_AUTO && form <= TNN_CONV_FORM_SMALL, who ": form %d", form)
 
@@ -413,7 +412,7 @@ extern "C" int tnn_conv2d_fwd(const void* x, const void* w, const void* b, void*
                               int64_t N, int64_t C, int64_t H, int64_t W, int64_t F, int64_t KH, int64_t KW,
                               int64_t sh, int64_t sw, int64_t ph, int64_t pw, int relu, int dtype, int form) {
     TNN_NEED_INIT();
-    TNN_CONV_DTYPE("tnn_conv2d_fwd");
+    TNN_REQUIRE_FLOAT("tnn_conv2d_fwd");
     TNN_CONV_FORM("tnn_conv2d_fwd");
     ConvArgs g;
     if (int rc = fill_geometry(g, "tnn_conv2d_fwd", N, C, H, W, F, KH, KW, sh, sw, ph, pw)) return rc;
@@ -429,7 +428,7 @@ extern "C" int tnn_conv2d_bwd_data(const void* dy, const void* w, void* dx,
                                    int64_t N, int64_t C, int64_t H, int64_t W, int64_t F, int64_t KH, int64_t KW,
                                    int64_t sh, int64_t sw, int64_t ph, int64_t pw, int dtype, int form) {
     TNN_NEED_INIT();
-    TNN_CONV_DTYPE("tnn_conv2d_bwd_data");
+    TNN_REQUIRE_FLOAT("tnn_conv2d_bwd_data");
     TNN_CONV_FORM("tnn_conv2d_bwd_data");
     ConvArgs g;
     if (int rc = fill_geometry(g, "tnn_conv2d_bwd_data", N, C, H, W, F, KH, KW, sh, sw, ph, pw)) return rc;
@@ -455,7 +454,7 @@ extern "C" int tnn_conv2d_bwd_filter(const void* x, const void* dy, void* dw, vo
                                      int64_t N, int64_t C, int64_t H, int64_t W, int64_t F, int64_t KH, int64_t KW,
                                      int64_t sh, int64_t sw, int64_t ph, int64_t pw, int dtype, int form, int splits) {
     TNN_NEED_INIT();
-    TNN_CONV_DTYPE("tnn_conv2d_bwd_filter");
+    TNN_REQUIRE_FLOAT("tnn_conv2d_bwd_filter");
     TNN_CONV_FORM("tnn_conv2d_bwd_filter");
     ConvArgs g;
     if (int rc = fill_geometry(g, "tnn_conv2d_bwd_filter", N, C, H, W, F, KH, KW, sh, sw, ph, pw)) return rc;
@@ -481,7 +480,7 @@ extern "C" int tnn_conv2d_bwd_filter(const void* x, const void* dy, void* dw, vo
 extern "C" int tnn_maxpool2d_fwd(const void* x, void* y, void* idx, int64_t planes, int64_t H, int64_t W,
                                  int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int dtype) {
     TNN_NEED_INIT();
-    TNN_CONV_DTYPE("tnn_maxpool2d_fwd");
+    TNN_REQUIRE_FLOAT("tnn_maxpool2d_fwd");
     PoolArgs g;
     if (int rc = fill_pool(g, "tnn_maxpool2d_fwd", planes, H, W, KH, KW, sh, sw, ph, pw)) return rc;
     if (planes == 0) return 0;
@@ -489,8 +488,7 @@ extern "C" int tnn_maxpool2d_fwd(const void* x, void* y, void* idx, int64_t plan
     g.in = x; g.in2 = nullptr; g.out = y; g.idx = static_cast<int*>(idx);
     const unsigned grid = tnn::stream_grid(planes * g.OH * g.OW);
     hipStream_t s = tnn::stream();
-    if (dtype == TNN_F32) hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid), dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(maxpool_fwd_kernel<double>, dim3(grid), dim3(256), 0, s, g);
+    tnn::with_float(dtype, [&](auto t) { hipLaunchKernelGGL(maxpool_fwd_kernel<decltype(t)>, dim3(grid), dim3(256), 0, s, g); });
     TNN_LAUNCH_OK();
     return 0;
 }
@@ -498,7 +496,7 @@ extern "C" int tnn_maxpool2d_fwd(const void* x, void* y, void* idx, int64_t plan
 extern "C" int tnn_maxpool2d_bwd(const void* dy, const void* idx, void* dx, int64_t planes, int64_t H, int64_t W,
                                  int64_t KH, int64_t KW, int64_t sh, int64_t sw, int64_t ph, int64_t pw, int dtype) {
     TNN_NEED_INIT();
-    TNN_CONV_DTYPE("tnn_maxpool2d_bwd");
+    TNN_REQUIRE_FLOAT("tnn_maxpool2d_bwd");
     PoolArgs g;
     if (int rc = fill_pool(g, "tnn_maxpool2d_bwd", planes, H, W, KH, KW, sh, sw, ph, pw)) return rc;
     if (planes == 0) return 0;
@@ -506,8 +504,7 @@ extern "C" int tnn_maxpool2d_bwd(const void* dy, const void* idx, void* dx, int6
     g.in = dy; g.in2 = idx; g.out = dx; g.idx = nullptr;
     const unsigned grid = tnn::stream_grid(planes * g.H * g.W);
     hipStream_t s = tnn::stream();
-    if (dtype == TNN_F32) hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid), dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(maxpool_bwd_kernel<double>, dim3(grid), dim3(256), 0, s, g);
+    tnn::with_float(dtype, [&](auto t) { hipLaunchKernelGGL(maxpool_bwd_kernel<decltype(t)>, dim3(grid), dim3(256), 0, s, g); });
     TNN_LAUNCH_OK();
     return 0;
 }

@@ -20,10 +20,12 @@
 
 #include <math.h>
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_decode.h"
 
 namespace {
+
+using namespace tnn;      // Pack, Math, aligned16, item_of, round16, with_float (tnn_pack.h)
 
 constexpr int THREADS = 256;
 constexpr int WAVES = THREADS / 64;
@@ -35,13 +37,6 @@ constexpr int BINS = 1 << TNN_SAMPLE_RADIX_BITS;
 static_assert(TNN_DECODE_VEC == 16, "wide accesses are global_load / store_dwordx4");
 static_assert(BINS == THREADS, "one thread clears one bin of the histogram");
 static_assert(MAXD <= 128, "two element packs per lane cover a row");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-template <typename T, bool VECTOR> struct Pack { typedef T type; static constexpr int N = 1; };
-template <> struct Pack<float, true> { typedef f32x4 type; static constexpr int N = 4; };
-template <> struct Pack<double, true> { typedef f64x2 type; static constexpr int N = 2; };
 
 __device__ __forceinline__ float dot_pack(float a, float b, float d) { return fmaf(a, b, d); }
 __device__ __forceinline__ double dot_pack(double a, double b, double d) { return fma(a, b, d); }
@@ -62,14 +57,6 @@ __device__ __forceinline__ f64x2 xor_pack(f64x2 v, int o) {
     r.x = __shfl_xor(v.x, o, 64); r.y = __shfl_xor(v.y, o, 64);
     return r;
 }
-
-template <typename T> struct Math;
-template <> struct Math<float> {
-    static __device__ __forceinline__ float exp_(float v) { return expf(v); }
-};
-template <> struct Math<double> {
-    static __device__ __forceinline__ double exp_(double v) { return exp(v); }
-};
 
 // ------------------------------------------------------------------------------------------------ decode attention
 struct DecodeArgs {
@@ -455,9 +442,6 @@ __global__ __launch_bounds__(THREADS) void sample_kernel(const T* __restrict__ l
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (TNN_DECODE_VEC - 1)) == 0; }
-inline int64_t item_of(int dtype) { return dtype == TNN_F32 ? 4 : 8; }
-inline int64_t round16(int64_t n) { return (n + 15) / 16 * 16; }
 inline int64_t decode_space(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype) {
     return splits == 1 ? 0 : round16(B * H * splits * (Dv + 2) * item_of(dtype));
 }
@@ -472,12 +456,9 @@ void launch_decode(const DecodeArgs& a, bool vec, int R, dim3 grid) {
 
 }  // namespace
 
-#define TNN_DECODE_DTYPE(name) \
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, name ": dtype %d (float32 and float64 only)", dtype)
-
 extern "C" int tnn_decode_attn_workspace(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype, int64_t* bytes) {
     TNN_REQUIRE(bytes != nullptr, "tnn_decode_attn_workspace: null result pointer");
-    TNN_DECODE_DTYPE("tnn_decode_attn_workspace");
+    TNN_REQUIRE_FLOAT("tnn_decode_attn_workspace");
     TNN_REQUIRE(B >= 0 && H >= 0 && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM && splits >= 1 && splits <= TNN_DECODE_MAX_SPLITS,
                 "tnn_decode_attn_workspace: B %lld, H %lld, Dv %lld, splits %lld (Dv <= %d, splits <= %d)", (long long)B,
                 (long long)H, (long long)Dv, (long long)splits, TNN_ATTN_MAX_HEAD_DIM, TNN_DECODE_MAX_SPLITS);
@@ -489,7 +470,7 @@ extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_n
                                void* workspace, int64_t workspace_bytes, int64_t B, int64_t H, int64_t len, int64_t Tmax,
                                int64_t D, int64_t Dv, const int64_t* strides, double scale, int64_t splits, int dtype) {
     TNN_NEED_INIT();
-    TNN_DECODE_DTYPE("tnn_decode_attn");
+    TNN_REQUIRE_FLOAT("tnn_decode_attn");
     TNN_REQUIRE(B >= 0 && H >= 0 && B * H < 65536 && D >= 1 && D <= TNN_ATTN_MAX_HEAD_DIM && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM,
                 "tnn_decode_attn: B %lld, H %lld, D %lld, Dv %lld (B H < 65536, 1 <= D, Dv <= %d)", (long long)B, (long long)H,
                 (long long)D, (long long)Dv, TNN_ATTN_MAX_HEAD_DIM);
@@ -505,9 +486,7 @@ extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_n
     if (B * H == 0) return 0;
     TNN_REQUIRE(q && k_cache && v_cache && o && strides, "tnn_decode_attn: null operand");
     const int64_t need = decode_space(B, H, splits, Dv, dtype);
-    TNN_REQUIRE(splits == 1 || (workspace != nullptr && workspace_bytes >= need && aligned16(workspace)),
-                "tnn_decode_attn: workspace of %lld bytes, %lld needed (16-byte aligned)", (long long)workspace_bytes,
-                (long long)need);
+    if (splits > 1) TNN_REQUIRE_WORKSPACE("tnn_decode_attn", workspace, workspace_bytes, need);
 
     DecodeArgs a = {};
     a.q = q; a.k_new = k_new; a.v_new = v_new; a.k_cache = k_cache; a.v_cache = v_cache; a.o = o; a.ws = workspace;
@@ -533,12 +512,12 @@ extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_n
     while (a.G < lanes) { a.G <<= 1; ++a.log_g; }
 
     const dim3 grid((unsigned)splits, (unsigned)(B * H));
-    if (dtype == TNN_F32) launch_decode<float>(a, vec, R, grid);
-    else launch_decode<double>(a, vec, R, grid);
+    with_float(dtype, [&](auto t) { launch_decode<decltype(t)>(a, vec, R, grid); });
     TNN_LAUNCH_OK();
     if (splits > 1) {
-        if (dtype == TNN_F32) hipLaunchKernelGGL(decode_combine_kernel<float>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
-        else hipLaunchKernelGGL(decode_combine_kernel<double>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
+        with_float(dtype, [&](auto t) {
+            hipLaunchKernelGGL(decode_combine_kernel<decltype(t)>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
+        });
         TNN_LAUNCH_OK();
     }
     return 0;
@@ -547,19 +526,18 @@ extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_n
 extern "C" int tnn_sample_rows(const void* logits, const void* u, void* out_ids, int64_t M, int64_t V, double temperature,
                                int64_t top_k, int dtype) {
     TNN_NEED_INIT();
-    TNN_DECODE_DTYPE("tnn_sample_rows");
+    TNN_REQUIRE_FLOAT("tnn_sample_rows");
     TNN_REQUIRE(M >= 0 && V >= 1 && V < (1ll << 31), "tnn_sample_rows: M %lld, V %lld (1 <= V < 2^31)", (long long)M, (long long)V);
     TNN_REQUIRE(temperature >= 0.0 && temperature < INFINITY, "tnn_sample_rows: temperature %g (finite, >= 0)", temperature);
     TNN_REQUIRE(top_k >= 0, "tnn_sample_rows: top_k %lld (0: every column)", (long long)top_k);
     if (M == 0) return 0;
     TNN_REQUIRE(logits && out_ids && (u || temperature == 0.0), "tnn_sample_rows: null operand");
     const int k = top_k >= V ? 0 : (int)top_k;
-    if (dtype == TNN_F32)
-        hipLaunchKernelGGL(sample_kernel<float>, dim3((unsigned)M), dim3(THREADS), 0, tnn::stream(), static_cast<const float*>(logits),
-                           static_cast<const float*>(u), static_cast<int64_t*>(out_ids), (int)V, (float)temperature, k);
-    else
-        hipLaunchKernelGGL(sample_kernel<double>, dim3((unsigned)M), dim3(THREADS), 0, tnn::stream(), static_cast<const double*>(logits),
-                           static_cast<const double*>(u), static_cast<int64_t*>(out_ids), (int)V, temperature, k);
+    with_float(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(sample_kernel<T>, dim3((unsigned)M), dim3(THREADS), 0, tnn::stream(), static_cast<const T*>(logits),
+                           static_cast<const T*>(u), static_cast<int64_t*>(out_ids), (int)V, (T)temperature, k);
+    });
     TNN_LAUNCH_OK();
     return 0;
 }

@@ -16,7 +16,7 @@
 // The ticket launch (one thread) copies {seed, calls} into the caller's ticket and advances calls; the data launch behind it
 // in stream order reads only the ticket.  Nothing is atomic and nothing waits.
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_dropout.h"
 
 // the product and the residual sum are rounded separately (the header's contract; what the numpy reference does)
@@ -29,8 +29,7 @@ static_assert(THREADS == 256, "the grid arithmetic assumes 256-thread workgroups
 static_assert(TNN_DROPOUT_VEC == 16, "wide accesses are global_load / store_dwordx4");
 static_assert(TNN_RNG_ROUNDS == 10 && TNN_RNG_DRAW_BITS == 24 && TNN_RNG_STATE_BYTES == 16, "Philox4x32-10, 24-bit draws");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
+using namespace tnn;      // f32x4, f64x2, aligned, aligned16, with_float, with_flag (tnn_pack.h)
 
 constexpr uint32_t kMul0 = 0xD2511F53u, kMul1 = 0xCD9E8D57u, kKey0 = 0x9E3779B9u, kKey1 = 0xBB67AE85u;
 
@@ -150,13 +149,11 @@ __global__ __launch_bounds__(THREADS) void dropout_kernel(DropArgs a) {
     }
 }
 
-inline bool aligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; }
-
 template <typename T, int MODE>
 void launch_typed(const DropArgs& a, unsigned grid, bool wide) {
-    hipStream_t s = tnn::stream();
-    if (wide) hipLaunchKernelGGL((dropout_kernel<T, MODE, true>), dim3(grid), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((dropout_kernel<T, MODE, false>), dim3(grid), dim3(THREADS), 0, s, a);
+    with_flag(wide, [&](auto w) {
+        hipLaunchKernelGGL((dropout_kernel<T, MODE, decltype(w)::value>), dim3(grid), dim3(THREADS), 0, tnn::stream(), a);
+    });
 }
 
 // the data launch over n > 0 elements; mode as dropout_kernel's MODE
@@ -169,26 +166,22 @@ void launch_data(int mode, const void* ticket, const void* x, const void* residu
     a.blocks = ((first + n - 1) >> 2) - (first >> 2) + 1;
     a.threshold = (uint32_t)threshold;
     a.scale = scale;
-    const bool wide = (first & 3) == 0 && aligned(y, TNN_DROPOUT_VEC) && (mode == 2 || aligned(x, TNN_DROPOUT_VEC)) &&
-                      (mode != 1 || aligned(residual, TNN_DROPOUT_VEC));
+    const bool wide = (first & 3) == 0 && aligned16(y) && (mode == 2 || aligned16(x)) && (mode != 1 || aligned16(residual));
     int64_t groups = (a.blocks + THREADS - 1) / THREADS;
     if (groups > TNN_DROPOUT_MAX_BLOCKS) groups = TNN_DROPOUT_MAX_BLOCKS;
     const unsigned grid = (unsigned)groups;
-    if (dtype == TNN_F32) {
-        if (mode == 0) launch_typed<float, 0>(a, grid, wide);
-        else if (mode == 1) launch_typed<float, 1>(a, grid, wide);
-        else launch_typed<float, 2>(a, grid, wide);
-    } else {
-        if (mode == 0) launch_typed<double, 0>(a, grid, wide);
-        else if (mode == 1) launch_typed<double, 1>(a, grid, wide);
-        else launch_typed<double, 2>(a, grid, wide);
-    }
+    with_float(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        if (mode == 0) launch_typed<T, 0>(a, grid, wide);
+        else if (mode == 1) launch_typed<T, 1>(a, grid, wide);
+        else launch_typed<T, 2>(a, grid, wide);
+    });
 }
 
 }  // namespace
 
 #define TNN_DROPOUT_RANGE(name)                                                                                          \
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, name ": dtype %d (float32 and float64 only)", dtype);              \
+    TNN_REQUIRE_FLOAT(name);                                                                                             \
     TNN_REQUIRE(first >= 0 && n >= 0 && first <= INT64_MAX - n, name ": first %lld, n %lld (both >= 0, first + n <= 2^63 - 1)", \
                 (long long)first, (long long)n)
 

@@ -23,22 +23,17 @@
 
 #include <math.h>
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_norm.h"
 
 namespace {
+
+using namespace tnn;      // Pack, Math, aligned16, item_of, with_float (tnn_pack.h)
 
 constexpr int THREADS = 64 * TNN_NORM_ROWS_PER_BLOCK;
 static_assert(THREADS == 256, "the kernels assume workgroups of four waves");
 static_assert(TNN_NORM_WAVE_MAX_N == 64 * 16 && TNN_NORM_BLOCK_MAX_N == THREADS * 16, "16 elements per thread at either limit");
 static_assert(TNN_NORM_VEC == 16, "wide accesses are global_load / store_dwordx4");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-template <typename T> struct Wide;
-template <> struct Wide<float> { typedef f32x4 type; };
-template <> struct Wide<double> { typedef f64x2 type; };
 
 struct NormArgs {
     const void *x, *dy, *gamma, *beta, *mean_in, *rstd_in;
@@ -53,7 +48,7 @@ template <typename T, int GROUP, int EPL, bool VECTOR>
 struct Row {
     static constexpr int V = TNN_NORM_VEC / (int)sizeof(T);
     static_assert(EPL % V == 0, "whole wide accesses per thread");
-    typedef typename Wide<T>::type W;
+    typedef typename Pack<T, true>::type W;
 
     static __device__ __forceinline__ int col(int e, int t) {
         return VECTOR ? (e / V * GROUP + t) * V + e % V : e * GROUP + t;
@@ -122,10 +117,6 @@ __device__ __forceinline__ void group_sum2(T& a, T& b, T* slots, int& phase) {
     }
 }
 
-template <typename T> __device__ __forceinline__ T rsqrt_exact(T v);
-template <> __device__ __forceinline__ float rsqrt_exact<float>(float v) { return 1.0f / sqrtf(v); }
-template <> __device__ __forceinline__ double rsqrt_exact<double>(double v) { return 1.0 / sqrt(v); }
-
 template <typename T, int GROUP, int EPL, bool VECTOR>
 __global__ __launch_bounds__(THREADS) void norm_fwd_kernel(NormArgs a) {
     typedef Row<T, GROUP, EPL, VECTOR> R;
@@ -157,7 +148,7 @@ __global__ __launch_bounds__(THREADS) void norm_fwd_kernel(NormArgs a) {
             q += d * d;
         }
         group_sum2<T, GROUP>(q, unused, slots, phase);
-        const T rstd = rsqrt_exact<T>(q / count + eps);
+        const T rstd = Math<T>::rsqrt_(q / count + eps);
 #pragma unroll
         for (int e = 0; e < EPL; ++e) x[e] = x[e] * rstd * gam[e] + bet[e];
         R::store(static_cast<T*>(a.y) + row * n, n, t, x);
@@ -267,18 +258,6 @@ __global__ __launch_bounds__(256) void norm_partials_kernel(PartialJobs j) {
 }
 
 // ------------------------------------------------------------------------------------------------ GELU
-template <typename T> struct Math;
-template <> struct Math<float> {
-    static __device__ __forceinline__ float erf_(float v) { return erff(v); }
-    static __device__ __forceinline__ float tanh_(float v) { return tanhf(v); }
-    static __device__ __forceinline__ float exp_(float v) { return expf(v); }
-};
-template <> struct Math<double> {
-    static __device__ __forceinline__ double erf_(double v) { return erf(v); }
-    static __device__ __forceinline__ double tanh_(double v) { return tanh(v); }
-    static __device__ __forceinline__ double exp_(double v) { return exp(v); }
-};
-
 constexpr double kSqrtHalf = 0.70710678118654752440;        // 1 / sqrt(2)
 constexpr double kSqrt2OverPi = 0.79788456080286535588;     // sqrt(2 / pi)
 constexpr double kInvSqrt2Pi = 0.39894228040143267794;      // 1 / sqrt(2 pi)
@@ -312,7 +291,7 @@ __device__ __forceinline__ T gelu_slope(T x) {
 template <typename T, bool APPROX, bool BWD>
 __global__ __launch_bounds__(256) void gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out,
                                                    int64_t n, int64_t n_wide) {
-    typedef typename Wide<T>::type W;
+    typedef typename Pack<T, true>::type W;
     constexpr int V = TNN_NORM_VEC / (int)sizeof(T);
     const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = first; i < n_wide; i += stride) {
@@ -335,8 +314,6 @@ __global__ __launch_bounds__(256) void gelu_kernel(const T* __restrict__ x, cons
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (TNN_NORM_VEC - 1)) == 0; }
-
 inline int rows_per_block(int64_t N) { return N <= TNN_NORM_WAVE_MAX_N ? TNN_NORM_ROWS_PER_BLOCK : 1; }
 
 inline int64_t blocks_for(int64_t M, int64_t N, int64_t cap) {
@@ -361,15 +338,6 @@ void launch_norm(const NormArgs& a, unsigned grid) {
     }
 }
 
-template <bool BWD>
-void launch_norm(const NormArgs& a, unsigned grid, int dtype, bool vec) {
-    if (dtype == TNN_F32) {
-        if (vec) launch_norm<float, true, BWD>(a, grid); else launch_norm<float, false, BWD>(a, grid);
-    } else {
-        if (vec) launch_norm<double, true, BWD>(a, grid); else launch_norm<double, false, BWD>(a, grid);
-    }
-}
-
 template <typename T, bool BWD>
 void launch_gelu(const void* x, const void* dy, void* out, int64_t n, int approx) {
     const bool vec = aligned16(x) && aligned16(out) && (!BWD || aligned16(dy));
@@ -385,7 +353,7 @@ void launch_gelu(const void* x, const void* dy, void* out, int64_t n, int approx
 }  // namespace
 
 #define TNN_NORM_COMMON(name)                                                                                       \
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, name ": dtype %d (float32 and float64 only)", dtype);         \
+    TNN_REQUIRE_FLOAT(name);                                                                                        \
     TNN_REQUIRE(kind == TNN_NORM_LAYER || kind == TNN_NORM_RMS, name ": kind %d", kind);                            \
     TNN_REQUIRE(M >= 0 && N >= 1 && N <= TNN_NORM_BLOCK_MAX_N, name ": M %lld, N %lld (1 <= N <= %d)", (long long)M, \
                 (long long)N, TNN_NORM_BLOCK_MAX_N)
@@ -401,19 +369,20 @@ extern "C" int tnn_norm_fwd(const void* x, const void* gamma, const void* beta, 
     NormArgs a = {};
     a.x = x; a.gamma = gamma; a.beta = beta; a.y = y; a.mean = mean; a.rstd = rstd;
     a.M = M; a.N = (int)N; a.kind = kind; a.eps = eps;
-    const int64_t per = TNN_NORM_VEC / (dtype == TNN_F32 ? 4 : 8);
+    const int64_t per = TNN_NORM_VEC / item_of(dtype);
     const bool vec = N % per == 0 && aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta);
-    launch_norm<false>(a, (unsigned)blocks_for(M, N, (int64_t)tnn::num_cus() * 8), dtype, vec);
+    const unsigned grid = (unsigned)blocks_for(M, N, (int64_t)tnn::num_cus() * 8);
+    with_float(dtype, vec, [&](auto t, auto v) { launch_norm<decltype(t), decltype(v)::value, false>(a, grid); });
     TNN_LAUNCH_OK();
     return 0;
 }
 
 extern "C" int tnn_norm_bwd_workspace(int64_t M, int64_t N, int with_dgamma, int with_dbeta, int dtype, int64_t* bytes) {
     TNN_REQUIRE(bytes != nullptr, "tnn_norm_bwd_workspace: null result pointer");
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, "tnn_norm_bwd_workspace: dtype %d (float32 and float64 only)", dtype);
+    TNN_REQUIRE_FLOAT("tnn_norm_bwd_workspace");
     TNN_REQUIRE(M >= 0 && N >= 1 && N <= TNN_NORM_BLOCK_MAX_N, "tnn_norm_bwd_workspace: M %lld, N %lld", (long long)M, (long long)N);
     const int arrays = (with_dgamma ? 1 : 0) + (with_dbeta ? 1 : 0);
-    *bytes = M == 0 ? 0 : arrays * blocks_for(M, N, TNN_NORM_MAX_PARTIALS) * N * (dtype == TNN_F32 ? 4 : 8);
+    *bytes = M == 0 ? 0 : arrays * blocks_for(M, N, TNN_NORM_MAX_PARTIALS) * N * item_of(dtype);
     return 0;
 }
 
@@ -424,7 +393,7 @@ extern "C" int tnn_norm_bwd(const void* x, const void* dy, const void* gamma, co
     TNN_NORM_COMMON("tnn_norm_bwd");
     TNN_REQUIRE(kind == TNN_NORM_LAYER || dbeta == nullptr, "tnn_norm_bwd: RMS norm has no beta gradient");
     if (!dx && !dgamma && !dbeta) return 0;
-    const size_t item = dtype == TNN_F32 ? 4 : 8;
+    const size_t item = (size_t)item_of(dtype);
     hipStream_t s = tnn::stream();
     if (M == 0) {                                                // no rows: the parameter gradients are zero
         if (dgamma) TNN_CHECK_HIP(hipMemsetAsync(dgamma, 0, (size_t)N * item, s));
@@ -442,15 +411,13 @@ extern "C" int tnn_norm_bwd(const void* x, const void* dy, const void* gamma, co
     if (params) {
         int64_t need = 0;
         if (int rc = tnn_norm_bwd_workspace(M, N, dgamma != nullptr, dbeta != nullptr, dtype, &need)) return rc;
-        TNN_REQUIRE(workspace != nullptr && workspace_bytes >= need && aligned16(workspace),
-                    "tnn_norm_bwd: workspace of %lld bytes, %lld needed (16-byte aligned)", (long long)workspace_bytes,
-                    (long long)need);
+        TNN_REQUIRE_WORKSPACE("tnn_norm_bwd", workspace, workspace_bytes, need);
         char* base = static_cast<char*>(workspace);
         if (dgamma) { a.part_gamma = base; base += blocks * N * item; }
         if (dbeta) a.part_beta = base;
         vec = vec && (blocks * N * item) % TNN_NORM_VEC == 0;
     }
-    launch_norm<true>(a, (unsigned)blocks, dtype, vec);
+    with_float(dtype, vec, [&](auto t, auto v) { launch_norm<decltype(t), decltype(v)::value, true>(a, (unsigned)blocks); });
     TNN_LAUNCH_OK();
     if (params) {
         PartialJobs j = {};
@@ -459,8 +426,7 @@ extern "C" int tnn_norm_bwd(const void* x, const void* dy, const void* gamma, co
         if (dbeta) { j.part[jobs] = a.part_beta; j.out[jobs] = dbeta; ++jobs; }
         j.P = (int)blocks; j.N = (int)N;
         const dim3 grid((unsigned)((N + 15) / 16), (unsigned)jobs);
-        if (dtype == TNN_F32) hipLaunchKernelGGL(norm_partials_kernel<float>, grid, dim3(256), 0, s, j);
-        else hipLaunchKernelGGL(norm_partials_kernel<double>, grid, dim3(256), 0, s, j);
+        with_float(dtype, [&](auto t) { hipLaunchKernelGGL(norm_partials_kernel<decltype(t)>, grid, dim3(256), 0, s, j); });
         TNN_LAUNCH_OK();
     }
     return 0;
@@ -468,24 +434,22 @@ extern "C" int tnn_norm_bwd(const void* x, const void* dy, const void* gamma, co
 
 extern "C" int tnn_gelu_fwd(const void* x, void* y, int64_t n, int approx, int dtype) {
     TNN_NEED_INIT();
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, "tnn_gelu_fwd: dtype %d (float32 and float64 only)", dtype);
+    TNN_REQUIRE_FLOAT("tnn_gelu_fwd");
     TNN_REQUIRE(n >= 0 && (approx == 0 || approx == 1), "tnn_gelu_fwd: n %lld, approx %d", (long long)n, approx);
     if (n == 0) return 0;
     TNN_REQUIRE(x && y, "tnn_gelu_fwd: null operand");
-    if (dtype == TNN_F32) launch_gelu<float, false>(x, nullptr, y, n, approx);
-    else launch_gelu<double, false>(x, nullptr, y, n, approx);
+    with_float(dtype, [&](auto t) { launch_gelu<decltype(t), false>(x, nullptr, y, n, approx); });
     TNN_LAUNCH_OK();
     return 0;
 }
 
 extern "C" int tnn_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, int approx, int dtype) {
     TNN_NEED_INIT();
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, "tnn_gelu_bwd: dtype %d (float32 and float64 only)", dtype);
+    TNN_REQUIRE_FLOAT("tnn_gelu_bwd");
     TNN_REQUIRE(n >= 0 && (approx == 0 || approx == 1), "tnn_gelu_bwd: n %lld, approx %d", (long long)n, approx);
     if (n == 0) return 0;
     TNN_REQUIRE(x && dy && dx, "tnn_gelu_bwd: null operand");
-    if (dtype == TNN_F32) launch_gelu<float, true>(x, dy, dx, n, approx);
-    else launch_gelu<double, true>(x, dy, dx, n, approx);
+    with_float(dtype, [&](auto t) { launch_gelu<decltype(t), true>(x, dy, dx, n, approx); });
     TNN_LAUNCH_OK();
     return 0;
 }

@@ -22,10 +22,12 @@
 
 #include <math.h>
 
-#include "tnn_internal.h"
+#include "tnn_pack.h"
 #include "tnn_token.h"
 
 namespace {
+
+using namespace tnn;      // Pack, Math, aligned16, item_of, round16, with_float (tnn_pack.h)
 
 constexpr int THREADS = 256;
 constexpr int K = TNN_EMBED_SEGMENT;
@@ -37,24 +39,7 @@ static_assert(TNN_TOKEN_VEC == 16, "wide accesses are global_load / store_dwordx
 static_assert(K <= THREADS, "a segment is staged by one pass of the workgroup");
 constexpr int BATCH = 8;      // rows in flight per thread in the segmented sum and in the sums of partial rows
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-template <typename T, bool VECTOR> struct Pack { typedef T type; static constexpr int N = 1; };
-template <> struct Pack<float, true> { typedef f32x4 type; static constexpr int N = 4; };
-template <> struct Pack<double, true> { typedef f64x2 type; static constexpr int N = 2; };
-
 template <typename P> __device__ __forceinline__ P zero_pack() { return P(0); }
-
-template <typename T> struct Math;
-template <> struct Math<float> {
-    static __device__ __forceinline__ float exp_(float v) { return expf(v); }
-    static __device__ __forceinline__ float log_(float v) { return logf(v); }
-};
-template <> struct Math<double> {
-    static __device__ __forceinline__ double exp_(double v) { return exp(v); }
-    static __device__ __forceinline__ double log_(double v) { return log(v); }
-};
 
 // ------------------------------------------------------------------------------------------------ embedding forward
 template <typename T, bool VECTOR>
@@ -449,10 +434,6 @@ __global__ __launch_bounds__(THREADS) void xent_bwd_kernel(XentArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (TNN_TOKEN_VEC - 1)) == 0; }
-inline int64_t round16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-inline int64_t item_of(int dtype) { return dtype == TNN_F32 ? 4 : 8; }
-
 struct EmbedSpace {
     int64_t counts, offsets, sorted, partial, bytes, segments;
 };
@@ -468,22 +449,6 @@ inline EmbedSpace embed_space(int64_t M, int64_t V, int64_t E, int dtype) {
     return w;
 }
 
-// the four (T, VECTOR) instances of a kernel template
-#define TNN_TOKEN_DISPATCH(kernel, dtype, vec, grid, block, ...)                                                       \
-    do {                                                                                                               \
-        hipStream_t s__ = tnn::stream();                                                                               \
-        if ((dtype) == TNN_F32) {                                                                                      \
-            if (vec) hipLaunchKernelGGL((kernel<float, true>), grid, block, 0, s__, __VA_ARGS__);                      \
-            else hipLaunchKernelGGL((kernel<float, false>), grid, block, 0, s__, __VA_ARGS__);                         \
-        } else {                                                                                                       \
-            if (vec) hipLaunchKernelGGL((kernel<double, true>), grid, block, 0, s__, __VA_ARGS__);                     \
-            else hipLaunchKernelGGL((kernel<double, false>), grid, block, 0, s__, __VA_ARGS__);                        \
-        }                                                                                                              \
-    } while (0)
-
-template <typename T>
-inline const T* as(const void* p) { return static_cast<const T*>(p); }
-
 template <typename T, bool VECTOR>
 void launch_wave(const XentArgs& a, unsigned grid) {
     hipStream_t s = tnn::stream();
@@ -493,13 +458,10 @@ void launch_wave(const XentArgs& a, unsigned grid) {
 
 }  // namespace
 
-#define TNN_TOKEN_DTYPE(name) \
-    TNN_REQUIRE(dtype == TNN_F32 || dtype == TNN_F64, name ": dtype %d (float32 and float64 only)", dtype)
-
 extern "C" int tnn_embed_fwd(const void* table, const void* ids, const void* pos, void* out, int64_t M, int64_t V, int64_t E,
                              int64_t T, int dtype) {
     TNN_NEED_INIT();
-    TNN_TOKEN_DTYPE("tnn_embed_fwd");
+    TNN_REQUIRE_FLOAT("tnn_embed_fwd");
     TNN_REQUIRE(M >= 0 && V >= 1 && E >= 1 && (pos == nullptr || T >= 1), "tnn_embed_fwd: M %lld, V %lld, E %lld, T %lld",
                 (long long)M, (long long)V, (long long)E, (long long)T);
     if (M == 0) return 0;
@@ -507,24 +469,19 @@ extern "C" int tnn_embed_fwd(const void* table, const void* ids, const void* pos
     const int64_t per = TNN_TOKEN_VEC / item_of(dtype);
     const bool vec = E % per == 0 && aligned16(table) && aligned16(out) && aligned16(pos);
     const unsigned grid = tnn::stream_grid(M * (vec ? E / per : E));
-    if (dtype == TNN_F32) {
-        if (vec) hipLaunchKernelGGL((embed_fwd_kernel<float, true>), dim3(grid), dim3(THREADS), 0, tnn::stream(), as<float>(table),
-                                    as<int64_t>(ids), as<float>(pos), static_cast<float*>(out), M, V, E, T);
-        else hipLaunchKernelGGL((embed_fwd_kernel<float, false>), dim3(grid), dim3(THREADS), 0, tnn::stream(), as<float>(table),
-                                as<int64_t>(ids), as<float>(pos), static_cast<float*>(out), M, V, E, T);
-    } else {
-        if (vec) hipLaunchKernelGGL((embed_fwd_kernel<double, true>), dim3(grid), dim3(THREADS), 0, tnn::stream(), as<double>(table),
-                                    as<int64_t>(ids), as<double>(pos), static_cast<double*>(out), M, V, E, T);
-        else hipLaunchKernelGGL((embed_fwd_kernel<double, false>), dim3(grid), dim3(THREADS), 0, tnn::stream(), as<double>(table),
-                                as<int64_t>(ids), as<double>(pos), static_cast<double*>(out), M, V, E, T);
-    }
+    with_float(dtype, vec, [&](auto t, auto v) {
+        typedef decltype(t) F;
+        hipLaunchKernelGGL((embed_fwd_kernel<F, decltype(v)::value>), dim3(grid), dim3(THREADS), 0, tnn::stream(),
+                           static_cast<const F*>(table), static_cast<const int64_t*>(ids), static_cast<const F*>(pos),
+                           static_cast<F*>(out), M, V, E, T);
+    });
     TNN_LAUNCH_OK();
     return 0;
 }
 
 extern "C" int tnn_embed_bwd_workspace(int64_t M, int64_t V, int64_t E, int dtype, int64_t* bytes) {
     TNN_REQUIRE(bytes != nullptr, "tnn_embed_bwd_workspace: null result pointer");
-    TNN_TOKEN_DTYPE("tnn_embed_bwd_workspace");
+    TNN_REQUIRE_FLOAT("tnn_embed_bwd_workspace");
     TNN_REQUIRE(M >= 0 && M < (1ll << 31) && V >= 1 && V < (1ll << 31) && E >= 1,
                 "tnn_embed_bwd_workspace: M %lld, V %lld, E %lld (M, V < 2^31)", (long long)M, (long long)V, (long long)E);
     *bytes = M == 0 ? 0 : embed_space(M, V, E, dtype).bytes;
@@ -554,20 +511,19 @@ static int embed_bwd_typed(const void* dy, const void* ids, void* dtable, void* 
         const dim3 seg_grid((unsigned)w.segments, (unsigned)((cols + THREADS - 1) / THREADS));
         const unsigned comb_grid = tnn::stream_grid(V * cols);
         T* dt = static_cast<T*>(dtable);
-        if (vec) {
-            hipLaunchKernelGGL((embed_segment_kernel<T, true>), seg_grid, dim3(THREADS), 0, s, g, idp, offsets, sorted, dt, partial, M, V, E);
-            hipLaunchKernelGGL((embed_combine_kernel<T, true>), dim3(comb_grid), dim3(THREADS), 0, s, offsets, partial, dt, V, E);
-        } else {
-            hipLaunchKernelGGL((embed_segment_kernel<T, false>), seg_grid, dim3(THREADS), 0, s, g, idp, offsets, sorted, dt, partial, M, V, E);
-            hipLaunchKernelGGL((embed_combine_kernel<T, false>), dim3(comb_grid), dim3(THREADS), 0, s, offsets, partial, dt, V, E);
-        }
+        with_flag(vec, [&](auto v) {
+            constexpr bool VECTOR = decltype(v)::value;
+            hipLaunchKernelGGL((embed_segment_kernel<T, VECTOR>), seg_grid, dim3(THREADS), 0, s, g, idp, offsets, sorted, dt, partial, M, V, E);
+            hipLaunchKernelGGL((embed_combine_kernel<T, VECTOR>), dim3(comb_grid), dim3(THREADS), 0, s, offsets, partial, dt, V, E);
+        });
         TNN_LAUNCH_OK();
     }
     if (dpos != nullptr) {
         const bool vec = E % per == 0 && aligned16(dy) && aligned16(dpos);
         const unsigned grid = tnn::stream_grid(Tlen * (vec ? E / per : E));
-        if (vec) hipLaunchKernelGGL((embed_dpos_kernel<T, true>), dim3(grid), dim3(THREADS), 0, s, g, static_cast<T*>(dpos), M, E, Tlen);
-        else hipLaunchKernelGGL((embed_dpos_kernel<T, false>), dim3(grid), dim3(THREADS), 0, s, g, static_cast<T*>(dpos), M, E, Tlen);
+        with_flag(vec, [&](auto v) {
+            hipLaunchKernelGGL((embed_dpos_kernel<T, decltype(v)::value>), dim3(grid), dim3(THREADS), 0, s, g, static_cast<T*>(dpos), M, E, Tlen);
+        });
         TNN_LAUNCH_OK();
     }
     return 0;
@@ -576,7 +532,7 @@ static int embed_bwd_typed(const void* dy, const void* ids, void* dtable, void* 
 extern "C" int tnn_embed_bwd(const void* dy, const void* ids, void* dtable, void* dpos, void* workspace, int64_t workspace_bytes,
                              int64_t M, int64_t V, int64_t E, int64_t T, int64_t padding_idx, int dtype) {
     TNN_NEED_INIT();
-    TNN_TOKEN_DTYPE("tnn_embed_bwd");
+    TNN_REQUIRE_FLOAT("tnn_embed_bwd");
     TNN_REQUIRE(M >= 0 && M < (1ll << 31) && V >= 1 && V < (1ll << 31) && E >= 1 && (dpos == nullptr || T >= 1),
                 "tnn_embed_bwd: M %lld, V %lld, E %lld, T %lld (M, V < 2^31)", (long long)M, (long long)V, (long long)E, (long long)T);
     if (!dtable && !dpos) return 0;
@@ -589,17 +545,15 @@ extern "C" int tnn_embed_bwd(const void* dy, const void* ids, void* dtable, void
     TNN_REQUIRE(dy && (ids || !dtable), "tnn_embed_bwd: null operand");
     if (dtable) {
         const int64_t need = embed_space(M, V, E, dtype).bytes;
-        TNN_REQUIRE(workspace != nullptr && workspace_bytes >= need && aligned16(workspace),
-                    "tnn_embed_bwd: workspace of %lld bytes, %lld needed (16-byte aligned)", (long long)workspace_bytes, (long long)need);
+        TNN_REQUIRE_WORKSPACE("tnn_embed_bwd", workspace, workspace_bytes, need);
     }
     char* ws = static_cast<char*>(workspace);
-    return dtype == TNN_F32 ? embed_bwd_typed<float>(dy, ids, dtable, dpos, ws, M, V, E, T, padding_idx, dtype)
-                            : embed_bwd_typed<double>(dy, ids, dtable, dpos, ws, M, V, E, T, padding_idx, dtype);
+    return with_float(dtype, [&](auto t) { return embed_bwd_typed<decltype(t)>(dy, ids, dtable, dpos, ws, M, V, E, T, padding_idx, dtype); });
 }
 
 #define TNN_XENT_COMMON(name)                                                                                          \
     TNN_NEED_INIT();                                                                                                   \
-    TNN_TOKEN_DTYPE(name);                                                                                             \
+    TNN_REQUIRE_FLOAT(name);                                                                                           \
     TNN_REQUIRE(M >= 0 && V >= 1, name ": M %lld, V %lld", (long long)M, (long long)V);                                \
     TNN_REQUIRE(reduction == TNN_XENT_MEAN || reduction == TNN_XENT_SUM, name ": reduction %d", reduction)
 
@@ -619,16 +573,16 @@ extern "C" int tnn_xent_fwd(const void* logits, const void* targets, void* losse
         if (V <= TNN_XENT_WAVE_MAX_V) {
             const int64_t blocks = (M + TNN_XENT_ROWS_PER_BLOCK - 1) / TNN_XENT_ROWS_PER_BLOCK;
             const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
-            if (dtype == TNN_F32) { if (vec) launch_wave<float, true>(a, grid); else launch_wave<float, false>(a, grid); }
-            else { if (vec) launch_wave<double, true>(a, grid); else launch_wave<double, false>(a, grid); }
+            with_float(dtype, vec, [&](auto t, auto v) { launch_wave<decltype(t), decltype(v)::value>(a, grid); });
         } else {
             const dim3 grid((unsigned)(M < cap ? M : cap));
-            TNN_TOKEN_DISPATCH(xent_block_kernel, dtype, vec, grid, dim3(THREADS), a);
+            with_float(dtype, vec, [&](auto t, auto v) {
+                hipLaunchKernelGGL((xent_block_kernel<decltype(t), decltype(v)::value>), grid, dim3(THREADS), 0, s, a);
+            });
         }
         TNN_LAUNCH_OK();
     }
-    if (dtype == TNN_F32) hipLaunchKernelGGL(xent_reduce_kernel<float>, dim3(1), dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL(xent_reduce_kernel<double>, dim3(1), dim3(THREADS), 0, s, a);
+    with_float(dtype, [&](auto t) { hipLaunchKernelGGL(xent_reduce_kernel<decltype(t)>, dim3(1), dim3(THREADS), 0, s, a); });
     TNN_LAUNCH_OK();
     return 0;
 }
@@ -644,7 +598,9 @@ extern "C" int tnn_xent_bwd(const void* logits, const void* targets, const void*
     const int64_t per = TNN_TOKEN_VEC / item_of(dtype);
     const bool vec = V % per == 0 && aligned16(logits) && aligned16(dlogits);
     const dim3 grid(tnn::stream_grid(M * (vec ? V / per : V)));
-    TNN_TOKEN_DISPATCH(xent_bwd_kernel, dtype, vec, grid, dim3(THREADS), a);
+    with_float(dtype, vec, [&](auto t, auto v) {
+        hipLaunchKernelGGL((xent_bwd_kernel<decltype(t), decltype(v)::value>), grid, dim3(THREADS), 0, tnn::stream(), a);
+    });
     TNN_LAUNCH_OK();
     return 0;
 }
