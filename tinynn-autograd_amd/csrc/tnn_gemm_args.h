@@ -1,0 +1,118 @@
+// What every fp32 GEMM kernel of tnn_gemm.hip shares: the vector types, the argument block GemmArgs with its epilogue codes,
+// the epilogue itself in its two forms, the tile-order helpers and the step-stamp buffer of the trace build.  First of the
+// fragments tnn_gemm.hip includes INSIDE its anonymous namespace (the kernels have internal linkage); expects tnn_internal.h.
+#pragma once
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+enum { EPI_AXPBY = 0, EPI_BIAS_ACT = 1, EPI_MASK = 2, EPI_ADAM = 3 };
+
+struct GemmArgs {
+    const float* A;
+    const float* B;
+    float* C;
+    int64_t M, N, K, lda, ldb, ldc;
+    float alpha, beta;
+    int epi;
+    const float* bias;
+    int act, relu_sign;
+    const float* Y;
+    int64_t ldy;
+    int vecA, vecB;        // 16-B vector loads legal for this operand
+    int64_t k_per_split;   // multiple of BK
+    int splits;
+    float* ws;             // [splits, M, N] partial sums when splits > 1
+    int tiles_m, tiles_n;
+    // small/latency kernel: XCD-aware tile order.  Workgroup b runs on XCD b % 8 and each XCD has a private L2; with
+    // xg_m x xg_n == 8 the tile grid is cut into 8 rectangles of (tiles_m / xg_m) x (tiles_n / xg_n) tiles, one per XCD,
+    // so an L2 fills only the operand rows / columns of its rectangle.  0 = plain order.
+    int xg_m, xg_n;
+    // small/latency kernel only (tnn_dense_fwd_head_partials): the NEXT (classifier) layer's weights head_w [N, head_c]
+    // and where this tile's share of that layer's logits goes, head_z [tiles_n][M][head_c]
+    const float* head_w;
+    float* head_z;
+    int head_c;
+    // small/latency kernel, FAST form only (tnn_dense_fwd_head_partials_stats with exchange = 2): a launch sequence that ONE
+    // thread of the launch advances — the tag of the deferred statistics exchange in the head launch behind it (tnn_p2p.h: XchgCtx)
+    unsigned int* bump;
+    // EPI_ADAM (tiled kernel, tnn_gemm_tn_adam): the product is a weight gradient that Adam consumes in the epilogue;
+    // C (may be NULL) receives the gradient itself
+    float *ad_p, *ad_m, *ad_v;
+    float ad_lr, ad_b1, ad_b2, ad_eps;
+    const double* ad_pows;
+    const int* ad_guard;
+    int staged_c;          // tiled kernel: interior tiles store through an LDS image of the tile (row-major 16-B stores)
+    int group_m;           // tiled kernel: M-tiles per raster group (8; 1 = an M panel per XCD range, tiles_m = N-major sweep)
+    // tiled TN kernel with EPI_ADAM (tnn_gemm_tn_adam_bias): the workgroups of tile row 0 also produce the column sums of B
+    // (= the bias gradient, core/ops.py:52-54) in their epilogue -> cs_db [N], and apply Adam to the bias block
+    // cs_p / cs_m / cs_v [N] when those are given
+    float *cs_db, *cs_p, *cs_m, *cs_v;
+#ifdef TNN_GEMM_TRACE
+    unsigned long long* trace;   // debug build only: [grid][8] timeline words (nullptr = off)
+#endif
+};
+
+__device__ __forceinline__ float apply_epilogue(const GemmArgs& g, float acc, int64_t row,
+                                                int64_t col) {
+    if (g.epi == EPI_AXPBY) {
+        float r = g.alpha * acc;
+        if (g.beta != 0.f) r += g.beta * g.C[row * g.ldc + col];
+        return r;
+    } else if (g.epi == EPI_BIAS_ACT) {
+        float v = acc + (g.bias ? g.bias[col] : 0.f);
+        if (g.act == TNN_ACT_RELU) {
+            if (g.relu_sign) v = v < 0.f ? -0.0f : fabsf(v);   // mask x>=0 kept in the sign bit
+            else v = v < 0.f ? 0.f : v;
+        }
+        return v;
+    } else {
+        float y = g.Y[row * g.ldy + col];
+        return (__float_as_uint(y) >> 31) ? 0.f : acc;
+    }
+}
+
+// bijective XCD remap (blocks b, b+8, b+16 ... share an XCD and therefore an L2): give every XCD a
+// contiguous range of tile ids so neighbouring tiles (same B panel, adjacent A panels) hit in L2.
+__device__ __forceinline__ int xcd_remap(int b, int nb) {
+    const int nx = 8;
+    if (nb < 2 * nx) return b;
+    int q = nb / nx, r = nb % nx;
+    int xcd = b % nx, local = b / nx;
+    int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    return base + local;
+}
+
+// the same epilogue with its operand (bias value / mask source / old C) already in a register
+__device__ __forceinline__ float finish_epilogue(const GemmArgs& g, float acc, float pre) {
+    if (g.epi == EPI_AXPBY) {
+        float r = g.alpha * acc;
+        if (g.beta != 0.f) r += g.beta * pre;
+        return r;
+    } else if (g.epi == EPI_BIAS_ACT) {
+        float v = acc + pre;
+        if (g.act == TNN_ACT_RELU) {
+            if (g.relu_sign) v = v < 0.f ? -0.0f : fabsf(v);
+            else v = v < 0.f ? 0.f : v;
+        }
+        return v;
+    } else {
+        return (__float_as_uint(pre) >> 31) ? 0.f : acc;
+    }
+}
+
+// tile of workgroup `block` of the latency kernels: one rectangle of the tile grid per XCD (pick_xcd_cut) or column-major
+__device__ __forceinline__ void small_tile_coords(const GemmArgs& g, const int block, int& tm, int& tn) {
+    if (g.xg_m) {
+        const int xcd = block & 7, idx = block >> 3, pm = g.tiles_m / g.xg_m, pn = g.tiles_n / g.xg_n;
+        tm = (xcd % g.xg_m) * pm + idx % pm;
+        tn = (xcd / g.xg_m) * pn + idx / pm;
+    } else {
+        tm = block % g.tiles_m;
+        tn = block / g.tiles_m;
+    }
+}
+
+#ifdef TNN_STEP_TRACE
+__device__ unsigned long long g_step_trace[4 * 1024 * 4];        // tnn_internal.h: TNN_STEP_STAMP
+#endif

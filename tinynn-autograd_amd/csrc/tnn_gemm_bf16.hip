@@ -133,7 +133,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16_nt_kernel(BfArgs g) {
         read_frag(0, 1);
     }
     constexpr int NMF = MI * NI;
-    // the barrier with the MFMAs of chunks 2-3 tied behind it (see tnn_gemm.hip: hipcc otherwise hoists them above
+    // the barrier with the MFMAs of chunks 2-3 tied behind it (see tnn_gemm_tiled.h: hipcc otherwise hoists them above
     // the barrier and the post-barrier fragment reads have nothing to hide behind)
     auto pinned_barrier = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(256) void mse_prep_bf16_kernel(const bf16_t* __rest
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // Two-level arrival: the tiles draw tickets in groups of G >= 32 (word 1 + group), the last of a group draws one of the
         // launch (word 0) — a thousand agent-scope atomics on ONE word serialise to ~25 us (measured on the data-parallel
-        // step's counters, csrc/tnn_gemm.hip), 32 + 32 do not.  Every word is back at 0 when the launch ends (graph replays).
+        // step's counters, csrc/tnn_gemm_step.h), 32 + 32 do not.  Every word is back at 0 when the launch ends (graph replays).
         const int G = max(32, (n_loss + 62) / 63), n_groups = (n_loss + G - 1) / G, grp = b / G;
         const unsigned members = (unsigned)min(G, n_loss - grp * G);
         int last = 0;

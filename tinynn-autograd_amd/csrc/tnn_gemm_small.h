@@ -1,0 +1,465 @@
+// The 16 x 16 latency tile in its three forms (small_tile, small_tile_fast, the 16 x 32 dw_tile_wide), what they read their
+// TN operands through (TnFrag, tn_batches) and the plain product's kernel.  Included by tnn_gemm.hip inside its anonymous
+// namespace, after tnn_gemm_args.h and tnn_gemm_adam.h; expects tnn_p2p.h (store_sys).
+#pragma once
+
+// ------------------------------------------------------------------------------ small / latency GEMM
+// MNIST-size layers (2MNK <= ~160 MFLOP) are latency-bound: the 64x64 LDS-tiled kernel needs split-K
+// plus a second launch and still leaves most CUs idle.  Here one workgroup owns ONE 16x16 output tile
+// (v_mfma_f32_16x16x4_f32, 4 accumulator VGPRs) and its WAVES waves split K between them in 16-deep
+// chunks (round-robin, so neighbouring waves touch neighbouring lines); fragments are loaded straight
+// from global memory in MFMA layout (everything is L2-resident at this size, an LDS round trip would
+// only add latency), the WAVES partial tiles are summed through LDS and the epilogue is applied once.
+// Optionally the workgroups of the first tile row also emit colsum[n] = sum_k B[k][n] — the bias
+// gradient (core/ops.py:52-54) — from the B fragments they already hold (B = dZ in dW = X^T dZ).
+//   lane l: i = l & 15 (row of A / column of B), grp = l >> 4 holds k = 16c + 4 grp + j, j = 0..3
+
+// One operand of a weight-gradient tile in TN form ([K][ld], the tile's own index contiguous), read through buffer loads:
+// lane (i16, grp) owns k = 4 grp + row for the `row`s it is asked for (16 c + j) and the column `col`.  A k >= K, or a lane
+// whose column is outside the matrix (ok == false), gets the offset 0xffffffff and the hardware returns 0 — no exec-mask
+// branch around the load and nothing read outside the operand.  32-bit offsets: tn_extents_ok() at the dispatch site.
+struct TnFrag {
+    __amdgpu_buffer_rsrc_t rsrc;
+    uint32_t K, ld4, lane, k0;
+    bool ok;
+    __device__ __forceinline__ TnFrag(const float* p, int64_t K_, int64_t ld, int64_t extent, int grp, int64_t col, bool ok_)
+        : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (uint32_t)((K_ - 1) * ld + extent) * 4u, 0x00020000)),
+          K((uint32_t)K_), ld4((uint32_t)ld * 4u), lane((uint32_t)grp * 4u * (uint32_t)ld * 4u + (uint32_t)col * 4u),
+          k0((uint32_t)grp * 4u), ok(ok_) {}
+    __device__ __forceinline__ float load(const uint32_t row, const uint32_t byte_off) const {
+        uint32_t off = (ok & (row + k0 < K)) ? lane + row * ld4 + byte_off : 0xffffffffu;
+        asm("" : "+v"(off));      // opaque: left visible, the select is turned into a branch over two loads
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+    }
+};
+
+// The K walk of those tiles: wave `wid` (wave-uniform) owns chunks wid, wid + WAVES, ... and takes them TN_MAXC at a time:
+// load(u, c) requests chunk c into fragment slot u, for every chunk of the batch, before mma(u) — the MFMAs and column-sum
+// adds of slot u — runs for the first of them.  A chunk that does not exist is skipped in both phases (wave-uniform branches).
+// Four chunks of a 16 x 32 tile are 48 fragment registers.  SINGLE: nchunks <= WAVES * TN_MAXC is the caller's contract.
+constexpr int TN_MAXC = 4;
+template <int WAVES, bool SINGLE, class L, class S, class M>
+__device__ __forceinline__ void tn_batches(const int wid, const int nchunks, L&& load, S&& loads_out, M&& mma) {
+    for (int c0 = wid; c0 < nchunks; c0 += WAVES * TN_MAXC) {
+        const int live = (nchunks - c0 + WAVES - 1) / WAVES;
+#pragma unroll
+        for (int u = 0; u < TN_MAXC; ++u)
+            if (u < live) load(u, c0 + u * WAVES);
+        __builtin_amdgcn_sched_barrier(0);                // no MFMA (and its wait) moves up between the loads
+        loads_out(c0 == wid);
+#pragma unroll
+        for (int u = 0; u < TN_MAXC; ++u)
+            if (u < live) mma(u);
+        if constexpr (SINGLE) break;
+    }
+}
+
+// TO_LDS: the finished tile goes to out_lds [16][16] (row-major; entries outside the matrix are not written) and the column
+// sums of the first tile row to out_lds[256 .. 272) instead of memory — for a caller that sends them elsewhere itself
+template <bool AKC, bool BKC, int WAVES, bool ADAM = false, bool TO_LDS = false>
+__device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict__ colsum, int block,
+                                           float (*red)[4][64], float (*bsum)[64], const AdamEpi* ad = nullptr,
+                                           float* out_lds = nullptr) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int i16 = lane & 15, grp = lane >> 4;
+    int tm, tn;
+    if (g.xg_m) {                                    // XCD-aware tile order (GemmArgs::xg_m)
+        const int xcd = block & 7, idx = block >> 3, pm = g.tiles_m / g.xg_m, pn = g.tiles_n / g.xg_n;
+        tm = (xcd % g.xg_m) * pm + idx % pm;
+        tn = (xcd / g.xg_m) * pn + idx / pm;
+    } else {
+        tm = block % g.tiles_m;
+        tn = block / g.tiles_m;
+    }
+    const int64_t m0 = (int64_t)tm * 16, n0 = (int64_t)tn * 16;
+    const int64_t am = m0 + i16, bn = n0 + i16;
+    const bool a_ok = am < g.M, b_ok = bn < g.N;
+    const int nchunks = (int)((g.K + 15) / 16);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float bs = 0.f;
+    float a_p = 0.f, a_m = 0.f, a_v = 0.f, ab_p = 0.f, ab_m = 0.f, ab_v = 0.f, ic1 = 0.f, ic2 = 0.f;
+    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);
+    if constexpr (ADAM) {
+        ic1 = (float)(1.0 / (1.0 - ad->pows[0]));
+        ic2 = (float)(1.0 / (1.0 - ad->pows[1]));
+        if (tid < 256) {
+            const int64_t row = m0 + ((tid & 63) >> 4) * 4 + (tid >> 6), col = n0 + (tid & 15);
+            if (row < g.M && col < g.N) {
+                const int64_t i = row * g.ldc + col;
+                a_p = ad->pw[i]; a_m = ad->mw[i]; a_v = ad->vw[i];
+            }
+        }
+        if (tm == 0 && tid < 16 && n0 + tid < g.N) {
+            ab_p = ad->pb[n0 + tid]; ab_m = ad->mb[n0 + tid]; ab_v = ad->vb[n0 + tid];
+        }
+    }
+    if constexpr (ADAM) {
+        // the first layer's weight gradient (TN form): all of a wave's chunks requested before its first MFMA, as in dw_tile_wide
+        static_assert(!AKC && !BKC, "the Adam epilogue belongs to dW = X^T dZ");
+        const TnFrag fa(g.A, g.K, g.lda, g.M, grp, am, a_ok), fb(g.B, g.K, g.ldb, g.N, grp, bn, b_ok);
+        const int swid = __builtin_amdgcn_readfirstlane(wid);
+        float a[TN_MAXC][4], b[TN_MAXC][4];
+        tn_batches<WAVES, false>(
+            swid, nchunks,
+            [&](const int u, const int c) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    a[u][j] = fa.load((uint32_t)c * 16u + (uint32_t)j, 0u);
+                    b[u][j] = fb.load((uint32_t)c * 16u + (uint32_t)j, 0u);
+                }
+            },
+            [&](const bool first) { if (first) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); },   // (first batch's operands + the Adam state)
+            [&](const int u) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
+                bs += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
+            });
+    } else {
+        for (int c = wid; c < nchunks; c += WAVES) {
+            const int64_t k = (int64_t)c * 16 + grp * 4;
+            float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (AKC) {
+                const float* p = g.A + am * g.lda + k;
+                if (a_ok) {
+                    if (g.vecA && k + 3 < g.K) {
+                        float4 v = *reinterpret_cast<const float4*>(p);
+                        a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (k + j < g.K) a[j] = p[j];
+                    }
+                }
+            } else {
+                if (a_ok) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if (k + j < g.K) a[j] = g.A[(k + j) * g.lda + am];
+                }
+            }
+            if constexpr (BKC) {
+                const float* p = g.B + bn * g.ldb + k;
+                if (b_ok) {
+                    if (g.vecB && k + 3 < g.K) {
+                        float4 v = *reinterpret_cast<const float4*>(p);
+                        b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) if (k + j < g.K) b[j] = p[j];
+                    }
+                }
+            } else {
+                if (b_ok) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) if (k + j < g.K) b[j] = g.B[(k + j) * g.ldb + bn];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
+            bs += (b[0] + b[1]) + (b[2] + b[3]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc[r];
+    bsum[wid][lane] = bs;
+    __syncthreads();
+    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 2);
+    if (tid < 256) {
+        const int r = tid >> 6, ln = tid & 63;
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) s += red[w][r][ln];
+        const int64_t row = m0 + (ln >> 4) * 4 + r, col = n0 + (ln & 15);   // 16x16x4 C/D layout
+        if (row < g.M && col < g.N) {
+            const float gval = apply_epilogue(g, s, row, col);
+            if constexpr (TO_LDS) out_lds[((ln >> 4) * 4 + r) * 16 + (ln & 15)] = gval;
+            else if (!ADAM || g.C != nullptr) g.C[row * g.ldc + col] = gval;      // ADAM: the gradient itself only on request
+            if constexpr (ADAM) {
+                const int64_t i = row * g.ldc + col;
+                ad->pw[i] = adam_apply(*ad, ic1, ic2, gval, a_m, a_v, a_p);
+                ad->mw[i] = a_m;
+                ad->vw[i] = a_v;
+            }
+        }
+    }
+    if ((TO_LDS || colsum != nullptr) && tm == 0 && tid < 16 && n0 + tid < g.N) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) s += (bsum[w][tid] + bsum[w][16 + tid]) + (bsum[w][32 + tid] + bsum[w][48 + tid]);
+        if constexpr (TO_LDS) out_lds[256 + tid] = s;
+        else colsum[n0 + tid] = s;
+        if constexpr (ADAM) {
+            ad->pb[n0 + tid] = adam_apply(*ad, ic1, ic2, s, ab_m, ab_v, ab_p);
+            ad->mb[n0 + tid] = ab_m;
+            ad->vb[n0 + tid] = ab_v;
+        }
+    }
+    if constexpr (ADAM) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 3);
+}
+
+// The first layer's weight gradient on 16 x 32 tiles (round 6): dW0 = X^T dZ of the MNIST net is 49 x 16 = 784 tiles of 16 x 16 —
+// 3.06 per CU, and the 16 workgroups that are a CU's FOURTH end 1.3 us behind the rest (profiles/r06_stepA_stamps.txt: 4.16 against
+// 2.85 / 3.04 / 3.55 us for the first / second / third 256).  Two column tiles per workgroup — ONE A fragment, two B fragments, two
+// accumulators per wave — make it 392 equal workgroups, at most two per CU, with 12 instead of 16 operand loads per 512 outputs.
+// TN form only (A [K][lda] and B [K][ldb], both MN-contiguous), EPI_AXPBY with beta = 0 (a gradient), N a multiple of 32.
+//   lane (i16, grp): a[j] = A[16 c + 4 grp + j][m0 + i16], b0 / b1[j] = B[.][n0 + i16] / B[.][n0 + 16 + i16]
+//   acc0 / acc1[r] = C[m0 + 4 grp + r][n0 + i16] / [.. + 16]   (16x16x4 C/D layout)
+// ADAM / TO_LDS as in small_tile; out_lds: [16][32] row-major, then the 32 column sums.
+template <int WAVES, bool ADAM, bool TO_LDS>
+__device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restrict__ colsum, const int block, float (*red)[8][64],
+                                             float (*bsum)[2][64], const AdamEpi* ad = nullptr, float* out_lds = nullptr) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int i16 = lane & 15, grp = lane >> 4;
+    int tm, tn;
+    small_tile_coords(g, block, tm, tn);                     // g.tiles_n counts 32-column tiles here
+    const int64_t m0 = (int64_t)tm * 16, n0 = (int64_t)tn * 32;
+    const int64_t am = m0 + i16, bn = n0 + i16;
+    const bool a_ok = am < g.M;
+    const int nchunks = (int)((g.K + 15) / 16);
+    // this thread's two outputs of the epilogue (threads < 256): rows m0 + 4 (ln >> 4) + r, columns n0 + (ln & 15) and + 16
+    const int e_r = tid >> 6, e_ln = tid & 63;
+    const int64_t e_row = m0 + (e_ln >> 4) * 4 + e_r, e_col = n0 + (e_ln & 15);
+    const bool e_live = tid < 256 && e_row < g.M;
+    float a_p[2] = {0.f, 0.f}, a_m[2] = {0.f, 0.f}, a_v[2] = {0.f, 0.f}, ab_p = 0.f, ab_m = 0.f, ab_v = 0.f, ic1 = 0.f, ic2 = 0.f;
+    if constexpr (ADAM) {
+        ic1 = (float)(1.0 / (1.0 - ad->pows[0]));
+        ic2 = (float)(1.0 / (1.0 - ad->pows[1]));
+        if (e_live) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int64_t i = e_row * g.ldc + e_col + 16 * u;
+                a_p[u] = ad->pw[i]; a_m[u] = ad->mw[i]; a_v[u] = ad->vw[i];
+            }
+        }
+        if (tm == 0 && tid < 32) { ab_p = ad->pb[n0 + tid]; ab_m = ad->mb[n0 + tid]; ab_v = ad->vb[n0 + tid]; }
+    }
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    float bs0 = 0.f, bs1 = 0.f;
+    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);
+    // K loop: a wave requests the fragments of ALL its chunks (batches of up to TN_MAXC) before its first MFMA — one load round
+    // trip per batch instead of one per chunk.  Buffer loads: a row k >= K (or a row of A past M) gets the offset 0xffffffff
+    // and reads 0, no exec-mask branch; chunks that do not exist cost neither loads nor MFMAs (tn_batches).  Chunk order, the
+    // two accumulator chains and the column-sum adds are those of the chunk-per-trip loop this replaces: the same bits.
+    const TnFrag fa(g.A, g.K, g.lda, g.M, grp, am, a_ok), fb(g.B, g.K, g.ldb, g.N, grp, bn, true);
+    const int swid = __builtin_amdgcn_readfirstlane(wid);
+    float a[TN_MAXC][4], b0[TN_MAXC][4], b1[TN_MAXC][4];
+    tn_batches<WAVES, true>(                              // at most 16 chunks on 4 waves (dispatch sites): one batch
+        swid, nchunks,
+        [&](const int u, const int c) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t row = (uint32_t)c * 16u + (uint32_t)j;         // + 4 grp: this lane's k
+                a[u][j] = fa.load(row, 0u);
+                b0[u][j] = fb.load(row, 0u);
+                b1[u][j] = fb.load(row, 64u);
+            }
+        },
+        [&](const bool first) { if constexpr (ADAM) { if (first) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); } },
+        [&](const int u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b0[u][j], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b1[u][j], acc1, 0, 0, 0);
+            }
+            bs0 += (b0[u][0] + b0[u][1]) + (b0[u][2] + b0[u][3]);
+            bs1 += (b1[u][0] + b1[u][1]) + (b1[u][2] + b1[u][3]);
+        });
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { red[wid][r][lane] = acc0[r]; red[wid][4 + r][lane] = acc1[r]; }
+    bsum[wid][0][lane] = bs0;
+    bsum[wid][1][lane] = bs1;
+    __syncthreads();
+    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 2);
+    if (e_live) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            float sres = 0.f;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) sres += red[w][4 * u + e_r][e_ln];
+            const float gval = g.alpha * sres;
+            const int64_t i = e_row * g.ldc + e_col + 16 * u;
+            if constexpr (TO_LDS) out_lds[(int)(e_row - m0) * 32 + (int)(e_col - n0) + 16 * u] = gval;
+            else if (!ADAM || g.C != nullptr) g.C[i] = gval;      // ADAM: the gradient itself only on request
+            if constexpr (ADAM) {
+                ad->pw[i] = adam_apply(*ad, ic1, ic2, gval, a_m[u], a_v[u], a_p[u]);
+                ad->mw[i] = a_m[u];
+                ad->vw[i] = a_v[u];
+            }
+        }
+    }
+    if ((TO_LDS || colsum != nullptr) && tm == 0 && tid < 32) {
+        const int u = tid >> 4, t = tid & 15;
+        float sres = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) sres += (bsum[w][u][t] + bsum[w][u][16 + t]) + (bsum[w][u][32 + t] + bsum[w][u][48 + t]);
+        if constexpr (TO_LDS) out_lds[512 + tid] = sres;
+        else colsum[n0 + tid] = sres;
+        if constexpr (ADAM) {
+            ad->pb[n0 + tid] = adam_apply(*ad, ic1, ic2, sres, ab_m, ab_v, ab_p);
+            ad->mb[n0 + tid] = ab_m;
+            ad->vb[n0 + tid] = ab_v;
+        }
+    }
+    if constexpr (ADAM) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 3);
+}
+
+// FAST variant of small_tile for aligned operands (vecA && vecB, every extent below 4 GiB) — same tile, same lane
+// layout, same reduction, but nothing on the path from launch to the first MFMA except the loads themselves:
+//   * fragments come through buffer loads (SGPR resource + 32-bit offset): an out-of-range row / column / k gets the
+//     offset 0xffffffff and the hardware returns 0 — no exec-mask branches, no 64-bit pointer arithmetic;
+//   * a wave issues the loads of ALL its K-chunks (up to MAXC = 4 per batch) before the first MFMA; one chunk per
+//     loop trip made every trip a dependent L2/HBM round trip (fwd0 of the MNIST net: 4 trips per wave);
+//   * the epilogue's operand (bias / ReLU-mask source / old C) is requested up front by the threads that apply it,
+//     instead of after the cross-wave reduction.
+// SYS_HEADZ: the partial logits leave through write-through (system-scope) stores, because a workgroup of THIS launch
+// on another XCD reads them back (dense_fwd_head_kernel)
+template <bool AKC, bool BKC, int WAVES, bool SYS_HEADZ = false>
+__device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __restrict__ colsum, int block,
+                                                float (*red)[4][64], float (*bsum)[64], float* head_lds = nullptr) {
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+    constexpr uint32_t OOB = 0xffffffffu;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int i16 = lane & 15, grp = lane >> 4;
+    int tm, tn;
+    small_tile_coords(g, block, tm, tn);
+    const int64_t m0 = (int64_t)tm * 16, n0 = (int64_t)tn * 16;
+    const int64_t am = m0 + i16, bn = n0 + i16;
+    const bool a_ok = am < g.M, b_ok = bn < g.N;
+    const int nchunks = (int)((g.K + 15) / 16);
+    const uint32_t K = (uint32_t)g.K, lda4 = (uint32_t)g.lda * 4u, ldb4 = (uint32_t)g.ldb * 4u;
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(g.A), 0, (uint32_t)(((AKC ? g.M : g.K) - 1) * g.lda + (AKC ? g.K : g.M)) * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(g.B), 0, (uint32_t)(((BKC ? g.N : g.K) - 1) * g.ldb + (BKC ? g.K : g.N)) * 4u, 0x00020000);
+    // byte offset of this lane's first element of chunk 0 (k = grp * 4), without the chunk term
+    const uint32_t a_lane = AKC ? (uint32_t)am * lda4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * lda4 + (uint32_t)am * 4u;
+    const uint32_t b_lane = BKC ? (uint32_t)bn * ldb4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * ldb4 + (uint32_t)bn * 4u;
+    const uint32_t a_chunk = AKC ? 64u : 16u * lda4;          // bytes per 16-deep chunk
+    const uint32_t b_chunk = BKC ? 64u : 16u * ldb4;
+
+    const int e_r = tid >> 6, e_ln = tid & 63;
+    const int64_t e_row = m0 + (e_ln >> 4) * 4 + e_r, e_col = n0 + (e_ln & 15);   // 16x16x4 C/D layout
+    const bool e_live = tid < 256 && e_row < g.M && e_col < g.N;
+    float e_pre = 0.f;
+    if (e_live) {
+        if (g.epi == EPI_BIAS_ACT) e_pre = g.bias ? g.bias[e_col] : 0.f;
+        else if (g.epi == EPI_MASK) e_pre = g.Y[e_row * g.ldy + e_col];
+        else if (g.beta != 0.f) e_pre = g.C[e_row * g.ldc + e_col];
+    }
+    float head_pre[4] = {0.f, 0.f, 0.f, 0.f};                 // wave 0: head_w[n0 + 4 grp + j][i16], the B fragment of the partial-logit product
+    if (g.head_z != nullptr && wid == 0 && i16 < g.head_c) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (n0 + 4 * grp + j < g.N) head_pre[j] = g.head_w[(n0 + 4 * grp + j) * g.head_c + i16];
+    }
+
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float bs = 0.f;
+    constexpr int MAXC = 4;
+    constexpr int KID = WAVES == 16 ? 0 : 1;              // (trace build: fwd0 runs 16 waves, fwd1 4 — or 8 in the data-parallel tail form)
+    TNN_STEP_STAMP(g_step_trace, KID, 0);
+    for (int c0 = wid; c0 < nchunks; c0 += WAVES * MAXC) {
+        float a[MAXC][4], b[MAXC][4];
+#pragma unroll
+        for (int u = 0; u < MAXC; ++u) {
+            const uint32_t c = (uint32_t)(c0 + u * WAVES);
+            const uint32_t k = c * 16u + (uint32_t)grp * 4u;
+            if ((int)c >= nchunks) {                                  // wave-uniform: no loads for chunks that do not exist
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { a[u][j] = 0.f; b[u][j] = 0.f; }
+                continue;
+            }
+            if constexpr (AKC) {
+                const uint32_t off = (a_ok && k < K) ? a_lane + c * a_chunk : OOB;     // K % 4 == 0: all in or all out
+                const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[u][j] = __uint_as_float(v[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t off = (a_ok && k + j < K) ? a_lane + c * a_chunk + (uint32_t)j * lda4 : OOB;
+                    a[u][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(a_rsrc, off, 0, 0));
+                }
+            }
+            if constexpr (BKC) {
+                const uint32_t off = (b_ok && k < K) ? b_lane + c * b_chunk : OOB;
+                const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, off, 0, 0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[u][j] = __uint_as_float(v[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t off = (b_ok && k + j < K) ? b_lane + c * b_chunk + (uint32_t)j * ldb4 : OOB;
+                    b[u][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b_rsrc, off, 0, 0));
+                }
+            }
+        }
+        if (c0 == wid) TNN_STEP_STAMP_ACKED(g_step_trace, KID, 1);
+#pragma unroll
+        for (int u = 0; u < MAXC; ++u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
+            bs += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc[r];
+    bsum[wid][lane] = bs;
+    __syncthreads();
+    TNN_STEP_STAMP(g_step_trace, KID, 2);
+    float e_val = 0.f;
+    if (tid < 256) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) s += red[w][e_r][e_ln];
+        if (e_live) {
+            e_val = finish_epilogue(g, s, e_pre);
+            g.C[e_row * g.ldc + e_col] = e_val;
+        }
+    }
+    if (colsum != nullptr && tm == 0 && tid < 16 && n0 + tid < g.N) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) s += (bsum[w][tid] + bsum[w][16 + tid]) + (bsum[w][32 + tid] + bsum[w][48 + tid]);
+        colsum[n0 + tid] = s;
+    }
+    if (head_lds != nullptr && g.head_z != nullptr) {
+        // This tile's share of the NEXT layer's logits: head_z[tn][row][c] = sum over the tile's 16 columns of
+        // out[row][col] * head_w[n0 + col][c] (a sign-encoded ReLU zero, -0.0, contributes -0 * w = 0).  The classifier
+        // head then only ADDS tiles_n partials per logit instead of re-reading the whole activation and redoing the
+        // product in every workgroup (csrc/tnn_head.hip).  The finished 16 x 16 tile goes through LDS once and wave 0
+        // multiplies it with head_w's 16 rows (fragments requested at kernel start) in four 16x16x4 MFMAs.
+        float* tile_s = head_lds;                               // [16][20]: 16-B aligned rows, conflict-free 16-B reads
+        if (tid < 256) tile_s[((e_ln >> 4) * 4 + e_r) * 20 + (e_ln & 15)] = e_val;
+        __syncthreads();
+        if (wid == 0) {
+            const f32x4 a4 = *reinterpret_cast<const f32x4*>(tile_s + i16 * 20 + 4 * grp);     // out[row i16][col 4 grp + j]
+            f32x4 hacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hacc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], head_pre[j], hacc, 0, 0, 0);
+            if (i16 < g.head_c) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int64_t row = m0 + 4 * grp + q;
+                    if (row < g.M) {
+                        float* dst = g.head_z + ((int64_t)tn * g.M + row) * g.head_c + i16;
+                        if constexpr (SYS_HEADZ) tnn::p2p::store_sys(reinterpret_cast<uint32_t*>(dst), __float_as_uint(hacc[q]));
+                        else *dst = hacc[q];
+                    }
+                }
+            }
+        }
+    }
+    TNN_STEP_STAMP_ACKED(g_step_trace, KID, 3);
+}
+
+template <bool AKC, bool BKC, int WAVES, bool FAST>
+__global__ __launch_bounds__(WAVES * 64) void gemm_small_f32_kernel(GemmArgs g, float* __restrict__ colsum) {
+    __shared__ float red[WAVES][4][64];
+    __shared__ float bsum[WAVES][64];
+    if constexpr (FAST) {
+        __shared__ __attribute__((aligned(16))) float head_lds[16 * 20];   // tnn_dense_fwd_head_partials: the finished tile
+        if (g.bump != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *g.bump += 1u;     // single writer; read by the NEXT launch
+        small_tile_fast<AKC, BKC, WAVES>(g, colsum, (int)blockIdx.x, red, bsum, head_lds);
+    } else {
+        small_tile<AKC, BKC, WAVES>(g, colsum, (int)blockIdx.x, red, bsum);
+    }
+}

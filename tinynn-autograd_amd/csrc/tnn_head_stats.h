@@ -1,5 +1,5 @@
 // Whole-batch softmax statistics of a classifier head (core/losses.py:24-32) shared by the head kernels (tnn_head.hip)
-// and by the forward launch in front of them (tnn_gemm.hip: the LAST workgroup of the hidden layer's forward to finish
+// and by the forward launch in front of them (tnn_gemm_step.h: the LAST workgroup of the hidden layer's forward to finish
 // reduces the shard's {max, sum-exp} — and on the xGMI peer-to-peer transport exchanges and merges them — so a
 // data-parallel step needs neither a statistics launch nor workgroups that wait for a peer inside the head launch).
 #pragma once

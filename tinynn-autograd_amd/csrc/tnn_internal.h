@@ -49,23 +49,45 @@ void set_update_guard(const int* device_word);
         }                                   \
     } while (0)
 
-// Debug build only (make trace: -DTNN_STEP_TRACE): 100 MHz wall-clock stamps of the headline step's four launches, one row of
-// four words per workgroup — [0] entry, [1] every operand of the product in registers (s_waitcnt vmcnt(0) behind the last
-// load), [2] last MFMA issued and the cross-wave reduction read back, [3] last store acknowledged.  Kernel ids: 0 fwd0, 1 fwd1
-// + partial logits, 2 head + hidden backward, 3 first-layer backward + Adam.  tools/probes/step_stamps.py reads them.
+// The one stamp hook of the debug builds (make trace): thread 0 of a workgroup stores the 100 MHz wall clock into word `slot`
+// of row `row` (`stride` words per row) of `buf`, if the row is below `limit` — a limit of 0 switches the site off.  _ACKED
+// first waits for the workgroup's outstanding loads and stores (s_waitcnt vmcnt(0)).  Each build switches its own sites on
+// through the names below; in the product build every site is an empty statement and names nothing.
+#define TNN_STAMP_STORE(buf, row, stride, limit, slot)                                                        \
+    do {                                                                                                      \
+        if (threadIdx.x == 0 && (row) < (limit)) (buf)[(row) * (stride) + (slot)] = wall_clock64();           \
+    } while (0)
+#define TNN_STAMP_STORE_ACKED(buf, row, stride, limit, slot)                                                  \
+    do {                                                                                                      \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                     \
+        TNN_STAMP_STORE(buf, row, stride, limit, slot);                                                       \
+    } while (0)
+#define TNN_STAMP_OFF(...) do { } while (0)
+// -DTNN_STEP_TRACE: the headline step's four launches, one row of four words per workgroup — [0] entry, [1] every operand of
+// the product in registers (s_waitcnt vmcnt(0) behind the last load), [2] last MFMA issued and the cross-wave reduction read
+// back, [3] last store acknowledged.  Kernel ids (blocks of 1024 rows): 0 fwd0, 1 fwd1 + partial logits, 2 head + hidden
+// backward, 3 first-layer backward + Adam.  tools/probes/step_stamps.py reads them.
 #ifdef TNN_STEP_TRACE
-#define TNN_STEP_STAMP(buf, kid, slot)                                                                              \
-    do {                                                                                                            \
-        if (threadIdx.x == 0 && blockIdx.x < 1024) (buf)[((kid) * 1024 + blockIdx.x) * 4 + (slot)] = wall_clock64(); \
-    } while (0)
-#define TNN_STEP_STAMP_ACKED(buf, kid, slot)                                                                        \
-    do {                                                                                                            \
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                           \
-        TNN_STEP_STAMP(buf, kid, slot);                                                                             \
-    } while (0)
+#define TNN_STEP_STAMP(buf, kid, slot) TNN_STAMP_STORE(buf, blockIdx.x, 4, 1024, (kid) * 1024 * 4 + (slot))
+#define TNN_STEP_STAMP_ACKED(buf, kid, slot) TNN_STAMP_STORE_ACKED(buf, blockIdx.x, 4, 1024, (kid) * 1024 * 4 + (slot))
 #else
-#define TNN_STEP_STAMP(buf, kid, slot) do { } while (0)
-#define TNN_STEP_STAMP_ACKED(buf, kid, slot) do { } while (0)
+#define TNN_STEP_STAMP TNN_STAMP_OFF
+#define TNN_STEP_STAMP_ACKED TNN_STAMP_OFF
+#endif
+// -DTNN_AR_TRACE: the data-parallel step's fused launches (g_fh_trace, g_ar_trace in tnn_gemm_step.h, SkipRanges::trace in
+// tnn_p2p.h; tools/probes/ar_fused_trace.py)
+#ifdef TNN_AR_TRACE
+#define TNN_AR_STAMP TNN_STAMP_STORE
+#else
+#define TNN_AR_STAMP TNN_STAMP_OFF
+#endif
+// -DTNN_GEMM_TRACE: the LDS-tiled kernel's per-workgroup timeline (GemmArgs::trace, tools/gemm_block_timeline.py)
+#ifdef TNN_GEMM_TRACE
+#define TNN_GEMM_STAMP TNN_STAMP_STORE
+#define TNN_GEMM_STAMP_ACKED TNN_STAMP_STORE_ACKED
+#else
+#define TNN_GEMM_STAMP TNN_STAMP_OFF
+#define TNN_GEMM_STAMP_ACKED TNN_STAMP_OFF
 #endif
 
 #define TNN_NEED_INIT() TNN_REQUIRE(tnn::initialised(), "tnn_init() has not been called")

@@ -309,12 +309,14 @@ __device__ __forceinline__ bool ll_poll(const char* const (&src)[N], const bool 
 
 // What a thread of an all-reduce does with ITS elements of every slice, i_k = first + k stride (k = 0 .. while i_k < slice / 4):
 // stages (A), (B), (C) of p2p_allreduce_kernel (tnn_p2p.hip has the protocol).  Also the tail of kernels that PRODUCE part of
-// the buffer themselves and push it straight into the owners' recv slots (tnn_gemm.hip: dense_bwd0_allreduce_adam_kernel) —
+// the buffer themselves and push it straight into the owners' recv slots (tnn_gemm_step.h: dense_bwd0_allreduce_adam_kernel) —
 // `skip` names the element ranges of buf that stage (A) must leave to them.
 struct SkipRanges {
     int64_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;      // [lo, hi) element ranges of buf, multiples of 4
 #ifdef TNN_AR_TRACE
     unsigned long long* trace = nullptr;             // debug build: [4] wall-clock stamps of this workgroup (start, A, B, C)
+    // (a member that exists in one build only: its three stamps in allreduce_body keep their own #ifdef — moved onto
+    // TNN_AR_STAMP of tnn_internal.h, whose test order is the other way round, the trace build's assembly changes)
 #endif
     __device__ __forceinline__ bool has(int64_t e) const { return (e >= lo0 && e < hi0) || (e >= lo1 && e < hi1); }
 };

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-workgroup timeline of the LDS-tiled fp32 GEMM (config-C shapes) from the kernel's own timestamps.
 
-Needs the debug library:  make -C tinynn-autograd_amd/csrc trace   (libtnn_hip_trace.so: tnn_gemm.hip compiled with
+Needs the debug library:  make -C tinynn-autograd_amd/csrc trace   (libtnn_hip_trace.so: tnn_gemm.hip — the tiled kernel is tnn_gemm_tiled.h — compiled with
 -DTNN_GEMM_TRACE; thread 0 of every workgroup writes entry / K-loop start / K-loop end / stores-acknowledged times from
 the 100 MHz clock plus HW_ID and XCC_ID).  Prints, per shape: how the workgroups spread over the CUs, the time spent
 in prologue, K loop and epilogue, and one CU's sequence of workgroups — which is how the lock-step of equal-length
