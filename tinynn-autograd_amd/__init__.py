@@ -61,6 +61,7 @@ from . import fused
 from . import graph
 from .graph import capture
 from . import dropout
+from . import ostep
 from . import rng
 from .fused import MLPTrainer, trainer_from_net
 

@@ -63,6 +63,10 @@ from ._dropout_signatures import _DROPOUT_SIGNATURES          # noqa: E402  (inc
 
 DROPOUT_SYMBOLS = sorted(_DROPOUT_SIGNATURES)
 
+from ._ostep_signatures import _OSTEP_SIGNATURES              # noqa: E402  (include/tnn_ostep.h: libtnn_hip.so only)
+
+OSTEP_SYMBOLS = sorted(_OSTEP_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -126,6 +130,8 @@ class _Lib(object):
         # assignment and runs the composed attention over the live prefix; sampling reads the logits back
         # and the random generator and dropout (include/tnn_dropout.h): under the twin rng.Generator keeps its state in two
         # host integers and device_array draws the mask with the planner's numpy generator (dropout.py)
+        # and the device-resident optimizer step (include/tnn_ostep.h): under the twin core/optimizer.AdamW and
+        # Model.clip_grad_norm evaluate the same maths on DeviceArray arithmetic and read the norm back
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -133,7 +139,8 @@ class _Lib(object):
                                     (_NORM_SIGNATURES, "tnn_norm.h", "normalisation"),
                                     (_TOKEN_SIGNATURES, "tnn_token.h", "embedding / cross-entropy"),
                                     (_DECODE_SIGNATURES, "tnn_decode.h", "decode attention / sampling"),
-                                    (_DROPOUT_SIGNATURES, "tnn_dropout.h", "random generator / dropout")):
+                                    (_DROPOUT_SIGNATURES, "tnn_dropout.h", "random generator / dropout"),
+                                    (_OSTEP_SIGNATURES, "tnn_ostep.h", "optimizer step")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -151,6 +158,7 @@ class _Lib(object):
         self.has_token = hasattr(self.cdll, "tnn_embed_fwd")
         self.has_decode = hasattr(self.cdll, "tnn_decode_attn")
         self.has_dropout = hasattr(self.cdll, "tnn_dropout_fwd")
+        self.has_ostep = hasattr(self.cdll, "tnn_ostep_adamw")
 
     @staticmethod
     def _absent(name, what):

@@ -10,6 +10,9 @@
   * data parallelism: with a communicator the gradient arena is all-reduced (SUM — the 1/m of the loss is
     already global) between backward() and compute_step, i.e. between examples/mnist/run.py:82 and :83.
 
+`clip_grad_norm(max_norm)` clips the gradient arena in place by the global norm in front of any optimizer, on the device
+(include/tnn_ostep.h); `optimizer.AdamW` clips inside its own step instead, AFTER the all-reduce.
+
 `save`/`load` are working .npz counterparts of the reference's pickle pair, which cannot round-trip
 (core/model.py:18-35).
 """
@@ -48,6 +51,7 @@ class Model(object):
         self._grad_arena = None
         self._arena_tensors = None
         self._pending_first = None   # (x, dz, w, rows, n_in, n_out): the first Dense layer's backward, deferred to step()
+        self._clip_rec = self._clip_ws = None    # clip_grad_norm's device record and workspace (include/tnn_ostep.h)
 
     def forward(self, inputs):
         return self.net.forward(inputs)
@@ -129,6 +133,21 @@ class Model(object):
                 t._grad, t._grad_shared, t._grad_zero = gv, False, False
             off += n
         self._param_arena, self._grad_arena, self._arena_tensors = params, grads, tensors
+        if hasattr(self.optimizer, "bind_layout"):   # (AdamW: which arena ranges decay)
+            self.optimizer.bind_layout(self._layout_segments())
+
+    def _layout_segments(self):
+        """[(offset, count, layer_index, layer, name)] of every live parameter in arena (= flattening) order."""
+        layers = getattr(self.net, "layers", None)
+        segments, off = [], 0
+        for i, layer_params in enumerate(self.net.get_parameters()):
+            for name, p in layer_params.items():
+                if p is None:
+                    continue
+                n = int(p.values.size)
+                segments.append((off, n, i, layers[i] if layers is not None else None, name))
+                off += n
+        return segments
 
     def _first_dense_params(self, tensors):
         """(w, b) of the net's first layer when that is a Dense whose parameters head the arena, else ()."""
@@ -232,6 +251,8 @@ class Model(object):
                 t.values = t._values_home                # same post-state as `param += step`: grad dropped
             return
 
+        if hasattr(self.optimizer, "bind_layout") and not self.optimizer.has_layout():
+            self.optimizer.bind_layout(self._layout_segments())      # (no arena: AdamW still learns which parameters decay)
         steps = self.optimizer.compute_step(all_grads, params)
 
         flat = getattr(self.optimizer, "_last_flat_step", None)
@@ -244,6 +265,65 @@ class Model(object):
         for step, layer in zip(steps, params):
             for key in layer:
                 layer[key] += step[key]
+
+    # ------------------------------------------------------------------ gradient clipping
+    def clip_grad_norm(self, max_norm):
+        """Clip every parameter's gradient in place by the GLOBAL L2 norm, in front of any optimizer: g *= min(1, max_norm /
+        (norm + 1e-6)), the rule of torch's clip_grad_norm_.  Returns the norm before clipping as a device scalar (float64) of
+        its own: a later call does not overwrite it (a replay of a captured call refreshes the scalar that call returned).  A
+        non-finite norm leaves the gradients untouched.
+
+        With the gradient arena on libtnn_hip.so this is three launches and nothing is read back (include/tnn_ostep.h: partial
+        sums, norm + factor, scale), so it can be captured; otherwise the composed route adds the squares with DeviceArray
+        arithmetic and READS the norm back, which a graph capture cannot do.  Call it after backward() and — data parallel —
+        remember that step() all-reduces after this point: clip there with AdamW(max_norm=...), whose norm is the global one."""
+        from .. import ostep as _os
+        max_norm = float(max_norm)
+        if not max_norm >= 0.0:
+            raise ValueError("clip_grad_norm: max_norm must be >= 0, got %r" % (max_norm,))
+        if self.use_arena:
+            self._bind_arenas()
+        if self._pending_first is not None:          # like every other reader of those gradients: the deferred launch first
+            ts = self._arena_tensors
+            if ts is not None and (ts[0]._grad_home.pending or ts[1]._grad_home.pending):
+                self._run_pending_first()
+            else:
+                self._pending_first = None
+        tensors = self._live_params()
+        grads = [t.grad for t in tensors]            # (the property: lazily-zero and shared gradients become private buffers)
+        lib = _lib.get()
+        arena = self._grad_arena
+        if (arena is not None and lib.has_ostep and arena.size and self._arena_tensors is not None
+                and len(tensors) == len(self._arena_tensors) and all(g is not None for g in grads)):
+            for t in self._arena_tensors:            # a gradient assigned from outside is first copied home
+                if t._grad is not t._grad_home:
+                    t._grad_home[...] = t._grad
+                    t._grad, t._grad_shared, t._grad_zero = t._grad_home, False, False
+            if self._clip_rec is None or self._clip_ws.size < _os.grid(arena.size):
+                self._clip_rec = da.asarray(_os.initial_state(0.0), dtype=np.float64)
+                self._clip_ws = da.empty((_os.grid(arena.size),), np.float64)
+            rec, ws, n, code = self._clip_rec, self._clip_ws, arena.size, arena._code()
+            lib.ostep_sumsq(arena._ptr, n, ws._ptr, ws.nbytes, code)
+            lib.ostep_begin(rec._ptr, ws._ptr, n, max_norm, 1, 1.0, 1.0, _os.SCHED_CONST, 0.0, 0.0, 0, 0)
+            lib.ostep_scale(arena._ptr, n, rec._ptr, code)
+            # a copy (one device-to-device copy on the stream, capturable): the record is reused by the next call and by
+            # every replay of a captured one, and a norm the caller keeps must not change under them
+            return rec[_os.GNORM:_os.GNORM + 1].copy().reshape(())
+        if _lib.capturing:
+            raise RuntimeError("clip_grad_norm (composed route) reads the norm back to the host, which a graph capture cannot "
+                               "do; it needs the gradient arena and libtnn_hip.so")
+        total = 0.0
+        for g in grads:
+            if g is not None:
+                g64 = g.astype(np.float64)
+                total += float((g64 * g64).sum())    # the read-back
+        norm = float(np.sqrt(total))
+        coef = _os.clip_coef(norm, max_norm)
+        if np.isfinite(norm) and coef != 1.0:
+            for g in grads:
+                if g is not None:
+                    g *= float(g.dtype.type(coef))
+        return da.asarray(np.float64(norm), dtype=np.float64)
 
     def zero_grad(self):
         self._pending_first = None                   # (Tensor.zero_grad drops the pending marks of the two arena views)

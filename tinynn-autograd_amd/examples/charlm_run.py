@@ -11,6 +11,11 @@ the motif is printed.
 
 --dropout P: dropout with rate P on the embedding's output and on both residual branches of every block (the fused residual
 form of ops.dropout_), drawn from the device generator of rng.py, which --seed seeds; 0, the default, adds no launch.
+
+--adamw: core/optimizer.AdamW instead of Adam — decoupled weight decay (--weight_decay, biases and norm parameters exempt),
+clipping by the global gradient norm (--clip MAX_NORM, 0 = none) and a linear warm-up over --warmup steps followed by a cosine
+decay to zero at the last step, all resident on the device (include/tnn_ostep.h).  Without --adamw the run and its launch
+sequence are what they were.
 """
 
 import argparse
@@ -24,14 +29,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import tinynn_autograd_amd as tn                                                            # noqa: E402
-from tinynn_autograd_amd import rng                                                         # noqa: E402
+from tinynn_autograd_amd import ostep, rng                                                  # noqa: E402
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
 from tinynn_autograd_amd.generation import generate                                         # noqa: E402
 from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
 from tinynn_autograd_amd.core.losses import CrossEntropyLoss                                # noqa: E402
 from tinynn_autograd_amd.core.model import Model                                            # noqa: E402
 from tinynn_autograd_amd.core.nn import Net                                                 # noqa: E402
-from tinynn_autograd_amd.core.optimizer import Adam                                         # noqa: E402
+from tinynn_autograd_amd.core.optimizer import Adam, AdamW                                  # noqa: E402
 from tinynn_autograd_amd.core.tensor import Tensor                                          # noqa: E402
 
 
@@ -60,7 +65,16 @@ def build(args):
                TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     loss_layer = CrossEntropyLoss(fused=fused)
-    return Model(net=net, loss=loss_layer, optimizer=Adam(lr=args.lr)), loss_layer
+    return Model(net=net, loss=loss_layer, optimizer=make_optimizer(args)), loss_layer
+
+
+def make_optimizer(args):
+    if not getattr(args, "adamw", False):
+        return Adam(lr=args.lr)
+    steps = args.num_ep * (args.n_train // args.batch_size)                 # cosine to the last step of the run
+    schedule = ostep.Cosine(args.warmup, steps) if args.warmup > 0 else None
+    return AdamW(lr=args.lr, weight_decay=args.weight_decay, max_norm=args.clip if args.clip > 0 else None, schedule=schedule,
+                 fused=not args.composed)
 
 
 def main(args):
@@ -92,6 +106,10 @@ def main(args):
         accuracy = float(hit[:, args.period:].mean())         # the positions whose next token the context determines
         history.append((mean, accuracy))
         print("epoch %d: mean loss %.4f, accuracy on predictable positions %.4f, %.2f s" % (epoch, mean, accuracy, time.time() - t0))
+        if isinstance(model.optimizer, AdamW):
+            st = model.optimizer.state()                    # the optimizer's only read-back, once per epoch
+            print("         step %d, lr %.3e, last gradient norm %.4f (factor %.4f), %d steps skipped"
+                  % (st["t"], st["lr"], st["gnorm"], st["coef"], st["skipped"]))
     args.generation = None              # with --generate: (ids [rows, prompt + N], share of motif continuations)
     if args.generate <= 0:
         return history
@@ -126,6 +144,10 @@ def parse(argv=None):
     parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")
     parser.add_argument("--generate", default=0, type=int, help="continue the first test sequences greedily by N tokens")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
+    parser.add_argument("--adamw", action="store_true", help="AdamW on the device instead of Adam")
+    parser.add_argument("--weight_decay", default=0.01, type=float, help="--adamw: decoupled weight decay")
+    parser.add_argument("--clip", default=1.0, type=float, help="--adamw: clip the global gradient norm to this (0: none)")
+    parser.add_argument("--warmup", default=0, type=int, help="--adamw: warm-up steps, then cosine decay to the last step (0: constant lr)")
     return parser.parse_args(argv)
 
 
