@@ -46,7 +46,8 @@ TNN_API int tnn_decode_attn_workspace(int64_t B, int64_t H, int64_t splits, int6
  * and [B, H, Tmax, D] caches are used in place.  `strides` is a HOST array of six (batch, head, row) triples in the order q,
  * k_new, v_new, k_cache, v_cache, o; the row stride of the single-row operands (q, k_new, v_new, o) is ignored.
  *
- * `len` is a HOST integer: every sequence of the batch holds `len` cached rows (ragged batches are out of scope).
+ * `len` is a HOST integer: every sequence of the batch holds `len` cached rows (per-sequence lengths read from
+ * device memory: tnn_ragged_decode_attn, include/tnn_ragged.h).
  *   k_new / v_new given ([B, H, D] / [B, H, Dv]; BOTH or NEITHER): the new row is written into cache row `len` (len < Tmax)
  *     and the query attends over keys [0, len].  The workgroup that owns position `len` takes that key and value from k_new /
  *     v_new, not from the cache, and it alone writes the row: nothing is read after being written inside the launch.  k_new /

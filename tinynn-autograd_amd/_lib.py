@@ -67,6 +67,10 @@ from ._ostep_signatures import _OSTEP_SIGNATURES              # noqa: E402  (inc
 
 OSTEP_SYMBOLS = sorted(_OSTEP_SIGNATURES)
 
+from ._ragged_signatures import _RAGGED_SIGNATURES            # noqa: E402  (include/tnn_ragged.h: libtnn_hip.so only)
+
+RAGGED_SYMBOLS = sorted(_RAGGED_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -132,6 +136,8 @@ class _Lib(object):
         # host integers and device_array draws the mask with the planner's numpy generator (dropout.py)
         # and the device-resident optimizer step (include/tnn_ostep.h): under the twin core/optimizer.AdamW and
         # Model.clip_grad_norm evaluate the same maths on DeviceArray arithmetic and read the norm back
+        # and the ragged decoding step (include/tnn_ragged.h): under the twin device_array loops over the sequences with the
+        # host mirror of the lengths and advances the step's state in numpy (ragged.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -140,7 +146,8 @@ class _Lib(object):
                                     (_TOKEN_SIGNATURES, "tnn_token.h", "embedding / cross-entropy"),
                                     (_DECODE_SIGNATURES, "tnn_decode.h", "decode attention / sampling"),
                                     (_DROPOUT_SIGNATURES, "tnn_dropout.h", "random generator / dropout"),
-                                    (_OSTEP_SIGNATURES, "tnn_ostep.h", "optimizer step")):
+                                    (_OSTEP_SIGNATURES, "tnn_ostep.h", "optimizer step"),
+                                    (_RAGGED_SIGNATURES, "tnn_ragged.h", "ragged decoding step")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -159,6 +166,7 @@ class _Lib(object):
         self.has_decode = hasattr(self.cdll, "tnn_decode_attn")
         self.has_dropout = hasattr(self.cdll, "tnn_dropout_fwd")
         self.has_ostep = hasattr(self.cdll, "tnn_ostep_adamw")
+        self.has_ragged = hasattr(self.cdll, "tnn_ragged_decode_attn")
 
     @staticmethod
     def _absent(name, what):

@@ -239,7 +239,9 @@ class MultiHeadAttention(Layer):
     def forward(self, inputs, cache=None):
         """cache: a generation.LayerCache (inference).  Empty: the PREFILL — the ordinary causal path runs and its k and v
         [B, T, H, E / H] are slice-assigned into the cache; afterwards T must be 1: three projections of the one row,
-        ops.attention_decode_ with the append, the output projection.  None: today's path, bit for bit."""
+        ops.attention_decode_ with the append, the output projection.  A cache with `lens` set (a ragged batch) takes
+        ops.attention_decode_ragged_, which reads every sequence's length on the device; cache.length stays the host's upper
+        bound.  None: today's path, bit for bit."""
         if len(inputs.shape) != 3:
             raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
         b, t, e = (int(s) for s in inputs.shape)
@@ -258,7 +260,10 @@ class MultiHeadAttention(Layer):
         rows = ops.reshape(inputs, (b * t, e))
         if cache is not None and cache.length > 0:
             q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h, e // h)) for n in "qkv")
-            att = ops.attention_decode_(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
+            if getattr(cache, "lens", None) is not None:         # a ragged batch: the lengths are read on the device
+                att = ops.attention_decode_ragged_(q, cache.k, cache.v, cache.lens, k, v, layout="bthd", route=route)
+            else:
+                att = ops.attention_decode_(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
             cache.length += 1
         else:
             q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h, e // h)) for n in "qkv")
@@ -468,11 +473,26 @@ class Embedding(Layer):
         self.inputs = None
         self.is_init = True
 
-    def forward(self, inputs, offset=0):
+    def forward(self, inputs, offset=0, positions=None):
         """offset: the position of the first id (a decoding step embeds token `offset` alone): positions offset .. offset +
-        T - 1 are used, as the row slice of "pos"."""
+        T - 1 are used, as the row slice of "pos".
+        positions: a ragged.Lengths [B] (inference only; it excludes `offset`) — ids [B, 1], sequence b's id sits at position
+        positions[b], read on the device (ops.embedding_at_); max_len is checked against the host mirror before any launch."""
         if len(inputs.shape) != 2:
             raise ValueError("Embedding: the input must be integer ids [B, T], got shape %s" % (tuple(inputs.shape),))
+        if positions is not None:
+            if int(offset) != 0:
+                raise ValueError("Embedding: `positions` excludes `offset`")
+            if int(inputs.shape[1]) != 1 or tuple(positions.shape) != (int(inputs.shape[0]),):
+                raise ValueError("Embedding: `positions` takes ids [B, 1] and one position per sequence, got ids %s and "
+                                 "positions %s" % (tuple(inputs.shape), tuple(positions.shape)))
+            if self.max_len is not None and positions.host.size and not (0 <= int(positions.host.min())
+                                                                         and int(positions.host.max()) < int(self.max_len)):
+                raise ValueError("Embedding: positions %d .. %d lie outside max_len %d"
+                                 % (int(positions.host.min()), int(positions.host.max()), int(self.max_len)))
+            self.inputs = inputs
+            return ops.embedding_at_(self.params["tok"], inputs, positions, self.params.get("pos"),
+                                     route=None if self.fused else "composed")
         offset = int(offset)
         if offset < 0:
             raise ValueError("Embedding: offset must be >= 0, got %d" % offset)

@@ -827,10 +827,11 @@ def attention_decode_(q, k_cache, v_cache, length, k_new=None, v_new=None, scale
     The result is a LEAF tensor without a grad_fn — nothing here is differentiable, and the operands' graphs are not
     extended.  ONE tnn_decode_attn call, whose keys are split over enough workgroups to cover the machine (decoding.py);
     under the CPU test twin and with route="composed" (or device_array.DECODE_ROUTE) a slice assignment and the composed
-    attention.  Out of scope: ragged batches, grouped-query heads, chunked prefill, bf16 — unknown keyword arguments raise."""
+    attention.  A ragged batch — every sequence at its own length — takes attention_decode_ragged_.  Out of scope:
+    grouped-query heads, chunked prefill, bf16 — unknown keyword arguments raise."""
     if unknown:
-        raise TypeError("attention_decode_: unsupported arguments %s (ragged batches, grouped-query heads and bf16 are out "
-                        "of scope)" % sorted(unknown))
+        raise TypeError("attention_decode_: unsupported arguments %s (grouped-query heads and bf16 are out of scope; a ragged "
+                        "batch takes attention_decode_ragged_)" % sorted(unknown))
     out = da.attention_decode(q.values, _raw_values(k_cache), _raw_values(v_cache), length,
                               None if k_new is None else k_new.values, None if v_new is None else v_new.values, scale=scale,
                               layout=layout, route=route, splits=splits)
@@ -848,6 +849,35 @@ def sample_rows_(logits, u=None, temperature=1.0, top_k=None, route=None, **unkn
         raise TypeError("sample_rows_: unsupported arguments %s (top-p is out of scope)" % sorted(unknown))
     ids = da.sample_rows(logits.values, None if u is None else _raw_values(u), temperature=temperature, top_k=top_k, route=route)
     return logits.__class__(ids, False, [])
+
+
+def attention_decode_ragged_(q, k_cache, v_cache, lens, k_new, v_new, scale=None, layout="bthd", route=None, splits=None,
+                             **unknown):
+    """attention_decode_ with the append for a RAGGED batch, INFERENCE ONLY: sequence b writes its new row into cache row
+    lens[b] and attends over keys [0, lens[b]].  lens: a ragged.Lengths (device int64 [B] and its host mirror) or a dense int64
+    device array — it is read ON THE DEVICE, so the call's arguments do not change from step to step and a token step can be
+    captured into a graph.  ONE tnn_ragged_decode_attn call whose grid depends on the shapes alone (ragged.py); under the CPU
+    test twin and with route="composed" (or device_array.RAGGED_ROUTE) a loop over the sequences with the host lengths.
+    The result is a LEAF tensor without a grad_fn.  Out of scope: grouped-query heads, bf16 — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_decode_ragged_: unsupported arguments %s (grouped-query heads and bf16 are out of scope)"
+                        % sorted(unknown))
+    out = da.attention_decode_ragged(q.values, _raw_values(k_cache), _raw_values(v_cache), _raw_values(lens), k_new.values,
+                                     v_new.values, scale=scale, layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
+def embedding_at_(table, ids, positions, pos=None, route=None, **unknown):
+    """The embedding of a ragged decoding step, INFERENCE ONLY: out[..., :] = table[ids[...], :] + pos[positions[...], :] —
+    every id sits at its own position.  table [V, E] and pos [Tpos, E] (or None) are tensors; ids (a Tensor or a DeviceArray,
+    int64 on the device) and positions (likewise, or a ragged.Lengths) are read on the device and never on the host: an id
+    outside [0, V) gives a zero token row, a position outside [0, Tpos) a zero position row.  ONE tnn_ragged_embed_fwd launch;
+    composed route: two row gathers and an addition.  The result is a LEAF tensor without a grad_fn — unknown keyword
+    arguments raise."""
+    if unknown:
+        raise TypeError("embedding_at_: unsupported arguments %s" % sorted(unknown))
+    out = da.embedding_at(table.values, _raw_values(ids), _raw_values(positions), None if pos is None else pos.values, route=route)
+    return table.__class__(out, False, [])
 
 
 def cross_entropy_(logits, targets, ignore_index=None, reduction="mean", route=None, **unknown):

@@ -20,210 +20,27 @@
 
 #include <math.h>
 
-#include "tnn_pack.h"
-#include "tnn_decode.h"
+#include "tnn_decode_kernel.h"
 
 namespace {
 
 using namespace tnn;      // Pack, Math, aligned16, item_of, round16, with_float (tnn_pack.h)
+using namespace tnn::decode;      // the key loop, its argument record and the lane-group geometry (tnn_decode_kernel.h)
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int CHUNK = TNN_DECODE_CHUNK;
-constexpr int U = TNN_DECODE_UNROLL;
-constexpr int MAXD = TNN_ATTN_MAX_HEAD_DIM;
 constexpr int ITEMS = TNN_SAMPLE_ITEMS;
 constexpr int BINS = 1 << TNN_SAMPLE_RADIX_BITS;
-static_assert(TNN_DECODE_VEC == 16, "wide accesses are global_load / store_dwordx4");
 static_assert(BINS == THREADS, "one thread clears one bin of the histogram");
-static_assert(MAXD <= 128, "two element packs per lane cover a row");
-
-__device__ __forceinline__ float dot_pack(float a, float b, float d) { return fmaf(a, b, d); }
-__device__ __forceinline__ double dot_pack(double a, double b, double d) { return fma(a, b, d); }
-__device__ __forceinline__ float dot_pack(f32x4 a, f32x4 b, float d) {
-    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, d))));
-}
-__device__ __forceinline__ double dot_pack(f64x2 a, f64x2 b, double d) { return fma(a.y, b.y, fma(a.x, b.x, d)); }
-
-__device__ __forceinline__ float xor_pack(float v, int o) { return __shfl_xor(v, o, 64); }
-__device__ __forceinline__ double xor_pack(double v, int o) { return __shfl_xor(v, o, 64); }
-__device__ __forceinline__ f32x4 xor_pack(f32x4 v, int o) {
-    f32x4 r;
-    r.x = __shfl_xor(v.x, o, 64); r.y = __shfl_xor(v.y, o, 64); r.z = __shfl_xor(v.z, o, 64); r.w = __shfl_xor(v.w, o, 64);
-    return r;
-}
-__device__ __forceinline__ f64x2 xor_pack(f64x2 v, int o) {
-    f64x2 r;
-    r.x = __shfl_xor(v.x, o, 64); r.y = __shfl_xor(v.y, o, 64);
-    return r;
-}
 
 // ------------------------------------------------------------------------------------------------ decode attention
-struct DecodeArgs {
-    const void* q; const void* k_new; const void* v_new;
-    void* k_cache; void* v_cache; void* o; void* ws;
-    int64_t sq[2], skn[2], svn[2], skc[3], svc[3], so[2];      // element strides: batch, head (, row)
-    int64_t nkeys;       // live keys, the appended one included
-    int64_t len;         // the cache row the appended key goes to (read only when k_new != NULL)
-    int64_t chunks, splits;
-    int H, D, Dv, G, log_g;
-    double scale;
-};
-
+// (the bodies are in tnn_decode_kernel.h: csrc/tnn_ragged.hip instantiates the same ones with the lengths read on the device)
 template <typename T, bool VECTOR, int R>
 __global__ __launch_bounds__(THREADS) void decode_kernel(DecodeArgs a) {
-    typedef typename Pack<T, VECTOR>::type P;
-    constexpr int N = Pack<T, VECTOR>::N;
-    __shared__ T s_m[WAVES], s_l[WAVES];
-    __shared__ T s_acc[WAVES][MAXD];
-
-    const int split = blockIdx.x, bh = blockIdx.y;
-    const int b = bh / a.H, h = bh - b * a.H;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int G = a.G, c = lane & (G - 1), grp = lane >> a.log_g;
-    const int per_wave = 64 >> a.log_g, slots = WAVES * per_wave, slot = wave * per_wave + grp;
-
-    const T* q = static_cast<const T*>(a.q) + b * a.sq[0] + h * a.sq[1];
-    T* kc = static_cast<T*>(a.k_cache) + b * a.skc[0] + h * a.skc[1];
-    T* vc = static_cast<T*>(a.v_cache) + b * a.svc[0] + h * a.svc[1];
-    const bool append = a.k_new != nullptr;
-    const T* kn = append ? static_cast<const T*>(a.k_new) + b * a.skn[0] + h * a.skn[1] : nullptr;
-    const T* vn = append ? static_cast<const T*>(a.v_new) + b * a.svn[0] + h * a.svn[1] : nullptr;
-
-    // the run of chunks of this split: keys [k0, k1)
-    const int64_t k0 = (split * a.chunks / a.splits) * CHUNK;
-    int64_t k1 = ((split + 1) * a.chunks / a.splits) * CHUNK;
-    if (k1 > a.nkeys) k1 = a.nkeys;
-
-    int col[R];
-    bool dok[R], vok[R];
-    P qp[R], acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        col[r] = (c + r * G) * N;
-        dok[r] = col[r] < a.D;
-        vok[r] = col[r] < a.Dv;
-        qp[r] = dok[r] ? *reinterpret_cast<const P*>(q + col[r]) : P(0);
-        acc[r] = P(0);
-    }
-    const T scale = (T)a.scale;
-    T m = (T)-INFINITY, l = (T)0;
-
-    for (int64_t base = k0; base < k1; base += (int64_t)U * slots) {          // (workgroup-uniform trip count)
-        P kp[U][R], vp[U][R];
-        bool live[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t j = base + (int64_t)u * slots + slot;
-            live[u] = j < k1;
-            const bool fresh = append && live[u] && j == a.len;        // (only the split that owns the position)
-            const T* krow = fresh ? kn : kc + j * a.skc[2];
-            const T* vrow = fresh ? vn : vc + j * a.svc[2];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                kp[u][r] = live[u] && dok[r] ? *reinterpret_cast<const P*>(krow + col[r]) : P(0);
-                vp[u][r] = live[u] && vok[r] ? *reinterpret_cast<const P*>(vrow + col[r]) : P(0);
-            }
-            if (fresh) {                                       // the step's own row: from registers into cache row len
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    if (dok[r]) *reinterpret_cast<P*>(kc + j * a.skc[2] + col[r]) = kp[u][r];
-                    if (vok[r]) *reinterpret_cast<P*>(vc + j * a.svc[2] + col[r]) = vp[u][r];
-                }
-            }
-        }
-        T s[U];
-        T mx = m;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            T d = (T)0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) d = dot_pack(qp[r], kp[u][r], d);
-            for (int o = G >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-            s[u] = live[u] ? d * scale : (T)-INFINITY;
-            mx = s[u] > mx ? s[u] : mx;
-        }
-        if (mx > (T)-INFINITY) {                               // (uniform over the group: it shares m and the scores)
-            const T f = Math<T>::exp_(m - mx);                 // 0 on the group's first keys (m = -inf)
-            l *= f;
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] *= f;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const T p = Math<T>::exp_(s[u] - mx);          // 0 for a key that is not live
-                l += p;
-#pragma unroll
-                for (int r = 0; r < R; ++r) acc[r] += p * vp[u][r];
-            }
-            m = mx;
-        }
-    }
-
-    // the groups of the wave meet: a fixed exchange tree; group 0 holds the wave's result
-    for (int o = G; o < 64; o <<= 1) {
-        const T m2 = __shfl_xor(m, o, 64), l2 = __shfl_xor(l, o, 64);
-        P acc2[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc2[r] = xor_pack(acc[r], o);
-        const T mx = m2 > m ? m2 : m;
-        if (mx > (T)-INFINITY) {
-            const T f1 = Math<T>::exp_(m - mx), f2 = Math<T>::exp_(m2 - mx);
-            l = l * f1 + l2 * f2;
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] = acc[r] * f1 + acc2[r] * f2;
-            m = mx;
-        }
-    }
-    if (grp == 0) {
-        if (c == 0) { s_m[wave] = m; s_l[wave] = l; }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (vok[r]) *reinterpret_cast<P*>(&s_acc[wave][col[r]]) = acc[r];
-        }
-    }
-    __syncthreads();
-    // the waves meet in wave order; thread x owns column x of the result (every split holds at least one live key, so the
-    // maximum is finite; a wave without keys has m = -inf and weighs 0)
-    if (tid < a.Dv) {
-        T mx = s_m[0];
-#pragma unroll
-        for (int w = 1; w < WAVES; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
-        T lsum = (T)0, asum = (T)0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const T f = Math<T>::exp_(s_m[w] - mx);
-            lsum += s_l[w] * f;
-            asum += s_acc[w][tid] * f;
-        }
-        if (a.splits == 1) {
-            static_cast<T*>(a.o)[b * a.so[0] + h * a.so[1] + tid] = asum / lsum;
-        } else {
-            T* rec = static_cast<T*>(a.ws) + ((int64_t)bh * a.splits + split) * (a.Dv + 2);
-            if (tid == 0) { rec[0] = mx; rec[1] = lsum; }
-            rec[2 + tid] = asum;
-        }
-    }
+    decode_body<T, VECTOR, R>(a);
 }
 
-// o = the splits' (m, l, acc) records combined in ascending split order; one workgroup per (batch, head), thread x owns column x
 template <typename T>
 __global__ __launch_bounds__(MAXD) void decode_combine_kernel(DecodeArgs a) {
-    const int bh = blockIdx.x, b = bh / a.H, h = bh - b * a.H, tid = threadIdx.x;
-    if (tid >= a.Dv) return;
-    const int64_t width = a.Dv + 2;
-    const T* rec = static_cast<const T*>(a.ws) + (int64_t)bh * a.splits * width;
-    T mx = rec[0];
-    for (int64_t s = 1; s < a.splits; ++s) {
-        const T v = rec[s * width];
-        mx = v > mx ? v : mx;
-    }
-    T lsum = (T)0, asum = (T)0;
-    for (int64_t s = 0; s < a.splits; ++s) {
-        const T f = Math<T>::exp_(rec[s * width] - mx);
-        lsum += rec[s * width + 1] * f;
-        asum += rec[s * width + 2 + tid] * f;
-    }
-    static_cast<T*>(a.o)[b * a.so[0] + h * a.so[1] + tid] = asum / lsum;
+    combine_body<T>(a);
 }
 
 // ------------------------------------------------------------------------------------------------ sampling
@@ -442,10 +259,6 @@ __global__ __launch_bounds__(THREADS) void sample_kernel(const T* __restrict__ l
     }
 }
 
-inline int64_t decode_space(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype) {
-    return splits == 1 ? 0 : round16(B * H * splits * (Dv + 2) * item_of(dtype));
-}
-
 template <typename T>
 void launch_decode(const DecodeArgs& a, bool vec, int R, dim3 grid) {
     hipStream_t s = tnn::stream();
@@ -489,27 +302,9 @@ extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_n
     if (splits > 1) TNN_REQUIRE_WORKSPACE("tnn_decode_attn", workspace, workspace_bytes, need);
 
     DecodeArgs a = {};
-    a.q = q; a.k_new = k_new; a.v_new = v_new; a.k_cache = k_cache; a.v_cache = v_cache; a.o = o; a.ws = workspace;
-    const int64_t* st = strides;
-    a.sq[0] = st[0]; a.sq[1] = st[1];
-    a.skn[0] = st[3]; a.skn[1] = st[4];
-    a.svn[0] = st[6]; a.svn[1] = st[7];
-    for (int i = 0; i < 3; ++i) { a.skc[i] = st[9 + i]; a.svc[i] = st[12 + i]; }
-    a.so[0] = st[15]; a.so[1] = st[16];
-    a.nkeys = nkeys; a.len = len; a.chunks = chunks; a.splits = splits;
-    a.H = (int)H; a.D = (int)D; a.Dv = (int)Dv; a.scale = scale;
-
-    const int64_t per = TNN_DECODE_VEC / item_of(dtype);
-    bool vec = D % per == 0 && Dv % per == 0 && aligned16(q) && aligned16(k_cache) && aligned16(v_cache) && aligned16(o) &&
-               aligned16(k_new) && aligned16(v_new);
-    for (int i = 0; i < 2 && vec; ++i)
-        vec = a.sq[i] % per == 0 && a.so[i] % per == 0 && (!append || (a.skn[i] % per == 0 && a.svn[i] % per == 0));
-    for (int i = 0; i < 3 && vec; ++i) vec = a.skc[i] % per == 0 && a.svc[i] % per == 0;
-    const int64_t widest = D > Dv ? D : Dv, packs = vec ? widest / per : widest;
-    const int R = packs > 64 ? 2 : 1;
-    const int64_t lanes = (packs + R - 1) / R;
-    a.G = 1; a.log_g = 0;
-    while (a.G < lanes) { a.G <<= 1; ++a.log_g; }
+    bool vec;
+    const int R = fill_args(a, q, k_new, v_new, k_cache, v_cache, o, workspace, H, D, Dv, strides, scale, splits, dtype, vec);
+    a.nkeys = nkeys; a.len = len; a.chunks = chunks;
 
     const dim3 grid((unsigned)splits, (unsigned)(B * H));
     with_float(dtype, [&](auto t) { launch_decode<decltype(t)>(a, vec, R, grid); });

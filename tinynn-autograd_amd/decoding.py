@@ -28,7 +28,8 @@ Routes
               in float64) — a host synchronisation per call, so it cannot be captured into a graph.  What runs under the CPU
               test twin and the second, independent implementation the GPU tests compare the kernels with.
 
-Out of scope: ragged batches, grouped-query heads, chunked prefill (it needs a bottom-right causal rule), top-p, bf16.
+Ragged batches — a length per sequence, read on the device — are ragged.py's (csrc/tnn_ragged.hip), which reuses this planner's
+strides and split rule.  Out of scope: grouped-query heads, chunked prefill (it needs a bottom-right causal rule), top-p, bf16.
 (u is an operand: generation.generate draws it on the host, or on the device with an rng.Generator.)
 """
 

@@ -33,6 +33,7 @@ from . import decoding as _dc
 from . import dropout as _dp
 from . import indexing as _ix
 from . import norm as _nm
+from . import ragged as _rg
 from . import tokens as _tk
 from ._lib import F32, F64, I64, U8
 
@@ -2068,6 +2069,155 @@ def sample_rows(logits, u, temperature=1.0, top_k=None, route=None):
     if _lib.capturing:
         raise RuntimeError("sample_rows (composed route) reads the logits back to the host, which a graph capture cannot do")
     return asarray(_dc.sample_host(np.asarray(x), None if ud is None else np.asarray(ud), plan.temperature, plan.top_k))
+
+
+# ---------------------------------------------------------------------- kernels: the ragged decoding step (csrc/tnn_ragged.hip)
+RAGGED_ROUTE = None   # tests / probes: "native" or "composed" overrides the planner's choice (ragged.py)
+
+
+def lengths(host):
+    """A ragged.Lengths from host integers [B]: the device int64 array and its host mirror."""
+    host = np.ascontiguousarray(host, dtype=np.int64).reshape(-1)
+    return _rg.Lengths(asarray(host), host)
+
+
+def _ragged_state(a, what, name):
+    """An integer state array is read (and mostly written) IN PLACE by a launch: a dense int64 device array."""
+    if isinstance(a, _rg.Lengths):
+        a = a.dev
+    if not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != np.dtype(np.int64):
+        raise TypeError("%s: %s must be a dense int64 device array" % (what, name))
+    return a
+
+
+def _ragged_mirror(lens, what):
+    """The host values of the lengths on the composed route: the mirror when there is one, else a read-back."""
+    if isinstance(lens, _rg.Lengths):
+        return lens.host
+    if _lib.capturing:
+        raise RuntimeError("%s (composed route) reads the lengths on the host, which a graph capture cannot do" % what)
+    return np.asarray(lens)
+
+
+def attention_decode_ragged(q, k_cache, v_cache, lens, k_new, v_new, scale=None, layout="bthd", route=None, splits=None):
+    """attention_decode with the append for a RAGGED batch: sequence b writes k_new[b] / v_new[b] into cache row lens[b] and
+    attends over keys [0, lens[b]].  lens: a ragged.Lengths (device int64 [B] + host mirror) or a dense int64 device array.
+    Native: ONE tnn_ragged_decode_attn call that reads the lengths on the device — its arguments do not depend on them, so
+    the call can be captured and replayed; a sequence whose length is outside [0, Tmax) gets zeros and its caches stay
+    untouched.  Composed (ragged.py: the CPU test twin, route="composed"): a loop over the sequences that calls the composed
+    attention_decode on batch slices with the host values of the lengths; it raises inside an open capture."""
+    what = "attention_decode_ragged"
+    if k_new is None or v_new is None:
+        raise ValueError("%s: k_new and v_new are required (the step appends its row)" % what)
+    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
+    dt = cands[0] if cands else _default_float
+    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
+    q, k_new, v_new = (asarray(a)._as_float(dt)._contig() for a in (q, k_new, v_new))
+    ld = _ragged_state(lens, what, "lens")
+    lib = _lib.get()
+    plan = _rg.plan_ragged_decode(q.shape, k_cache.shape, v_cache.shape, ld.shape, k_new.shape, v_new.shape, scale, layout,
+                                  splits, native=lib.has_ragged, float_ok=dt in (np.dtype(np.float32), np.dtype(np.float64)),
+                                  route=route or RAGGED_ROUTE)
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        nbytes = plan.workspace_bytes(dt.itemsize)
+        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+        lib.ragged_decode_attn(q._ptr, k_new._ptr, v_new._ptr, k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
+                               ld._ptr, *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
+        return out
+    if _lib.capturing:
+        raise RuntimeError("%s (composed route) loops over the sequences with host lengths, which a graph capture cannot do" % what)
+    host = _ragged_mirror(lens, what)
+    out = zeros(plan.out_shape, dt)
+    for b in range(plan.B):
+        if not 0 <= int(host[b]) < plan.Tmax:
+            continue                                           # zeros, the caches untouched
+        one = slice(b, b + 1)
+        out[one] = attention_decode(q[one], k_cache[one], v_cache[one], int(host[b]), k_new[one], v_new[one], scale=plan.scale,
+                                    layout=layout, route="composed")
+    return out
+
+
+def embedding_at(table, ids, positions, pos=None, route=None):
+    """out[..., :] = table[ids[...], :] + pos[positions[...], :]: every id sits at its OWN position.  table [V, E], pos
+    [Tpos, E] or None (nothing is added); ids and positions: dense int64 device arrays of one shape (positions may be a
+    ragged.Lengths), neither is read back — an id outside [0, V) gives a zero token row, a position outside [0, Tpos) a zero
+    position row.  Native: ONE tnn_ragged_embed_fwd launch; composed: two row gathers and an addition (in-range indices only)."""
+    what = "embedding_at"
+    dt, (table, pos) = _norm_operands(table, pos)
+    if table.ndim != 2 or (pos is not None and (pos.ndim != 2 or pos.shape[1] != table.shape[1])):
+        raise ValueError("%s: the table must be [V, E] and pos [Tpos, E], got shapes %s and %s"
+                         % (what, tuple(table.shape), None if pos is None else tuple(pos.shape)))
+    idd = _ragged_state(ids, what, "ids")._contig()
+    shape = tuple(idd.shape)
+    m, e = _prod(shape), int(table.shape[1])
+    pd = None
+    if pos is not None:
+        pd = _ragged_state(positions, what, "positions")
+        if _prod(pd.shape) != m:
+            raise ValueError("%s: ids %s and positions %s must hold one position per id" % (what, shape, tuple(pd.shape)))
+    lib = _lib.get()
+    route = _rg.pick_route(lib.has_ragged and dt in (np.dtype(np.float32), np.dtype(np.float64)), route or RAGGED_ROUTE, what)
+    if m == 0:
+        return zeros(shape + (e,), dt)
+    if route == "native":
+        out = DeviceArray._new(shape + (e,), dt)
+        lib.ragged_embed_fwd(table._ptr, idd._ptr, _ptr_of(pos), _ptr_of(pd), out._ptr, m, int(table.shape[0]), e,
+                             0 if pos is None else int(pos.shape[0]), out._code())
+        return out
+    out = table.take(idd.reshape(m))
+    if pos is not None:
+        out = out + pos.take(pd.reshape(m))
+    return out.reshape(shape + (e,))
+
+
+def ragged_advance(picked, lens, start, done, out, cur, u_all=None, u_cur=None, eos=None, pad=0, route=None):
+    """The bookkeeping of one token step of a ragged batch, IN PLACE (include/tnn_ragged.h states the rule; ragged.advance_host
+    is its numpy form): every sequence's length grows by one, its id — `picked`, or `pad` once it has ended — goes to
+    out[b, lens[b]] and to cur[b], the end-of-sequence flag done[b] is set on `eos` (None: there is none), and the next
+    step's uniform numbers are copied from u_all [N, B] into u_cur [B].  All integer arrays: dense int64 device arrays
+    (lens may be a ragged.Lengths, whose host mirror is advanced too — except while a graph capture records the launch, which
+    does not run it).  Native: ONE tnn_ragged_advance launch; composed: the arrays are read back, advanced in numpy and
+    uploaded, which a graph capture cannot do."""
+    what = "ragged_advance"
+    ld, sd, dd, od, cd, pk = (_ragged_state(a, what, n) for a, n in ((lens, "lens"), (start, "start"), (done, "done"),
+                                                                      (out, "out"), (cur, "cur"), (picked, "picked")))
+    if (u_all is None) != (u_cur is None):
+        raise ValueError("%s: u_all and u_cur come together or not at all" % what)
+    dt = np.dtype(np.float32)
+    if u_all is not None:
+        dt = u_all.dtype
+        for a, n in ((u_all, "u_all"), (u_cur, "u_cur")):
+            if not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != dt or dt.kind != "f":
+                raise TypeError("%s: %s must be a dense floating-point device array (u_all and u_cur of one dtype)" % (what, n))
+    B, Tout, N = _rg.check_advance(pk.shape, ld.shape, sd.shape, dd.shape, od.shape, cd.shape,
+                                   None if u_all is None else u_all.shape, None if u_cur is None else u_cur.shape)
+    eos = -1 if eos is None else int(eos)
+    lib = _lib.get()
+    route = _rg.pick_route(lib.has_ragged and dt in (np.dtype(np.float32), np.dtype(np.float64)), route or RAGGED_ROUTE, what)
+    if B == 0:
+        return
+    if route == "native":
+        lib.ragged_advance(pk._ptr, ld._ptr, sd._ptr, dd._ptr, od._ptr, cd._ptr, _ptr_of(u_all), _ptr_of(u_cur), B, Tout, N, eos,
+                           int(pad), _CODE[dt])
+        if isinstance(lens, _rg.Lengths) and not _lib.capturing:
+            lens.host += 1
+        return
+    if _lib.capturing:
+        raise RuntimeError("%s (composed route) advances the state on the host, which a graph capture cannot do" % what)
+    h_lens = np.array(_ragged_mirror(lens, what))
+    h_done, h_out, h_cur = np.asarray(dd).copy(), np.asarray(od).copy(), np.asarray(cd).copy()
+    h_u = None if u_all is None else np.asarray(u_cur).copy()
+    _rg.advance_host(np.asarray(pk), h_lens, np.asarray(sd), h_done, h_out, h_cur, None if u_all is None else np.asarray(u_all),
+                     h_u, eos, int(pad))
+    for dev, host in ((ld, h_lens), (dd, h_done), (od, h_out), (cd, h_cur)):
+        dev[...] = asarray(host)
+    if u_all is not None:
+        u_cur[...] = asarray(h_u)
+    if isinstance(lens, _rg.Lengths):
+        lens.host[:] = h_lens
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)

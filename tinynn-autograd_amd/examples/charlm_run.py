@@ -7,7 +7,9 @@ token — so every position >= period can be predicted by attending one period b
 
 --generate N: after training, the first test sequences are continued greedily by N tokens from a prompt of 2 * period tokens
 (generation.generate: a key / value cache, every token chosen on the device), and the share of generated tokens that continue
-the motif is printed.
+the motif is printed.  --ragged cuts the prompts to differing lengths between `period` and 2 * period tokens (the ragged path
+of generation.generate: the sequences' lengths live on the device), --eos ID ends a sequence at token ID (the pad token 0 is
+emitted after it) and --capture records the token step into a graph once and replays it.
 
 --dropout P: dropout with rate P on the embedding's output and on both residual branches of every block (the fused residual
 form of ops.dropout_), drawn from the device generator of rng.py, which --seed seeds; 0, the default, adds no launch.
@@ -118,6 +120,22 @@ def main(args):
         raise ValueError("--generate %d: %d prompt + %d new tokens exceed --seq %d (the learned positions)"
                          % (args.generate, prompt_len, args.generate, args.seq))
     rows = test_x[:min(len(test_x), 8)]
+    if args.ragged or args.eos is not None or args.capture:
+        lens = np.full(len(rows), prompt_len)
+        if args.ragged:                                     # prompts of period .. 2 period tokens, the same in every run
+            lens = args.period + np.arange(len(rows)) % (args.period + 1)
+        out, ends = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, prompt_lens=lens, eos_id=args.eos,
+                             capture=args.capture, return_lengths=True)
+        new = np.stack([out[b, p:p + args.generate] for b, p in enumerate(lens)])
+        motif = np.stack([rows[b, np.arange(p, p + args.generate) % args.period] for b, p in enumerate(lens)])
+        live = np.arange(args.generate)[None, :] < (ends - lens)[:, None]          # up to and including an end of sequence
+        share = float((new == motif)[live].mean())
+        for b, row in enumerate(out):
+            print("  %s | %s" % (" ".join("%2d" % t for t in row[:lens[b]]), " ".join("%2d" % t for t in row[lens[b]:ends[b]])))
+        print("generated up to %d tokens for %d sequences (prompts of %d .. %d tokens): %.4f of them continue the motif"
+              % (args.generate, len(out), lens.min(), lens.max(), share))
+        args.generation = (out, share)
+        return history
     out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0)
     motif = rows[:, np.arange(prompt_len, prompt_len + args.generate) % args.period]     # what repeating the motif gives
     share = float((out[:, prompt_len:] == motif).mean())
@@ -143,6 +161,9 @@ def parse(argv=None):
     parser.add_argument("--seed", default=0, type=int)
     parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")
     parser.add_argument("--generate", default=0, type=int, help="continue the first test sequences greedily by N tokens")
+    parser.add_argument("--ragged", action="store_true", help="--generate: prompts of differing lengths (period .. 2 period tokens)")
+    parser.add_argument("--eos", default=None, type=int, metavar="ID", help="--generate: a sequence ends at token ID")
+    parser.add_argument("--capture", action="store_true", help="--generate: record the token step into a graph and replay it")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
     parser.add_argument("--adamw", action="store_true", help="AdamW on the device instead of Adam")
     parser.add_argument("--weight_decay", default=0.01, type=float, help="--adamw: decoupled weight decay")
