@@ -107,6 +107,9 @@ bool small_fast_ok(const GemmArgs& g, int transA, int transB) {
     // loop; the first layer's weight gradient with Adam (dw_tile_wide, small_tile<.., ADAM>) has its own up-front form, which
     // skips the MFMAs of chunks that do not exist: dense_bwd0_adam_kernel 5.4 -> 4.9 us at 128 rows, 6.5 -> 5.7 at 256 (kernel
     // trace), step 20.09 -> 19.80 / 25.81 -> 25.13 us (profiles/bwd0_roundtrips_ab.txt)
+    // the epilogue's operand (bias / mask source Y / old C) goes through a buffer load with a 32-bit offset as well
+    const int64_t lim = int64_t(1) << 31;
+    if (((g.M - 1) * g.ldc + g.N) * 4 >= lim || (g.epi == EPI_MASK && ((g.M - 1) * g.ldy + g.N) * 4 >= lim)) return false;
     return (!transA || transB) && mid_ok(g, transA, transB);      // (the same operand conditions as the mid-size kernel)
 }
 

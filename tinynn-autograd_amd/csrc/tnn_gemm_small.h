@@ -60,6 +60,7 @@ template <bool AKC, bool BKC, int WAVES, bool ADAM = false, bool TO_LDS = false>
 __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict__ colsum, int block,
                                            float (*red)[4][64], float (*bsum)[64], const AdamEpi* ad = nullptr,
                                            float* out_lds = nullptr) {
+    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);      // entry: in front of the Adam state's requests
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     int tm, tn;
@@ -78,7 +79,6 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float bs = 0.f;
     float a_p = 0.f, a_m = 0.f, a_v = 0.f, ab_p = 0.f, ab_m = 0.f, ab_v = 0.f, ic1 = 0.f, ic2 = 0.f;
-    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);
     if constexpr (ADAM) {
         ic1 = (float)(1.0 / (1.0 - ad->pows[0]));
         ic2 = (float)(1.0 / (1.0 - ad->pows[1]));
@@ -206,6 +206,7 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
 template <int WAVES, bool ADAM, bool TO_LDS>
 __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restrict__ colsum, const int block, float (*red)[8][64],
                                              float (*bsum)[2][64], const AdamEpi* ad = nullptr, float* out_lds = nullptr) {
+    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);      // entry: in front of the Adam state's requests
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     int tm, tn;
@@ -233,7 +234,6 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
     }
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     float bs0 = 0.f, bs1 = 0.f;
-    if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);
     // K loop: a wave requests the fragments of ALL its chunks (batches of up to TN_MAXC) before its first MFMA — one load round
     // trip per batch instead of one per chunk.  Buffer loads: a row k >= K (or a row of A past M) gets the offset 0xffffffff
     // and reads 0, no exec-mask branch; chunks that do not exist cost neither loads nor MFMAs (tn_batches).  Chunk order, the
@@ -316,6 +316,8 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
                                                 float (*red)[4][64], float (*bsum)[64], float* head_lds = nullptr) {
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     constexpr uint32_t OOB = 0xffffffffu;
+    constexpr int KID = WAVES == 16 ? 0 : 1;              // (trace build: fwd0 runs 16 waves, fwd1 4 — or 8 in the data-parallel tail form)
+    TNN_STEP_STAMP(g_step_trace, KID, 0);                 // the entry stamp is the first thing: a stamp behind the prologue hides it
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     int tm, tn;
@@ -338,25 +340,60 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
     const int e_r = tid >> 6, e_ln = tid & 63;
     const int64_t e_row = m0 + (e_ln >> 4) * 4 + e_r, e_col = n0 + (e_ln & 15);   // 16x16x4 C/D layout
     const bool e_live = tid < 256 && e_row < g.M && e_col < g.N;
+    // The epilogue's operand and wave 0's head_w fragment travel like the K loop's fragments: a buffer resource chosen by
+    // kernel-uniform selects (a NULL bias / no operand: 0 bytes long, every offset reads 0), a 32-bit byte offset, and
+    // 0xffffffff for a thread, row or unit that does not exist.  Left to pointers, each of these loads sat under its own
+    // exec-mask branch behind a 64-bit multiply-add whose register pair overlapped the load in front of it, and wave 0 of
+    // every workgroup took three dependent round trips before it requested its first fragment.  32-bit extents of C / Y:
+    // small_fast_ok.
+    const float* e_ptr = nullptr;
+    uint32_t e_bytes = 0u, e_off = 0u;
+    if (g.epi == EPI_BIAS_ACT) {
+        e_ptr = g.bias; e_bytes = (uint32_t)g.N * 4u; e_off = (uint32_t)e_col * 4u;
+    } else if (g.epi == EPI_MASK) {
+        e_ptr = g.Y; e_bytes = (uint32_t)((g.M - 1) * g.ldy + g.N) * 4u; e_off = ((uint32_t)e_row * (uint32_t)g.ldy + (uint32_t)e_col) * 4u;
+    } else if (g.beta != 0.f) {
+        e_ptr = g.C; e_bytes = (uint32_t)((g.M - 1) * g.ldc + g.N) * 4u; e_off = ((uint32_t)e_row * (uint32_t)g.ldc + (uint32_t)e_col) * 4u;
+    }
+    const __amdgpu_buffer_rsrc_t e_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e_ptr), 0, e_ptr ? e_bytes : 0u, 0x00020000);
+    const bool head_on = g.head_z != nullptr;                 // kernel-uniform
+    const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(g.head_w), 0, (head_on && g.head_w) ? (uint32_t)g.N * (uint32_t)g.head_c * 4u : 0u, 0x00020000);
+    const int swid = __builtin_amdgcn_readfirstlane(wid);     // the branches below are scalar: no exec mask around a load
     float e_pre = 0.f;
-    if (e_live) {
-        if (g.epi == EPI_BIAS_ACT) e_pre = g.bias ? g.bias[e_col] : 0.f;
-        else if (g.epi == EPI_MASK) e_pre = g.Y[e_row * g.ldy + e_col];
-        else if (g.beta != 0.f) e_pre = g.C[e_row * g.ldc + e_col];
-    }
     float head_pre[4] = {0.f, 0.f, 0.f, 0.f};                 // wave 0: head_w[n0 + 4 grp + j][i16], the B fragment of the partial-logit product
-    if (g.head_z != nullptr && wid == 0 && i16 < g.head_c) {
+    auto request_epilogue = [&]() {
+        if (WAVES <= 4 || swid < 4) {                         // the waves whose threads apply the epilogue
+            uint32_t off = e_live ? e_off : OOB;
+            asm("" : "+v"(off));                              // opaque (TnFrag::load): the select stays a select
+            e_pre = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(e_rsrc, off, 0, 0));
+        }
+        if (head_on && swid == 0) {
+            // one vector multiply for the lane's first unit (opaque, so that it is not fused with the add: a 32-bit multiply-add
+            // comes out as v_mad_u64_u32 on a register pair whose upper half is the load in flight in front of it — a full
+            // wait for nothing), the unit step added as a scalar
+            const uint32_t unit0 = (uint32_t)n0 + 4u * (uint32_t)grp, hc4 = (uint32_t)g.head_c * 4u;
+            uint32_t unit_b = unit0 * hc4;
+            asm("" : "+v"(unit_b));
+            const uint32_t off0 = unit_b + (uint32_t)i16 * 4u;
+            const bool cls_ok = i16 < g.head_c;
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (n0 + 4 * grp + j < g.N) head_pre[j] = g.head_w[(n0 + 4 * grp + j) * g.head_c + i16];
-    }
+            for (int j = 0; j < 4; ++j) {
+                const bool ok = cls_ok & (unit0 + (uint32_t)j < (uint32_t)g.N);
+                uint32_t off = ok ? off0 + (uint32_t)j * hc4 : OOB;
+                asm("" : "+v"(off));
+                head_pre[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(h_rsrc, off, 0, 0));
+            }
+        }
+    };
 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float bs = 0.f;
     constexpr int MAXC = 4;
-    constexpr int KID = WAVES == 16 ? 0 : 1;              // (trace build: fwd0 runs 16 waves, fwd1 4 — or 8 in the data-parallel tail form)
-    TNN_STEP_STAMP(g_step_trace, KID, 0);
-    for (int c0 = wid; c0 < nchunks; c0 += WAVES * MAXC) {
+    // Every global read of the workgroup is requested before anything waits: the first batch's fragments, then — behind them,
+    // because loads return in order and nothing needs these before the reduction barrier — the epilogue's.  A wave without a
+    // chunk (K < 16 WAVES) still requests its epilogue operand.
+    for (int c0 = swid; c0 < nchunks; c0 += WAVES * MAXC) {
         float a[MAXC][4], b[MAXC][4];
 #pragma unroll
         for (int u = 0; u < MAXC; ++u) {
@@ -392,7 +429,12 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
                 }
             }
         }
-        if (c0 == wid) TNN_STEP_STAMP_ACKED(g_step_trace, KID, 1);
+        if (c0 == swid) {
+            __builtin_amdgcn_sched_barrier(0);                // the fragment requests stay in front
+            request_epilogue();
+            __builtin_amdgcn_sched_barrier(0);                // ... and no MFMA (with its wait) moves up between the loads
+            TNN_STEP_STAMP_ACKED(g_step_trace, KID, 1);
+        }
 #pragma unroll
         for (int u = 0; u < MAXC; ++u) {
 #pragma unroll
@@ -400,6 +442,7 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
             bs += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
         }
     }
+    if (swid >= nchunks) request_epilogue();
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc[r];
     bsum[wid][lane] = bs;
@@ -426,7 +469,7 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
         // out[row][col] * head_w[n0 + col][c] (a sign-encoded ReLU zero, -0.0, contributes -0 * w = 0).  The classifier
         // head then only ADDS tiles_n partials per logit instead of re-reading the whole activation and redoing the
         // product in every workgroup (csrc/tnn_head.hip).  The finished 16 x 16 tile goes through LDS once and wave 0
-        // multiplies it with head_w's 16 rows (fragments requested at kernel start) in four 16x16x4 MFMAs.
+        // multiplies it with head_w's 16 rows (fragments requested behind the first batch's: request_epilogue) in four 16x16x4 MFMAs.
         float* tile_s = head_lds;                               // [16][20]: 16-B aligned rows, conflict-free 16-B reads
         if (tid < 256) tile_s[((e_ln >> 4) * 4 + e_r) * 20 + (e_ln & 15)] = e_val;
         __syncthreads();

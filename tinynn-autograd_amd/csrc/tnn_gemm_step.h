@@ -208,6 +208,19 @@ __global__ __launch_bounds__(512) void dense_fwd_rowpanel_head_kernel(RowPanelAr
     __shared__ __attribute__((aligned(16))) float a_s[16 * AS];
     f32x4 accq[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   // independent MFMA chains
     for (int kb = 0; kb < g.K; kb += KB) {
+        // A[16 rows][kb .. kb + 256): 1024 pieces of 16 B, two per thread (rows beyond M / columns beyond K: zero-filled)
+        // Requested BEFORE the 64 B fragments: the load counter holds 63, so behind them these two waited for the oldest loads
+        // to return (s_waitcnt vmcnt(52) in the gfx950 assembly) — the rows every MFMA of the super-block needs went out a
+        // round trip late.  In front, the wait falls on the last few B fragments, which the first chunks' MFMAs do not need.
+        u32x4_t av[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int piece = tid + i * 512, row = piece >> 6, c4 = piece & 63;
+            const uint32_t k = (uint32_t)kb + (uint32_t)c4 * 4u;
+            const uint32_t aoff = (m0 + row < g.M && k < K) ? (uint32_t)(m0 + row) * lda4 + k * 4u : OOB;
+            av[i] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, aoff, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
         float b[CH][4];
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -217,15 +230,6 @@ __global__ __launch_bounds__(512) void dense_fwd_rowpanel_head_kernel(RowPanelAr
                 const uint32_t boff = (k + j < K) ? b_lane + (uint32_t)(kb / 16 + c) * 16u * ldb4 + (uint32_t)j * ldb4 : OOB;
                 b[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b_rsrc, boff, 0, 0));
             }
-        }
-        // A[16 rows][kb .. kb + 256): 1024 pieces of 16 B, two per thread (rows beyond M / columns beyond K: zero-filled)
-        u32x4_t av[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int piece = tid + i * 512, row = piece >> 6, c4 = piece & 63;
-            const uint32_t k = (uint32_t)kb + (uint32_t)c4 * 4u;
-            const uint32_t aoff = (m0 + row < g.M && k < K) ? (uint32_t)(m0 + row) * lda4 + k * 4u : OOB;
-            av[i] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, aoff, 0, 0);
         }
         if (kb) __syncthreads();                              // the previous super-block's fragments have been read
 #pragma unroll

@@ -77,15 +77,27 @@ __device__ __forceinline__ void head_stage_request(const HeadMArgs& p, const int
         h.yv = *reinterpret_cast<const f32x4*>(p.y + 4 * t);
     }
 }
+// BI: the bias of this thread's four staged elements, requested WITH the partial logits (no exec-mask branch: every index is
+// below C) — asked for inside ST it was a second dependent round trip behind the wait for everything else.  The same for
+// every row block of the row-blocked kernel (a block starts at a multiple of C floats).  The element-wise path reads its own.
 template <int C, int NP>
-__device__ __forceinline__ void head_stage_store(const HeadMArgs& p, const int t, const HeadStage<C, NP>& h, float* zs, float* ys) {
+__device__ __forceinline__ f32x4 head_stage_bias(const HeadMArgs& p, const int t) {
+    f32x4 b = {0.f, 0.f, 0.f, 0.f};
+    if (p.vec) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) b[i] = p.b[(4 * t + i) % C];
+    }
+    return b;
+}
+template <int C, int NP>
+__device__ __forceinline__ void head_stage_store(const HeadMArgs& p, const int t, const HeadStage<C, NP>& h, float* zs, float* ys,
+                                                 const f32x4 bias4) {
     static_assert(NP == 8, "the partial-sum tree is written for 8 tiles");
     const int n = p.m * C;
     if (p.vec) {
         if (t < (n >> 2)) {
             f32x4 s = ((h.v[0] + h.v[1]) + (h.v[2] + h.v[3])) + ((h.v[4] + h.v[5]) + (h.v[6] + h.v[7]));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s[i] += p.b[(4 * t + i) % C];
+            s += bias4;                                    // (tree + bias, element by element, as before)
             *reinterpret_cast<f32x4*>(zs + 4 * t) = s;
             *reinterpret_cast<f32x4*>(ys + 4 * t) = h.yv;
         }
@@ -137,8 +149,10 @@ __device__ __forceinline__ void head_block(const HeadMArgs& p, const int g) {
     __shared__ __attribute__((aligned(16))) float zst[PART ? ROWS * C : 4], yst[PART ? ROWS * C : 4];   // staged logits / labels
     HeadStage<C, NP> stg;
     f32x4 av[PART ? 1 : KC];
+    f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
     if constexpr (PART) {
         head_stage_request<C, NP>(p, t, stg);
+        bias4 = head_stage_bias<C, NP>(p, t);
     } else {
         const float* arow = p.a + (size_t)min(16 * wid + i16, m - 1) * H + 4 * grp;
 #pragma unroll
@@ -174,7 +188,7 @@ __device__ __forceinline__ void head_block(const HeadMArgs& p, const int g) {
     }
 
     if constexpr (PART) {
-        head_stage_store<C, NP>(p, t, stg, zst, yst);
+        head_stage_store<C, NP>(p, t, stg, zst, yst, bias4);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -407,6 +421,7 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     // r = 0..3 — for the dW tile that IS the B fragment of the tile product (b[j] = dz1[16 w + 4 grp + j][n0 + i16]).
     HeadStage<C, NP> stg;
     head_stage_request<C, NP>(p, t, stg);
+    const f32x4 bias4 = head_stage_bias<C, NP>(p, t);
     const int urow = (is_dw ? n0 : 16 * wid) + i16;                  // this lane's hidden unit
     const int prow0 = (is_dw ? 16 * wid : m0) + 4 * grp;             // first of this lane's 4 panel rows
     float w2f[3], a1m[4];
@@ -414,27 +429,32 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     for (int s3 = 0; s3 < 3; ++s3) w2f[s3] = p.w[(size_t)urow * C + min(4 * s3 + grp, C - 1)];
 #pragma unroll
     for (int r = 0; r < 4; ++r) a1m[r] = p.a[(size_t)min(prow0 + r, m - 1) * H + urow];
-    float af[4] = {0.f, 0.f, 0.f, 0.f};          // dW: x fragment
-    f32x4 bf = {0.f, 0.f, 0.f, 0.f}, bf1 = {0.f, 0.f, 0.f, 0.f};     // dx: W1 fragment(s)
-    float e_pre = 0.f, e_pre1 = 0.f;             // dx: mask source(s)
+    // The role's own loads, in ONE sequence for both roles (the role is block-uniform, but loads issued inside the two arms of a
+    // branch came out with a full wait in front of them or behind them in the gfx950 assembly — a second round trip).  Both roles
+    // read x: the dW tile its A fragment x[16 w + 4 grp + j][m0 + i16], the dx tile its mask source(s) x[m0 + 4 grp + e_r][n0 + i16
+    // (+ 16)] (e_ln >> 4 == grp, e_ln & 15 == i16) — so the four loads differ in their row and column only, chosen by selects
+    // (loads 2 and 3 of a dx tile repeat load 0).  Rows beyond m read row m - 1, as before.
     const int e_r = (t >> 6) & 3, e_ln = t & 63;
-    if (is_dw) {
+    float xq[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) af[j] = q.x[(size_t)min(16 * wid + 4 * grp + j, m - 1) * n_in + m0 + i16];
-    } else {
-        bf = *reinterpret_cast<const f32x4*>(q.w1 + (size_t)(n0 + i16) * H + 16 * wid + 4 * grp);
-        if (wide) bf1 = *reinterpret_cast<const f32x4*>(q.w1 + (size_t)(n0 + 16 + i16) * H + 16 * wid + 4 * grp);
-        if (t < 256) {
-            const float* xr = q.x + (size_t)min(m0 + (e_ln >> 4) * 4 + e_r, m - 1) * n_in + n0 + (e_ln & 15);
-            e_pre = xr[0];
-            if (wide) e_pre1 = xr[16];
-        }
+    for (int j = 0; j < 4; ++j) {
+        const int xrow = is_dw ? 16 * wid + 4 * grp + j : m0 + 4 * grp + e_r;
+        const int xcol = (is_dw ? m0 : n0 + ((j == 1 && wide) ? 16 : 0)) + i16;
+        xq[j] = q.x[(size_t)min(xrow, m - 1) * n_in + xcol];
     }
+    // dx: W1 fragment(s), 16 bytes each, rows n0 + i16 and (wide) n0 + 16 + i16 of W1.  Unconditional as well — inside a scalar
+    // branch the second one came out with s_waitcnt vmcnt(0) directly behind it (its registers are copied where the arms join).
+    // A narrow tile repeats its first row, a dW tile, which has no use for them, reads rows i16 (n_in >= 16: they exist).
+    const int wrow = (is_dw ? 0 : n0) + i16, wrow1 = wrow + ((!is_dw && wide) ? 16 : 0);
+    const f32x4 bf = *reinterpret_cast<const f32x4*>(q.w1 + (size_t)wrow * H + 16 * wid + 4 * grp);
+    const f32x4 bf1 = *reinterpret_cast<const f32x4*>(q.w1 + (size_t)wrow1 * H + 16 * wid + 4 * grp);
+    float af[4] = {xq[0], xq[1], xq[2], xq[3]};  // dW: x fragment
+    float e_pre = xq[0], e_pre1 = xq[1];         // dx: mask source(s); their sign is tested behind the last barrier
     if (grp >= 2) w2f[2] = 0.f;                  // classes 10, 11 do not exist (the clamped address read class 9)
     static_assert(C == 10, "the zero columns of the K = 12 product are written for 10 classes");
 
     TNN_STEP_STAMP_ACKED(g_step_trace_head, 0, 1);
-    head_stage_store<C, NP>(p, t, stg, zs, ys);
+    head_stage_store<C, NP>(p, t, stg, zs, ys, bias4);
     __syncthreads();
     float zc[3], yc[3];
 #pragma unroll
@@ -521,6 +541,8 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     bsum[wid][lane] = bs;
     __syncthreads();
     TNN_STEP_STAMP(g_step_trace_head, 0, 2);
+    // opaque here: a sign test hoisted to directly behind its load waits for every operand in front of the other requests
+    asm volatile("" : "+v"(e_pre), "+v"(e_pre1));
     if (t < 256) {
         float s = 0.f;
 #pragma unroll
@@ -559,16 +581,6 @@ __device__ __forceinline__ void head_stage_request_rb(const HeadMArgs& p, const 
         }
         h.yv = *reinterpret_cast<const f32x4*>(p.y + base + 4 * t);
     }
-}
-template <int C, int NP>
-__device__ __forceinline__ f32x4 head_stage_bias(const HeadMArgs& p, const int t) {
-    // the bias of this thread's four staged elements — the same for every row block (a block starts at a multiple of C floats)
-    f32x4 b = {0.f, 0.f, 0.f, 0.f};
-    if (p.vec) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) b[i] = p.b[(4 * t + i) % C];
-    }
-    return b;
 }
 template <int C, int NP>
 __device__ __forceinline__ void head_stage_store_rb(const HeadMArgs& p, const int t, const HeadStage<C, NP>& h, float* zs, float* ys,
