@@ -289,7 +289,8 @@ int gemm_f64(int transA, int transB, int64_t M, int64_t N, int64_t K, const void
     g.sbk = transB ? 1 : ldb; g.sbn = transB ? ldb : 1;
     g.ldc = ldc; g.alpha = alpha; g.beta = beta; g.epi = epi;
     g.bias = (const double*)bias; g.act = act; g.Y = (const double*)Y; g.ldy = ldy;
-    dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
+    // y is capped at the grid limit like every launch of the library; the kernel walks the row tiles beyond it
+    dim3 grid((unsigned)((N + 63) / 64), (unsigned)std::min<int64_t>((M + 63) / 64, 65535));
     hipLaunchKernelGGL(gemm_f64_kernel, grid, 256, 0, tnn::stream(), g);
     TNN_LAUNCH_OK();
     return 0;

@@ -14,10 +14,10 @@ struct GemmArgsD {
     int64_t ldy;
 };
 
-__global__ __launch_bounds__(256) void gemm_f64_kernel(GemmArgsD g) {
-    __shared__ double As[16][64 + 1], Bs[16][64 + 1];
+// one 64 x 64 tile at (m0, n0); every thread of the workgroup calls it (barriers inside), each K step ends with one
+__device__ __forceinline__ void gemm_f64_tile(const GemmArgsD& g, const int64_t m0, const int64_t n0, double (*As)[64 + 1],
+                                              double (*Bs)[64 + 1]) {
     int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    int64_t m0 = (int64_t)blockIdx.y * 64, n0 = (int64_t)blockIdx.x * 64;
     double acc[4][4] = {};
     for (int64_t k0 = 0; k0 < g.K; k0 += 16) {
         for (int f = threadIdx.x; f < 16 * 64; f += 256) {
@@ -61,4 +61,12 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(GemmArgsD g) {
             }
             g.C[row * g.ldc + col] = v;
         }
+}
+
+// grid (column tiles, row tiles capped at the grid's y limit by gemm_f64): a workgroup walks its row tiles in steps of
+// gridDim.y, so a product with more than 65535 row tiles still launches (block-uniform trip count)
+__global__ __launch_bounds__(256) void gemm_f64_kernel(GemmArgsD g) {
+    __shared__ double As[16][64 + 1], Bs[16][64 + 1];
+    for (int64_t m0 = (int64_t)blockIdx.y * 64; m0 < g.M; m0 += (int64_t)gridDim.y * 64)
+        gemm_f64_tile(g, m0, (int64_t)blockIdx.x * 64, As, Bs);
 }
