@@ -71,6 +71,10 @@ from ._ragged_signatures import _RAGGED_SIGNATURES            # noqa: E402  (inc
 
 RAGGED_SYMBOLS = sorted(_RAGGED_SIGNATURES)
 
+from ._gqa_signatures import _GQA_SIGNATURES                  # noqa: E402  (include/tnn_gqa.h: libtnn_hip.so only)
+
+GQA_SYMBOLS = sorted(_GQA_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -138,6 +142,8 @@ class _Lib(object):
         # Model.clip_grad_norm evaluate the same maths on DeviceArray arithmetic and read the norm back
         # and the ragged decoding step (include/tnn_ragged.h): under the twin device_array loops over the sequences with the
         # host mirror of the lengths and advances the step's state in numpy (ragged.py)
+        # and grouped-query attention (include/tnn_gqa.h): under the twin device_array repeats k and v over the group, runs
+        # the composed attention / decode and sums dk and dv over the group (gqa.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -147,7 +153,8 @@ class _Lib(object):
                                     (_DECODE_SIGNATURES, "tnn_decode.h", "decode attention / sampling"),
                                     (_DROPOUT_SIGNATURES, "tnn_dropout.h", "random generator / dropout"),
                                     (_OSTEP_SIGNATURES, "tnn_ostep.h", "optimizer step"),
-                                    (_RAGGED_SIGNATURES, "tnn_ragged.h", "ragged decoding step")):
+                                    (_RAGGED_SIGNATURES, "tnn_ragged.h", "ragged decoding step"),
+                                    (_GQA_SIGNATURES, "tnn_gqa.h", "grouped-query attention")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -167,6 +174,7 @@ class _Lib(object):
         self.has_dropout = hasattr(self.cdll, "tnn_dropout_fwd")
         self.has_ostep = hasattr(self.cdll, "tnn_ostep_adamw")
         self.has_ragged = hasattr(self.cdll, "tnn_ragged_decode_attn")
+        self.has_gqa = hasattr(self.cdll, "tnn_gqa_decode_attn")
 
     @staticmethod
     def _absent(name, what):

@@ -209,13 +209,26 @@ class MultiHeadAttention(Layer):
 
     Forward: [B T, E] rows -> three ops.dense_ -> [B, T, H, E / H] by reshape alone -> ops.attention_(layout="bthd"), whose
     kernels take strides, so nothing is transposed -> [B T, E] -> the output projection -> [B, T, E].  `fused=False` runs
-    the attention on the composed route (batched products, exp and sums on the generic array operations)."""
+    the attention on the composed route (batched products, exp and sums on the generic array operations).
 
-    def __init__(self, num_heads, num_in=None, causal=False, w_init=XavierUniformInit(), b_init=ZerosInit(), fused=True):
+    kv_heads (grouped-query attention): a divisor Hkv of num_heads — the keys and values have Hkv heads, query head h attends
+    over key / value head h // (num_heads / Hkv); Hkv == 1 is multi-query attention.  "wk" and "wv" are then
+    [E, Hkv E / num_heads] and "bk", "bv" [1, Hkv E / num_heads]; the parameter order and the order of host RNG draws are
+    unchanged.  Training runs ops.attention_gqa_, the cached path keeps Hkv heads in its LayerCache — num_heads / Hkv times
+    fewer bytes per token step — and runs ops.attention_decode_gqa_ / ops.attention_decode_ragged_gqa_.  None (the default)
+    is the multi-head path as it was, launch for launch; kv_heads == num_heads computes the same through the grouped ops."""
+
+    def __init__(self, num_heads, num_in=None, causal=False, w_init=XavierUniformInit(), b_init=ZerosInit(), fused=True,
+                 kv_heads=None):
         super().__init__("MultiHeadAttention")
         num_heads = int(num_heads)
         if num_heads < 1:
             raise ValueError("MultiHeadAttention: num_heads must be >= 1, got %r" % (num_heads,))
+        if kv_heads is not None:
+            kv_heads = int(kv_heads)
+            if kv_heads < 1 or num_heads % kv_heads != 0:
+                raise ValueError("MultiHeadAttention: kv_heads must be a divisor of num_heads = %d, got %r" % (num_heads, kv_heads))
+        self.kv_heads = kv_heads
         self.num_heads, self.causal, self.fused = num_heads, bool(causal), fused
         self.initializers = {name: (w_init if name[0] == "w" else b_init) for name in MHA_PARAM_ORDER}
         self.shapes = {name: ([num_in, num_in] if name[0] == "w" else [1, num_in]) for name in MHA_PARAM_ORDER}
@@ -229,8 +242,10 @@ class MultiHeadAttention(Layer):
         if width % self.num_heads != 0:
             raise ValueError("MultiHeadAttention: the input width %d is not a multiple of num_heads = %d"
                              % (width, self.num_heads))
+        kv_width = width if self.kv_heads is None else width // self.num_heads * self.kv_heads
         for name in MHA_PARAM_ORDER:                 # host RNG in parameter order: wq, wk, wv, wo draw, the biases do not
-            self.shapes[name] = [width, width] if name[0] == "w" else [1, width]
+            cols = kv_width if name[1] in "kv" else width
+            self.shapes[name] = [width, cols] if name[0] == "w" else [1, cols]
             tensor = self.initializers[name](shape=self.shapes[name])
             tensor.zero_grad()
             self.params[name] = tensor
@@ -241,7 +256,8 @@ class MultiHeadAttention(Layer):
         [B, T, H, E / H] are slice-assigned into the cache; afterwards T must be 1: three projections of the one row,
         ops.attention_decode_ with the append, the output projection.  A cache with `lens` set (a ragged batch) takes
         ops.attention_decode_ragged_, which reads every sequence's length on the device; cache.length stays the host's upper
-        bound.  None: today's path, bit for bit."""
+        bound.  None: today's path, bit for bit.  With kv_heads the cache holds the key / value heads and the grouped ops run
+        in the same places."""
         if len(inputs.shape) != 3:
             raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
         b, t, e = (int(s) for s in inputs.shape)
@@ -250,24 +266,32 @@ class MultiHeadAttention(Layer):
         if e != self.shapes["wq"][0]:
             raise ValueError("MultiHeadAttention: the input width %d differs from the layer's %d" % (e, self.shapes["wq"][0]))
         p, h = self.params, self.num_heads
+        hk = h if self.kv_heads is None else self.kv_heads       # the heads of k, v and the cache
         route = None if self.fused else "composed"
         if cache is not None:
             if not self.causal:
                 raise ValueError("MultiHeadAttention: a key / value cache needs causal=True (a non-causal layer's earlier "
                                  "positions would depend on later tokens)")
-            cache.check(b, t, h, e // h)                 # raises before any launch: a full cache, T > 1 after the prefill
+            cache.check(b, t, hk, e // h)                # raises before any launch: a full cache, T > 1 after the prefill
         self.inputs = inputs
         rows = ops.reshape(inputs, (b * t, e))
+        grouped = self.kv_heads is not None
         if cache is not None and cache.length > 0:
-            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h, e // h)) for n in "qkv")
+            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h if n == "q" else hk, e // h)) for n in "qkv")
             if getattr(cache, "lens", None) is not None:         # a ragged batch: the lengths are read on the device
-                att = ops.attention_decode_ragged_(q, cache.k, cache.v, cache.lens, k, v, layout="bthd", route=route)
+                decode = ops.attention_decode_ragged_gqa_ if grouped else ops.attention_decode_ragged_
+                att = decode(q, cache.k, cache.v, cache.lens, k, v, layout="bthd", route=route)
             else:
-                att = ops.attention_decode_(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
+                decode = ops.attention_decode_gqa_ if grouped else ops.attention_decode_
+                att = decode(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
             cache.length += 1
         else:
-            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h, e // h)) for n in "qkv")
-            att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route)
+            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h if n == "q" else hk, e // h))
+                       for n in "qkv")
+            if grouped:
+                att = ops.attention_gqa_(q, k, v, causal=self.causal, route=route)
+            else:
+                att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route)
             if cache is not None:
                 cache.fill(k.values, v.values)
         out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
@@ -383,10 +407,12 @@ class TransformerBlock(Layer):
     dropout > 0: h = x + drop(MHA(LN1(x))) and out = h + drop(MLP(LN2(h))) in the TRAIN phase, both through the fused residual
     form of ops.dropout_ — its launch REPLACES the block's residual add — drawing from `generator` (None: the default
     generator of rng.py).  With dropout == 0 (the default) and in the TEST phase the block runs exactly its launches without
-    the argument."""
+    the argument.  kv_heads: handed to the attention part (grouped-query attention; None: multi-head, as it was)."""
 
-    def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True, dropout=0.0, generator=None):
+    def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True, dropout=0.0, generator=None,
+                 kv_heads=None):
         super().__init__("TransformerBlock")
+        self.kv_heads = kv_heads
         self.drop = Dropout(dropout, generator=generator, fused=fused)
         self.num_heads, self.hidden, self.causal, self.eps, self.fused = int(num_heads), hidden, bool(causal), float(eps), fused
         if self.num_heads < 1:
@@ -405,7 +431,8 @@ class TransformerBlock(Layer):
         # created in BLOCK_PARAM_ORDER: each part draws from the host RNG as it is built
         parts = {}
         parts["ln1"] = LayerNorm(width, eps=self.eps, fused=self.fused)
-        parts["attn"] = MultiHeadAttention(self.num_heads, num_in=width, causal=self.causal, fused=self.fused)
+        parts["attn"] = MultiHeadAttention(self.num_heads, num_in=width, causal=self.causal, fused=self.fused,
+                                           kv_heads=self.kv_heads)
         parts["ln2"] = LayerNorm(width, eps=self.eps, fused=self.fused)
         parts["fc1"] = Dense(hidden, num_in=width, fused=self.fused)
         parts["fc2"] = Dense(width, num_in=hidden, fused=self.fused)

@@ -635,6 +635,45 @@ def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **u
     return node
 
 
+class _GqaVjp(_AttnVjp):
+    """The vjps of one ops.attention_gqa_ node: _AttnVjp's forms on the grouped entry points (dk and dv have the shapes of the
+    Hkv-head k and v: the group's query heads are summed inside the one dk + dv launch)."""
+    __slots__ = ()
+
+    def _opts(self):
+        return dict(causal=self.causal, scale=self.scale, route=self.route)
+
+    def _bwd_q(self, g, need_dq, dq_out=None):
+        return da.gqa_attention_bwd_q(self.q.values, self.k.values, self.v.values, self.out, g, self.lse, need_dq=need_dq,
+                                      dq_out=dq_out, **self._opts())
+
+    def _bwd_kv(self, g, delta, need_dk, need_dv, dk_out=None, dv_out=None):
+        return da.gqa_attention_bwd_kv(self.q.values, self.k.values, self.v.values, g, self.lse, delta, need_dk=need_dk,
+                                       need_dv=need_dv, dk_out=dk_out, dv_out=dv_out, **self._opts())
+
+
+def attention_gqa_(q, k, v, causal=False, scale=None, route=None, **unknown):
+    """Grouped-query attention node, layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] -> [B, Tq, H, Dv]
+    with H a multiple of Hkv; query head h attends over key / value head h // (H / Hkv).  Hkv == 1 is multi-query attention,
+    Hkv == H gives attention_'s result bit for bit.  The causal rule, the scale and the dtypes are attention_'s.
+
+    Forward is ONE tnn_gqa_fwd launch — k and v are never expanded.  Backward: dq from one launch, dk + dv from one launch in
+    which a workgroup owns a key block of ONE key / value head and adds its group's query heads in a fixed order (no atomics,
+    dk and dv are written once, in the shapes of k and v), into lent arena views when there are any.  Under the CPU test
+    twin, with route="composed" (or device_array.GQA_ROUTE), beyond head dimension 128 and for groups above 8, k and v are
+    repeated over the group, the composed attention runs and dk / dv are summed over the group axis.  Out of scope: masks,
+    dropout, bf16, other layouts — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_gqa_: unsupported arguments %s (masks, dropout, bf16 and other layouts than \"bthd\" are out "
+                        "of scope)" % sorted(unknown))
+    out, lse = da.gqa_attention(q.values, k.values, v.values, causal=causal, scale=scale, route=route)
+    ctx = _GqaVjp(q, k, v, out, lse, causal, scale, "bthd", route)
+    node = _make_node(q.__class__, out, [(q, ctx.d_q), (k, ctx.d_k), (v, ctx.d_v)])
+    ctx.edges = [name for name, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
 class _NormVjp(object):
     """The vjps of one ops.layer_norm_ / ops.rms_norm_ node: `fused_vjp` for Tensor.backward (ONE tnn_norm_bwd call for
     whichever of x, gamma, beta require gradients, written into arena views when they are lent), per-edge forms for
@@ -827,11 +866,11 @@ def attention_decode_(q, k_cache, v_cache, length, k_new=None, v_new=None, scale
     The result is a LEAF tensor without a grad_fn — nothing here is differentiable, and the operands' graphs are not
     extended.  ONE tnn_decode_attn call, whose keys are split over enough workgroups to cover the machine (decoding.py);
     under the CPU test twin and with route="composed" (or device_array.DECODE_ROUTE) a slice assignment and the composed
-    attention.  A ragged batch — every sequence at its own length — takes attention_decode_ragged_.  Out of scope:
-    grouped-query heads, chunked prefill, bf16 — unknown keyword arguments raise."""
+    attention.  A ragged batch — every sequence at its own length — takes attention_decode_ragged_, grouped-query heads
+    attention_decode_gqa_.  Out of scope: chunked prefill, bf16 — unknown keyword arguments raise."""
     if unknown:
-        raise TypeError("attention_decode_: unsupported arguments %s (grouped-query heads and bf16 are out of scope; a ragged "
-                        "batch takes attention_decode_ragged_)" % sorted(unknown))
+        raise TypeError("attention_decode_: unsupported arguments %s (bf16 is out of scope; a ragged batch takes "
+                        "attention_decode_ragged_, grouped-query heads attention_decode_gqa_)" % sorted(unknown))
     out = da.attention_decode(q.values, _raw_values(k_cache), _raw_values(v_cache), length,
                               None if k_new is None else k_new.values, None if v_new is None else v_new.values, scale=scale,
                               layout=layout, route=route, splits=splits)
@@ -858,12 +897,46 @@ def attention_decode_ragged_(q, k_cache, v_cache, lens, k_new, v_new, scale=None
     device array — it is read ON THE DEVICE, so the call's arguments do not change from step to step and a token step can be
     captured into a graph.  ONE tnn_ragged_decode_attn call whose grid depends on the shapes alone (ragged.py); under the CPU
     test twin and with route="composed" (or device_array.RAGGED_ROUTE) a loop over the sequences with the host lengths.
-    The result is a LEAF tensor without a grad_fn.  Out of scope: grouped-query heads, bf16 — unknown keyword arguments raise."""
+    The result is a LEAF tensor without a grad_fn.  Grouped-query heads take attention_decode_ragged_gqa_.  Out of scope: bf16 —
+    unknown keyword arguments raise."""
     if unknown:
-        raise TypeError("attention_decode_ragged_: unsupported arguments %s (grouped-query heads and bf16 are out of scope)"
+        raise TypeError("attention_decode_ragged_: unsupported arguments %s (bf16 is out of scope; grouped-query heads take "
+                        "attention_decode_ragged_gqa_)"
                         % sorted(unknown))
     out = da.attention_decode_ragged(q.values, _raw_values(k_cache), _raw_values(v_cache), _raw_values(lens), k_new.values,
                                      v_new.values, scale=scale, layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
+def attention_decode_gqa_(q, k_cache, v_cache, length, k_new=None, v_new=None, scale=None, layout="bthd", route=None,
+                          splits=None, **unknown):
+    """attention_decode_ for grouped-query heads, INFERENCE ONLY: q [B, H, D] over caches that hold Hkv heads ("bthd":
+    [B, Tmax, Hkv, D]; "bhtd": [B, Hkv, Tmax, D]), k_new [B, Hkv, D], v_new [B, Hkv, Dv]; query head h reads key / value head
+    h // (H / Hkv).  ONE tnn_gqa_decode_attn call in which a workgroup serves all H / Hkv queries of a key / value head from
+    one read of each cached row — the cache and the bytes of a step are H / Hkv times smaller than with repeated heads.
+    Composed route (CPU test twin, route="composed" or device_array.GQA_ROUTE, groups above 8): the append by a slice
+    assignment and the composed attention over the live prefix repeated over the group.  The result is a LEAF tensor without
+    a grad_fn.  Out of scope: chunked prefill, bf16 — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_decode_gqa_: unsupported arguments %s (bf16 is out of scope; a ragged batch takes "
+                        "attention_decode_ragged_gqa_)" % sorted(unknown))
+    out = da.gqa_decode(q.values, _raw_values(k_cache), _raw_values(v_cache), length,
+                        None if k_new is None else k_new.values, None if v_new is None else v_new.values, scale=scale,
+                        layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
+def attention_decode_ragged_gqa_(q, k_cache, v_cache, lens, k_new, v_new, scale=None, layout="bthd", route=None, splits=None,
+                                 **unknown):
+    """attention_decode_ragged_ for grouped-query heads, INFERENCE ONLY: the operands of attention_decode_gqa_ with lens (a
+    ragged.Lengths or a dense int64 device array [B]) read ON THE DEVICE.  ONE tnn_gqa_ragged_decode_attn call whose arguments
+    are fixed by the shapes, so a token step can be captured into a graph; the composed route loops over the sequences with
+    the host lengths and raises inside an open capture.  The result is a LEAF tensor without a grad_fn — unknown keyword
+    arguments raise."""
+    if unknown:
+        raise TypeError("attention_decode_ragged_gqa_: unsupported arguments %s (bf16 is out of scope)" % sorted(unknown))
+    out = da.gqa_decode(q.values, _raw_values(k_cache), _raw_values(v_cache), None, k_new.values, v_new.values,
+                        lens=_raw_values(lens), scale=scale, layout=layout, route=route, splits=splits)
     return q.__class__(out, False, [])
 
 
@@ -1213,6 +1286,28 @@ def cross_entropy(obj, targets, ignore_index=None, reduction="mean", **unknown):
     if unknown:
         raise TypeError("cross_entropy: unsupported arguments %s" % sorted(unknown))
     return cross_entropy_(as_tensor(obj), targets, ignore_index=ignore_index, reduction=reduction)
+
+
+def attention_gqa(obj, k, v, causal=False, scale=None, **unknown):
+    """not in the reference: see attention_gqa_ (grouped-query heads, layout "bthd"; unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("attention_gqa: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
+    return attention_gqa_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale)
+
+
+def attention_decode_gqa(obj, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=None, scale=None, layout="bthd",
+                         **unknown):
+    """not in the reference: see attention_decode_gqa_ (length=) and attention_decode_ragged_gqa_ (lens=); inference only;
+    unknown keyword arguments raise"""
+    if unknown:
+        raise TypeError("attention_decode_gqa: unsupported arguments %s" % sorted(unknown))
+    if (length is None) == (lens is None):
+        raise ValueError("attention_decode_gqa: give length= (a host integer shared by the batch) or lens= (one per sequence)")
+    if lens is not None:
+        return attention_decode_ragged_gqa_(as_tensor(obj), k_cache, v_cache, lens, as_tensor(k_new), as_tensor(v_new),
+                                            scale=scale, layout=layout)
+    return attention_decode_gqa_(as_tensor(obj), k_cache, v_cache, length, _opt_tensor(k_new), _opt_tensor(v_new), scale=scale,
+                                 layout=layout)
 
 
 def attention_decode(obj, k_cache, v_cache, length, k_new=None, v_new=None, scale=None, layout="bthd", **unknown):

@@ -42,6 +42,7 @@ __device__ __forceinline__ f64x2 xor_pack(f64x2 v, int o) {
 
 struct DecodeArgs {
     static constexpr bool RAGGED = false;
+    static constexpr bool GROUPED = false;
     const void* q; const void* k_new; const void* v_new;
     void* k_cache; void* v_cache; void* o; void* ws;
     int64_t sq[2], skn[2], svn[2], skc[3], svc[3], so[2];      // element strides: batch, head (, row)
@@ -60,6 +61,24 @@ struct RaggedArgs : DecodeArgs {
     int64_t Tmax;
 };
 
+// grouped-query heads (csrc/tnn_gqa.hip): a workgroup serves the `nq` query heads h nq .. h nq + nq - 1 of key / value head h
+// from ONE read of each K / V row.  H is then the number of KEY / VALUE heads (the grid's rows per batch); q, o and the
+// workspace records are indexed by the query head.  nq <= Q, the compile-time number of query states of the instantiation.
+struct GroupedArgs : DecodeArgs {
+    static constexpr bool GROUPED = true;
+    int nq;
+};
+struct GroupedRaggedArgs : RaggedArgs {
+    static constexpr bool GROUPED = true;
+    int nq;
+};
+
+template <typename A>
+__device__ __forceinline__ int live_queries(const A& a) {
+    if constexpr (A::GROUPED) return a.nq;
+    else return 1;
+}
+
 // what a workgroup without keys leaves: the neutral record (m = -inf, l = 0, acc = 0), which the combine skips
 template <typename T, typename A>
 __device__ __forceinline__ void neutral_record(const A& a, int bh, int split, int tid) {
@@ -70,25 +89,33 @@ __device__ __forceinline__ void neutral_record(const A& a, int bh, int split, in
     }
 }
 
-template <typename T, bool VECTOR, int R, typename A>
+// Q: the query states a workgroup keeps (1: one query per key / value head, the only form of tnn_decode.hip and
+// tnn_ragged.hip).  Every K / V pack a lane loads is used for all Q dot products and accumulations; query x of the
+// workgroup is query head h nq + x and goes through exactly the steps of the Q = 1 form, so its bits do not depend on Q.
+template <typename T, bool VECTOR, int R, int Q = 1, typename A>
 __device__ __forceinline__ void decode_body(const A& a) {
     typedef typename Pack<T, VECTOR>::type P;
     constexpr int N = Pack<T, VECTOR>::N;
-    __shared__ T s_m[WAVES], s_l[WAVES];
-    __shared__ T s_acc[WAVES][MAXD];
+    __shared__ T s_m[Q][WAVES], s_l[Q][WAVES];
+    __shared__ T s_acc[Q][WAVES][MAXD];
 
     const int split = blockIdx.x, bh = blockIdx.y;
     const int b = bh / a.H, h = bh - b * a.H;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nq = live_queries(a), h0 = h * nq, bh0 = bh * nq;        // the first query head of this workgroup
 
     int64_t nkeys, len, chunks;
     if constexpr (A::RAGGED) {
         len = a.lens[b];                                       // the ONE load that the ragged form adds
         if (len < 0 || len >= a.Tmax) {                        // (workgroup-uniform) no such row: zeros, the caches untouched
-            if (a.splits == 1) {
-                if (tid < a.Dv) static_cast<T*>(a.o)[b * a.so[0] + h * a.so[1] + tid] = (T)0;
-            } else {
-                neutral_record<T>(a, bh, split, tid);
+#pragma unroll
+            for (int x = 0; x < Q; ++x) {
+                if (x >= nq) break;
+                if (a.splits == 1) {
+                    if (tid < a.Dv) static_cast<T*>(a.o)[b * a.so[0] + (h0 + x) * a.so[1] + tid] = (T)0;
+                } else {
+                    neutral_record<T>(a, bh0 + x, split, tid);
+                }
             }
             return;
         }
@@ -101,7 +128,7 @@ __device__ __forceinline__ void decode_body(const A& a) {
     const int G = a.G, c = lane & (G - 1), grp = lane >> a.log_g;
     const int per_wave = 64 >> a.log_g, slots = WAVES * per_wave, slot = wave * per_wave + grp;
 
-    const T* q = static_cast<const T*>(a.q) + b * a.sq[0] + h * a.sq[1];
+    const T* q = static_cast<const T*>(a.q) + b * a.sq[0] + h0 * a.sq[1];
     T* kc = static_cast<T*>(a.k_cache) + b * a.skc[0] + h * a.skc[1];
     T* vc = static_cast<T*>(a.v_cache) + b * a.svc[0] + h * a.svc[1];
     const bool append = a.k_new != nullptr;
@@ -114,24 +141,32 @@ __device__ __forceinline__ void decode_body(const A& a) {
     if (k1 > nkeys) k1 = nkeys;
     if constexpr (A::RAGGED) {
         if (k0 >= k1) {                                        // (workgroup-uniform; only under a grid sized for a longer sequence)
-            neutral_record<T>(a, bh, split, tid);
+#pragma unroll
+            for (int x = 0; x < Q; ++x) {
+                if (x < nq) neutral_record<T>(a, bh0 + x, split, tid);
+            }
             return;
         }
     }
 
     int col[R];
     bool dok[R], vok[R];
-    P qp[R], acc[R];
+    P qp[Q][R], acc[Q][R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         col[r] = (c + r * G) * N;
         dok[r] = col[r] < a.D;
         vok[r] = col[r] < a.Dv;
-        qp[r] = dok[r] ? *reinterpret_cast<const P*>(q + col[r]) : P(0);
-        acc[r] = P(0);
+#pragma unroll
+        for (int x = 0; x < Q; ++x) {                          // (a state beyond nq keeps a zero query and is never written)
+            qp[x][r] = dok[r] && x < nq ? *reinterpret_cast<const P*>(q + x * a.sq[1] + col[r]) : P(0);
+            acc[x][r] = P(0);
+        }
     }
     const T scale = (T)a.scale;
-    T m = (T)-INFINITY, l = (T)0;
+    T m[Q], l[Q];
+#pragma unroll
+    for (int x = 0; x < Q; ++x) { m[x] = (T)-INFINITY; l[x] = (T)0; }
 
     for (int64_t base = k0; base < k1; base += (int64_t)U * slots) {          // (workgroup-uniform trip count)
         P kp[U][R], vp[U][R];
@@ -156,75 +191,89 @@ __device__ __forceinline__ void decode_body(const A& a) {
                 }
             }
         }
-        T s[U];
-        T mx = m;
+        // (the loaded rows are shared; what follows is per query)
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            T d = (T)0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) d = dot_pack(qp[r], kp[u][r], d);
-            for (int o = G >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-            s[u] = live[u] ? d * scale : (T)-INFINITY;
-            mx = s[u] > mx ? s[u] : mx;
-        }
-        if (mx > (T)-INFINITY) {                               // (uniform over the group: it shares m and the scores)
-            const T f = Math<T>::exp_(m - mx);                 // 0 on the group's first keys (m = -inf)
-            l *= f;
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] *= f;
+        for (int x = 0; x < Q; ++x) {
+            T s[U];
+            T mx = m[x];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const T p = Math<T>::exp_(s[u] - mx);          // 0 for a key that is not live
-                l += p;
+                T d = (T)0;
 #pragma unroll
-                for (int r = 0; r < R; ++r) acc[r] += p * vp[u][r];
+                for (int r = 0; r < R; ++r) d = dot_pack(qp[x][r], kp[u][r], d);
+                for (int o = G >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+                s[u] = live[u] ? d * scale : (T)-INFINITY;
+                mx = s[u] > mx ? s[u] : mx;
             }
-            m = mx;
+            if (mx > (T)-INFINITY) {                           // (uniform over the group: it shares m and the scores)
+                const T f = Math<T>::exp_(m[x] - mx);          // 0 on the group's first keys (m = -inf)
+                l[x] *= f;
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[x][r] *= f;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const T p = Math<T>::exp_(s[u] - mx);      // 0 for a key that is not live
+                    l[x] += p;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) acc[x][r] += p * vp[u][r];
+                }
+                m[x] = mx;
+            }
         }
     }
 
     // the groups of the wave meet: a fixed exchange tree; group 0 holds the wave's result
     for (int o = G; o < 64; o <<= 1) {
-        const T m2 = __shfl_xor(m, o, 64), l2 = __shfl_xor(l, o, 64);
-        P acc2[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) acc2[r] = xor_pack(acc[r], o);
-        const T mx = m2 > m ? m2 : m;
-        if (mx > (T)-INFINITY) {
-            const T f1 = Math<T>::exp_(m - mx), f2 = Math<T>::exp_(m2 - mx);
-            l = l * f1 + l2 * f2;
+        for (int x = 0; x < Q; ++x) {
+            const T m2 = __shfl_xor(m[x], o, 64), l2 = __shfl_xor(l[x], o, 64);
+            P acc2[R];
 #pragma unroll
-            for (int r = 0; r < R; ++r) acc[r] = acc[r] * f1 + acc2[r] * f2;
-            m = mx;
+            for (int r = 0; r < R; ++r) acc2[r] = xor_pack(acc[x][r], o);
+            const T mx = m2 > m[x] ? m2 : m[x];
+            if (mx > (T)-INFINITY) {
+                const T f1 = Math<T>::exp_(m[x] - mx), f2 = Math<T>::exp_(m2 - mx);
+                l[x] = l[x] * f1 + l2 * f2;
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[x][r] = acc[x][r] * f1 + acc2[r] * f2;
+                m[x] = mx;
+            }
         }
     }
     if (grp == 0) {
-        if (c == 0) { s_m[wave] = m; s_l[wave] = l; }
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if (vok[r]) *reinterpret_cast<P*>(&s_acc[wave][col[r]]) = acc[r];
+        for (int x = 0; x < Q; ++x) {
+            if (c == 0) { s_m[x][wave] = m[x]; s_l[x][wave] = l[x]; }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (vok[r]) *reinterpret_cast<P*>(&s_acc[x][wave][col[r]]) = acc[x][r];
+            }
         }
     }
     __syncthreads();
     // the waves meet in wave order; thread x owns column x of the result (every split that gets here holds at least one live
     // key, so the maximum is finite; a wave without keys has m = -inf and weighs 0)
     if (tid < a.Dv) {
-        T mx = s_m[0];
 #pragma unroll
-        for (int w = 1; w < WAVES; ++w) mx = s_m[w] > mx ? s_m[w] : mx;
-        T lsum = (T)0, asum = (T)0;
+        for (int x = 0; x < Q; ++x) {
+            if (x >= nq) break;
+            T mx = s_m[x][0];
 #pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            const T f = Math<T>::exp_(s_m[w] - mx);
-            lsum += s_l[w] * f;
-            asum += s_acc[w][tid] * f;
-        }
-        if (a.splits == 1) {
-            static_cast<T*>(a.o)[b * a.so[0] + h * a.so[1] + tid] = asum / lsum;
-        } else {
-            T* rec = static_cast<T*>(a.ws) + ((int64_t)bh * a.splits + split) * (a.Dv + 2);
-            if (tid == 0) { rec[0] = mx; rec[1] = lsum; }
-            rec[2 + tid] = asum;
+            for (int w = 1; w < WAVES; ++w) mx = s_m[x][w] > mx ? s_m[x][w] : mx;
+            T lsum = (T)0, asum = (T)0;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) {
+                const T f = Math<T>::exp_(s_m[x][w] - mx);
+                lsum += s_l[x][w] * f;
+                asum += s_acc[x][w][tid] * f;
+            }
+            if (a.splits == 1) {
+                static_cast<T*>(a.o)[b * a.so[0] + (h0 + x) * a.so[1] + tid] = asum / lsum;
+            } else {
+                T* rec = static_cast<T*>(a.ws) + ((int64_t)(bh0 + x) * a.splits + split) * (a.Dv + 2);
+                if (tid == 0) { rec[0] = mx; rec[1] = lsum; }
+                rec[2 + tid] = asum;
+            }
         }
     }
 }

@@ -31,6 +31,7 @@ from . import batching as _bt
 from . import conv as _cv
 from . import decoding as _dc
 from . import dropout as _dp
+from . import gqa as _gq
 from . import indexing as _ix
 from . import norm as _nm
 from . import ragged as _rg
@@ -2218,6 +2219,174 @@ def ragged_advance(picked, lens, start, done, out, cur, u_all=None, u_cur=None, 
         u_cur[...] = asarray(h_u)
     if isinstance(lens, _rg.Lengths):
         lens.host[:] = h_lens
+
+
+# ---------------------------------------------------------------------- kernels: grouped-query attention (csrc/tnn_gqa.hip)
+GQA_ROUTE = None      # tests / probes: "native" or "composed" overrides the planner's choice (gqa.py)
+
+
+def _gqa_plan(q, k, v, causal, scale, route):
+    return _gq.plan_gqa_attention(q.shape, k.shape, v.shape, causal, scale, native=_lib.get().has_gqa, route=route or GQA_ROUTE)
+
+
+def _gqa_expand(x, group, axis=2):
+    """k or v with every head repeated `group` times along the head axis: head h of the result is head h // group."""
+    return x if group == 1 else _np_repeat(x, group, axis)
+
+
+def gqa_attention(q, k, v, causal=False, scale=None, route=None):
+    """(o, lse) of grouped-query attention in layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] ->
+    o [B, Tq, H, Dv], lse [B, H, Tq]; query head h reads key / value head h // (H / Hkv) (gqa.py: the checks, the routes).
+    Native: ONE tnn_gqa_fwd launch, k and v are never expanded; composed: k and v repeated over the group, then attention()
+    on its composed route."""
+    dt, (q, k, v) = _attn_operands(q, k, v)
+    plan = _gqa_plan(q, k, v, causal, scale, route)
+    if plan.empty():
+        return _attn_empty(plan, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        lse = DeviceArray._new(plan.lse_shape, dt)
+        _lib.get().gqa_fwd(q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr, *plan.geometry(),
+                           _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
+        return out, lse
+    return attention(q, _gqa_expand(k, plan.group), _gqa_expand(v, plan.group), plan.causal, plan.scale, "bthd", "composed")
+
+
+def gqa_attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, route=None, need_dq=True, dq_out=None):
+    """(dq, delta) of gqa_attention, as attention_bwd_q: delta [B, H, Tq] is what gqa_attention_bwd_kv reads; need_dq=False:
+    only delta.  Native: ONE tnn_gqa_bwd_q launch."""
+    dt, (q, k, v, o, do, lse) = _attn_operands(q, k, v, o, do, lse)
+    plan = _gqa_plan(q, k, v, causal, scale, route)
+    _attn_bwd_check(plan, o.shape, lse, "gqa_attention_bwd_q")
+    if do.shape != plan.out_shape:
+        do = do._broadcast_to(plan.out_shape)
+    if plan.empty():
+        return (zeros(q.shape, dt) if need_dq else None), zeros(plan.lse_shape, dt)
+    if plan.route == "native":
+        dq = None
+        if need_dq:
+            dq = _attn_dest(dq_out, q.shape, dt)
+            if dq is None:
+                dq = DeviceArray._new(q.shape, dt)
+        delta = DeviceArray._new(plan.lse_shape, dt)
+        _lib.get().gqa_bwd_q(q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, None if dq is None else dq._ptr, delta._ptr,
+                             *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale,
+                             int(plan.causal), delta._code())
+        return dq, delta
+    return attention_bwd_q(q, _gqa_expand(k, plan.group), _gqa_expand(v, plan.group), o, do, lse, plan.causal, plan.scale, "bthd",
+                           "composed", need_dq)
+
+
+def gqa_attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, route=None, need_dk=True, need_dv=True,
+                         dk_out=None, dv_out=None):
+    """(dk, dv) of gqa_attention with the shapes of k and v: the sums over every key / value head's group of query heads.
+    Native: ONE tnn_gqa_bwd_kv launch (it must follow gqa_attention_bwd_q on the stream: it reads that call's delta) — one
+    workgroup per (b, key / value head, key block) adds the group's heads in ascending order and writes once.  Composed:
+    attention_bwd_kv on k and v repeated over the group, then a sum over the group axis."""
+    dt, (q, k, v, do, lse, delta) = _attn_operands(q, k, v, do, lse, delta)
+    plan = _gqa_plan(q, k, v, causal, scale, route)
+    if tuple(lse.shape) != plan.lse_shape or tuple(delta.shape) != plan.lse_shape:
+        raise ValueError("gqa_attention_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
+                         % (tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
+    if do.shape != plan.out_shape:
+        do = do._broadcast_to(plan.out_shape)
+    if not need_dk and not need_dv:
+        return None, None
+    if plan.empty():
+        return (zeros(k.shape, dt) if need_dk else None), (zeros(v.shape, dt) if need_dv else None)
+    if plan.route == "native":
+        dk = dv = None
+        if need_dk:
+            dk = _attn_dest(dk_out, k.shape, dt)
+            if dk is None:
+                dk = DeviceArray._new(k.shape, dt)
+        if need_dv:
+            dv = _attn_dest(dv_out, v.shape, dt)
+            if dv is None:
+                dv = DeviceArray._new(v.shape, dt)
+        _lib.get().gqa_bwd_kv(q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, None if dk is None else dk._ptr,
+                              None if dv is None else dv._ptr, *plan.geometry(),
+                              _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale, int(plan.causal), lse._code())
+        return dk, dv
+    dk, dv = attention_bwd_kv(q, _gqa_expand(k, plan.group), _gqa_expand(v, plan.group), do, lse, delta, plan.causal, plan.scale,
+                              "bthd", "composed", need_dk, need_dv)
+    fold = lambda g, w: g.reshape(plan.B, plan.Tk, plan.Hkv, plan.group, w).sum(axis=3)
+    return (None if dk is None else fold(dk, plan.D)), (None if dv is None else fold(dv, plan.Dv))
+
+
+def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=None, scale=None, layout="bthd", route=None,
+               splits=None):
+    """o [B, H, Dv] for ONE query per (batch, query head) over the live rows of caches that hold Hkv heads (gqa.py); query
+    head h reads key / value head h // (H / Hkv).  q [B, H, D]; k_new [B, Hkv, D], v_new [B, Hkv, Dv].
+        length=   a host integer shared by the batch, as attention_decode (with k_new / v_new the row is written into cache
+                  row `length` IN PLACE and the keys are [0, length]; without, [0, length))
+        lens=     a ragged.Lengths or a dense int64 device array [B], read on the device, as attention_decode_ragged (k_new
+                  and v_new are required; a length outside [0, Tmax) gives zeros and leaves the caches untouched)
+    Native: ONE tnn_gqa_decode_attn / tnn_gqa_ragged_decode_attn call: a workgroup serves all H / Hkv queries of a key / value
+    head from one read of each K / V row; the ragged call's arguments are fixed by the shapes, so it can be captured.
+    Composed: the append by a slice assignment, then the composed attention over the live prefix repeated over the group;
+    with lens= a loop over the sequences on the host, which raises inside an open capture."""
+    what = "gqa_decode"
+    if (k_new is None) != (v_new is None):
+        raise ValueError("%s: k_new and v_new come together or not at all" % what)
+    if (length is None) == (lens is None):
+        raise ValueError("%s: give length= (a host integer shared by the batch) or lens= (one per sequence), not both" % what)
+    ragged = lens is not None
+    append = k_new is not None
+    if ragged and not append:
+        raise ValueError("%s: with lens= k_new and v_new are required (the step appends its row)" % what)
+    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
+    dt = cands[0] if cands else _default_float
+    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
+    q = asarray(q)._as_float(dt)._contig()
+    if append:
+        k_new, v_new = asarray(k_new)._as_float(dt)._contig(), asarray(v_new)._as_float(dt)._contig()
+    ld = _ragged_state(lens, what, "lens") if ragged else None
+    lib = _lib.get()
+    plan = _gq.plan_gqa_decode(q.shape, k_cache.shape, v_cache.shape, length, append, k_new.shape if append else None,
+                               v_new.shape if append else None, scale, layout, splits, ld.shape if ragged else None,
+                               native=lib.has_gqa, float_ok=dt in (np.dtype(np.float32), np.dtype(np.float64)),
+                               route=route or GQA_ROUTE)
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        nbytes = plan.workspace_bytes(dt.itemsize)
+        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+        if ragged:
+            lib.gqa_ragged_decode_attn(q._ptr, k_new._ptr, v_new._ptr, k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
+                                       ld._ptr, *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
+        else:
+            lib.gqa_decode_attn(q._ptr, _ptr_of(k_new), _ptr_of(v_new), k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
+                                *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
+        return out
+    if ragged:
+        if _lib.capturing:
+            raise RuntimeError("%s (composed route) loops over the sequences with host lengths, which a graph capture cannot do"
+                               % what)
+        host = _ragged_mirror(lens, what)
+        out = zeros(plan.out_shape, dt)
+        for b in range(plan.B):
+            if not 0 <= int(host[b]) < plan.Tmax:
+                continue                                       # zeros, the caches untouched
+            one = slice(b, b + 1)
+            out[one] = gqa_decode(q[one], k_cache[one], v_cache[one], int(host[b]), k_new[one], v_new[one], scale=plan.scale,
+                                  layout=layout, route="composed")
+        return out
+    n, b, h = plan.keys, plan.B, plan.H
+    if layout == "bthd":
+        if append:
+            k_cache[:, plan.length] = k_new
+            v_cache[:, plan.length] = v_new
+        o, _ = attention(q.reshape(b, 1, h, plan.D), _gqa_expand(k_cache[:, :n], plan.group, 2),
+                         _gqa_expand(v_cache[:, :n], plan.group, 2), False, plan.scale, "bthd", "composed")
+    else:
+        if append:
+            k_cache[:, :, plan.length] = k_new
+            v_cache[:, :, plan.length] = v_new
+        o, _ = attention(q.reshape(b, h, 1, plan.D), _gqa_expand(k_cache[:, :, :n], plan.group, 1),
+                         _gqa_expand(v_cache[:, :, :n], plan.group, 1), False, plan.scale, "bhtd", "composed")
+    return o.reshape(plan.out_shape)
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)

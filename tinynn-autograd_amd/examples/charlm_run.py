@@ -63,8 +63,8 @@ def build(args):
     fused = not args.composed
     drop = args.dropout
     net = Net([Embedding(args.vocab, args.width, max_len=args.seq, fused=fused, dropout=drop),
-               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop),
-               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     loss_layer = CrossEntropyLoss(fused=fused)
     return Model(net=net, loss=loss_layer, optimizer=make_optimizer(args)), loss_layer
@@ -157,6 +157,8 @@ def parse(argv=None):
     parser.add_argument("--vocab", default=16, type=int)
     parser.add_argument("--width", default=32, type=int)
     parser.add_argument("--heads", default=4, type=int)
+    parser.add_argument("--kv-heads", dest="kv_heads", default=None, type=int, metavar="N",
+                        help="grouped-query attention: N key / value heads shared by the --heads query heads (a divisor of it)")
     parser.add_argument("--period", default=4, type=int)
     parser.add_argument("--seed", default=0, type=int)
     parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")

@@ -19,7 +19,10 @@ ONE small launch (device_array.ragged_advance) advances all of it.  No argument 
 so `capture=True` records the step once (graph.capture) and replays it: one graph launch per token instead of one Python
 dispatch per kernel.  Without these arguments the path above runs, bit for bit.
 
-Out of scope: grouped-query heads, chunked prefill (it needs a bottom-right causal rule), top-p, bf16, and skipping the work
+Grouped-query heads need no concept here: a layer built with kv_heads= calls LayerCache.check and fill with its key / value
+head count and runs the grouped decode ops, whose ragged form has fixed arguments and is captured like the multi-head one.
+
+Out of scope: chunked prefill (it needs a bottom-right causal rule), top-p, bf16, and skipping the work
 of sequences that have ended (they go on emitting the pad token; `stop_every` ends the loop once ALL have ended).
 """
 
