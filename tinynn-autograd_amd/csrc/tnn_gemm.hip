@@ -9,12 +9,13 @@
 
 #include "tnn_internal.h"
 #include "tnn_dispatch.h"
+#include "tnn_tile_order.h"
 #include "tnn_p2p.h"
 #include "tnn_head_stats.h"
 
 namespace {
 
-#include "tnn_gemm_args.h"    // GemmArgs, EPI_*, apply_epilogue / finish_epilogue, xcd_remap, small_tile_coords
+#include "tnn_gemm_args.h"    // GemmArgs, SmallFast, EPI_*, apply_epilogue / finish_epilogue, xcd_remap, small_tile_coords
 #include "tnn_gemm_tiled.h"   // gemm_f32_mfma_kernel, splitk_reduce_kernel
 #include "tnn_gemm_adam.h"    // AdamEpi, adam_apply*, adam_flat_range, adam_flat_blocks
 #include "tnn_gemm_small.h"   // TnFrag, tn_batches, small_tile, small_tile_fast, dw_tile_wide, gemm_small_f32_kernel
@@ -72,6 +73,7 @@ void small_geometry(GemmArgs& g) {
     g.tiles_n = (int)((g.N + 15) / 16);
     g.splits = 1;
     g.ws = nullptr;
+    g.ord = tnn::tile_order(g.tiles_m, g.tiles_n, 0, 0);
 }
 
 // 32-bit offsets of the TN buffer loads (TnFrag in tnn_gemm_small.h)
@@ -79,16 +81,16 @@ inline bool tn_extents_ok(const GemmArgs& g) {
     return g.K * g.lda * 4 < (int64_t(1) << 31) && g.K * g.ldb * 4 < (int64_t(1) << 31);
 }
 
-// XCD-aware cut of a 16 x 16 tile grid (GemmArgs::xg_m / xg_n): the one with the smallest operand footprint per XCD
+// XCD-aware cut of a tile grid (GemmArgs::ord): the one with the smallest operand footprint per XCD, or none
 void pick_xcd_cut(GemmArgs& g) {
-    g.xg_m = g.xg_n = 0;
-    int best = 0;
+    int xg_m = 0, xg_n = 0, best = 0;
     for (int xm = 1; xm <= 8; xm *= 2) {
         const int xn = 8 / xm;
         if (g.tiles_m % xm || g.tiles_n % xn) continue;
         const int cost = g.tiles_m / xm + g.tiles_n / xn;
-        if (!best || cost < best) { best = cost; g.xg_m = xm; g.xg_n = xn; }
+        if (!best || cost < best) { best = cost; xg_m = xm; xg_n = xn; }
     }
+    g.ord = tnn::tile_order(g.tiles_m, g.tiles_n, xg_m, xg_n);
 }
 
 // the mid-size kernel takes 16-B loads on its K-contiguous operands: alignment, ld % 4 == 0, K % 4 == 0, extents below 2 GiB
@@ -113,6 +115,31 @@ bool small_fast_ok(const GemmArgs& g, int transA, int transB) {
     return (!transA || transB) && mid_ok(g, transA, transB);      // (the same operand conditions as the mid-size kernel)
 }
 
+// GemmArgs::f, what small_tile_fast would otherwise derive per wave: the same 32-bit expressions, evaluated once.
+// akc / bkc: K is the contiguous axis of A / of B (with_layout).  After set_head, for a launch small_fast_ok has passed.
+void fill_small_fast(GemmArgs& g, bool akc, bool bkc) {
+    SmallFast& f = g.f;
+    f.A = g.A; f.B = g.B;
+    f.a_bytes = (uint32_t)(((akc ? g.M : g.K) - 1) * g.lda + (akc ? g.K : g.M)) * 4u;
+    f.b_bytes = (uint32_t)(((bkc ? g.N : g.K) - 1) * g.ldb + (bkc ? g.K : g.N)) * 4u;
+    f.lda4 = (uint32_t)g.lda * 4u; f.ldb4 = (uint32_t)g.ldb * 4u;
+    f.M = (uint32_t)g.M; f.N = (uint32_t)g.N; f.K = (uint32_t)g.K;
+    f.nchunks = (int)((g.K + 15) / 16);
+    f.e_ptr = nullptr; f.e_bytes = 0u; f.e_ld4 = 0u;
+    if (g.epi == EPI_BIAS_ACT) {
+        f.e_ptr = g.bias; f.e_bytes = (uint32_t)g.N * 4u;
+    } else if (g.epi == EPI_MASK) {
+        f.e_ptr = g.Y; f.e_bytes = (uint32_t)((g.M - 1) * g.ldy + g.N) * 4u; f.e_ld4 = (uint32_t)g.ldy * 4u;
+    } else if (g.beta != 0.f) {
+        f.e_ptr = g.C; f.e_bytes = (uint32_t)((g.M - 1) * g.ldc + g.N) * 4u; f.e_ld4 = (uint32_t)g.ldc * 4u;
+    }
+    if (f.e_ptr == nullptr) f.e_bytes = 0u;
+    const bool head = g.head_z != nullptr && g.head_w != nullptr;
+    f.head_w = head ? g.head_w : nullptr;
+    f.h_bytes = head ? (uint32_t)g.N * (uint32_t)g.head_c * 4u : 0u;
+    f.hc4 = (uint32_t)g.head_c * 4u;
+}
+
 template <int WAVES>
 int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
     small_geometry(g);
@@ -120,6 +147,7 @@ int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
     hipStream_t s = tnn::stream();
     const bool fast = small_fast_ok(g, transA, transB);
     pick_xcd_cut(g);
+    if (fast) fill_small_fast(g, !transA, transB != 0);
     with_layout(transA, transB, [&](auto akc, auto bkc) {
         tnn::with_flag(fast, [&](auto f) {
             hipLaunchKernelGGL((gemm_small_f32_kernel<decltype(akc)::value, decltype(bkc)::value, WAVES, decltype(f)::value>), grid,
@@ -131,10 +159,11 @@ int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
 }
 
 bool use_small_path(const GemmArgs& g) {
-    if (const char* e = getenv("TNN_GEMM_SMALL")) return atoi(e) != 0;
+    int64_t tiles = ((g.M + 15) / 16) * ((g.N + 15) / 16);
+    // (the latency kernels' tile order divides by a 16-bit reciprocal, tnn_tile_order.h: a larger grid takes the tiled kernel)
+    if (const char* e = getenv("TNN_GEMM_SMALL")) return atoi(e) != 0 && tiles <= tnn::kTileOrderMaxTiles;
     if (getenv("TNN_GEMM_CFG")) return false;
     double flop = 2.0 * (double)g.M * (double)g.N * (double)g.K;
-    int64_t tiles = ((g.M + 15) / 16) * ((g.N + 15) / 16);
     // measured on the MNIST net's layers (whole step, one GPU): bs 256 36 us; bs 512 70 us with the tiled kernel (205 MFLOP in 32
     // tiles of 64 x 64 + split-K + its reduce launch) against 57 us here; bs 1024 77 / 76 us — the switch-over sits at the
     // largest product of the bs-1024 step (2 x 1024 x 784 x 256 = 411 MFLOP)
@@ -447,6 +476,7 @@ int tnn_dense_bwd(int64_t rows, int64_t n_in, int64_t n_out, const void* x, cons
             int nchunks = (int)((std::max(gw.K, gx.K) + 15) / 16);
             hipStream_t s = tnn::stream();
             const bool fast = small_fast_ok(gw, 1, 0) && small_fast_ok(gx, 0, 1);
+            if (fast) { fill_small_fast(gw, false, false); fill_small_fast(gx, true, true); }
 #define TNN_BWD_SMALL(W)                                                                                             \
     do {                                                                                                             \
         if (fast) hipLaunchKernelGGL((dense_bwd_small_kernel<W, true>), n_dw + n_dx, W * 64, 0, s, gw, (float*)db, gx, n_dw); \
@@ -683,6 +713,7 @@ int tnn_dense_fwd_head_partials_stats(int64_t M, int64_t N, int64_t K, const voi
     set_head(g, head_w, head_z, head_c);
     small_geometry(g);                                     // (N % 16 == 0 here)
     pick_xcd_cut(g);
+    fill_small_fast(g, true, false);
     tnn::p2p::LaunchCtx ctx = {};
     if (exchange == 2) {
         // DEFERRED exchange (round 6): this launch has no statistics tail at all — the plain forward with its partial logits —

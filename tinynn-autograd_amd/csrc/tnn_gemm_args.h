@@ -8,6 +8,22 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum { EPI_AXPBY = 0, EPI_BIAS_ACT = 1, EPI_MASK = 2, EPI_ADAM = 3 };
 
+// What small_tile_fast derives from GemmArgs in front of its first request, derived ONCE by the host instead (fill_small_fast
+// in tnn_gemm.hip): none of it depends on data, and per wave it was ~130 scalar instructions, a chain of kernel-uniform selects
+// and a second and third argument fetch.  One contiguous block behind GemmArgs::ord, so the prologue is one group of scalar
+// loads, one wait, and the lanes' offset arithmetic.
+struct SmallFast {
+    uint32_t a_bytes, b_bytes;     // extents of the A / B buffer resources
+    uint32_t lda4, ldb4;           // leading dimensions in bytes
+    uint32_t M, N, K;
+    int nchunks;                   // ceil(K / 16)
+    // the epilogue's operand (bias / mask source Y / old C, or none: NULL and 0 bytes, every offset reads 0): element
+    // (row, col) at byte row * e_ld4 + col * 4 (a bias has e_ld4 == 0)
+    uint32_t e_bytes, e_ld4;
+    uint32_t h_bytes, hc4;         // head_w's extent (0: no partial logits) and head_c * 4
+    const float *A, *B, *e_ptr, *head_w;
+};
+
 struct GemmArgs {
     const float* A;
     const float* B;
@@ -24,10 +40,11 @@ struct GemmArgs {
     int splits;
     float* ws;             // [splits, M, N] partial sums when splits > 1
     int tiles_m, tiles_n;
-    // small/latency kernel: XCD-aware tile order.  Workgroup b runs on XCD b % 8 and each XCD has a private L2; with
-    // xg_m x xg_n == 8 the tile grid is cut into 8 rectangles of (tiles_m / xg_m) x (tiles_n / xg_n) tiles, one per XCD,
-    // so an L2 fills only the operand rows / columns of its rectangle.  0 = plain order.
-    int xg_m, xg_n;
+    // small/latency kernels: the tile of workgroup b (tnn_tile_order.h).  XCD-aware where pick_xcd_cut finds a cut: the tile
+    // grid is cut into 8 rectangles, one per XCD, so an L2 fills only the operand rows / columns of its rectangle; otherwise
+    // the plain column-major order (small_geometry).
+    tnn::TileOrder ord;
+    SmallFast f;           // FAST form of the small/latency kernel only
     // small/latency kernel only (tnn_dense_fwd_head_partials): the NEXT (classifier) layer's weights head_w [N, head_c]
     // and where this tile's share of that layer's logits goes, head_z [tiles_n][M][head_c]
     const float* head_w;
@@ -103,14 +120,7 @@ __device__ __forceinline__ float finish_epilogue(const GemmArgs& g, float acc, f
 
 // tile of workgroup `block` of the latency kernels: one rectangle of the tile grid per XCD (pick_xcd_cut) or column-major
 __device__ __forceinline__ void small_tile_coords(const GemmArgs& g, const int block, int& tm, int& tn) {
-    if (g.xg_m) {
-        const int xcd = block & 7, idx = block >> 3, pm = g.tiles_m / g.xg_m, pn = g.tiles_n / g.xg_n;
-        tm = (xcd % g.xg_m) * pm + idx % pm;
-        tn = (xcd / g.xg_m) * pn + idx / pm;
-    } else {
-        tm = block % g.tiles_m;
-        tn = block / g.tiles_m;
-    }
+    tnn::tile_coords(g.ord, block, tm, tn);
 }
 
 #ifdef TNN_STEP_TRACE

@@ -24,14 +24,7 @@ __device__ __forceinline__ void mid_tile(const GemmArgs& g, float* __restrict__ 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int l31 = lane & 31, lhi = lane >> 5;
     int tm, tn;
-    if (g.xg_m) {
-        const int xcd = block & 7, idx = block >> 3, pm = g.tiles_m / g.xg_m, pn = g.tiles_n / g.xg_n;
-        tm = (xcd % g.xg_m) * pm + idx % pm;
-        tn = (xcd / g.xg_m) * pn + idx / pm;
-    } else {
-        tm = block % g.tiles_m;
-        tn = block / g.tiles_m;
-    }
+    small_tile_coords(g, block, tm, tn);
     const int64_t m0 = (int64_t)tm * 32, n0 = (int64_t)tn * 32;
     const int64_t am = m0 + l31, bn = n0 + l31;
     const bool a_ok = am < g.M, b_ok = bn < g.N;

@@ -64,14 +64,7 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     int tm, tn;
-    if (g.xg_m) {                                    // XCD-aware tile order (GemmArgs::xg_m)
-        const int xcd = block & 7, idx = block >> 3, pm = g.tiles_m / g.xg_m, pn = g.tiles_n / g.xg_n;
-        tm = (xcd % g.xg_m) * pm + idx % pm;
-        tn = (xcd / g.xg_m) * pn + idx / pm;
-    } else {
-        tm = block % g.tiles_m;
-        tn = block / g.tiles_m;
-    }
+    small_tile_coords(g, block, tm, tn);
     const int64_t m0 = (int64_t)tm * 16, n0 = (int64_t)tn * 16;
     const int64_t am = m0 + i16, bn = n0 + i16;
     const bool a_ok = am < g.M, b_ok = bn < g.N;
@@ -320,45 +313,36 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
     TNN_STEP_STAMP(g_step_trace, KID, 0);                 // the entry stamp is the first thing: a stamp behind the prologue hides it
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
+    // Everything launch-uniform arrives finished in g.f (SmallFast: extents, byte strides, the chunk count, the epilogue's
+    // operand) and the tile comes from g.ord without a division: one group of argument loads, then the lanes' own offsets.
+    const SmallFast& f = g.f;
     int tm, tn;
     small_tile_coords(g, block, tm, tn);
-    const int64_t m0 = (int64_t)tm * 16, n0 = (int64_t)tn * 16;
-    const int64_t am = m0 + i16, bn = n0 + i16;
-    const bool a_ok = am < g.M, b_ok = bn < g.N;
-    const int nchunks = (int)((g.K + 15) / 16);
-    const uint32_t K = (uint32_t)g.K, lda4 = (uint32_t)g.lda * 4u, ldb4 = (uint32_t)g.ldb * 4u;
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(g.A), 0, (uint32_t)(((AKC ? g.M : g.K) - 1) * g.lda + (AKC ? g.K : g.M)) * 4u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(g.B), 0, (uint32_t)(((BKC ? g.N : g.K) - 1) * g.ldb + (BKC ? g.K : g.N)) * 4u, 0x00020000);
+    const uint32_t m0 = (uint32_t)tm * 16u, n0 = (uint32_t)tn * 16u;
+    const uint32_t am = m0 + (uint32_t)i16, bn = n0 + (uint32_t)i16;
+    const bool a_ok = am < f.M, b_ok = bn < f.N;
+    const int nchunks = f.nchunks;
+    const uint32_t K = f.K, lda4 = f.lda4, ldb4 = f.ldb4;
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.A), 0, f.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.B), 0, f.b_bytes, 0x00020000);
     // byte offset of this lane's first element of chunk 0 (k = grp * 4), without the chunk term
-    const uint32_t a_lane = AKC ? (uint32_t)am * lda4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * lda4 + (uint32_t)am * 4u;
-    const uint32_t b_lane = BKC ? (uint32_t)bn * ldb4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * ldb4 + (uint32_t)bn * 4u;
+    const uint32_t a_lane = AKC ? am * lda4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * lda4 + am * 4u;
+    const uint32_t b_lane = BKC ? bn * ldb4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * ldb4 + bn * 4u;
     const uint32_t a_chunk = AKC ? 64u : 16u * lda4;          // bytes per 16-deep chunk
     const uint32_t b_chunk = BKC ? 64u : 16u * ldb4;
 
     const int e_r = tid >> 6, e_ln = tid & 63;
-    const int64_t e_row = m0 + (e_ln >> 4) * 4 + e_r, e_col = n0 + (e_ln & 15);   // 16x16x4 C/D layout
-    const bool e_live = tid < 256 && e_row < g.M && e_col < g.N;
-    // The epilogue's operand and wave 0's head_w fragment travel like the K loop's fragments: a buffer resource chosen by
-    // kernel-uniform selects (a NULL bias / no operand: 0 bytes long, every offset reads 0), a 32-bit byte offset, and
-    // 0xffffffff for a thread, row or unit that does not exist.  Left to pointers, each of these loads sat under its own
-    // exec-mask branch behind a 64-bit multiply-add whose register pair overlapped the load in front of it, and wave 0 of
-    // every workgroup took three dependent round trips before it requested its first fragment.  32-bit extents of C / Y:
-    // small_fast_ok.
-    const float* e_ptr = nullptr;
-    uint32_t e_bytes = 0u, e_off = 0u;
-    if (g.epi == EPI_BIAS_ACT) {
-        e_ptr = g.bias; e_bytes = (uint32_t)g.N * 4u; e_off = (uint32_t)e_col * 4u;
-    } else if (g.epi == EPI_MASK) {
-        e_ptr = g.Y; e_bytes = (uint32_t)((g.M - 1) * g.ldy + g.N) * 4u; e_off = ((uint32_t)e_row * (uint32_t)g.ldy + (uint32_t)e_col) * 4u;
-    } else if (g.beta != 0.f) {
-        e_ptr = g.C; e_bytes = (uint32_t)((g.M - 1) * g.ldc + g.N) * 4u; e_off = ((uint32_t)e_row * (uint32_t)g.ldc + (uint32_t)e_col) * 4u;
-    }
-    const __amdgpu_buffer_rsrc_t e_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e_ptr), 0, e_ptr ? e_bytes : 0u, 0x00020000);
-    const bool head_on = g.head_z != nullptr;                 // kernel-uniform
-    const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(g.head_w), 0, (head_on && g.head_w) ? (uint32_t)g.N * (uint32_t)g.head_c * 4u : 0u, 0x00020000);
+    const uint32_t e_row = m0 + (uint32_t)((e_ln >> 4) * 4 + e_r), e_col = n0 + (uint32_t)(e_ln & 15);   // 16x16x4 C/D layout
+    const bool e_live = tid < 256 && e_row < f.M && e_col < f.N;
+    // The epilogue's operand and wave 0's head_w fragment travel like the K loop's fragments: a buffer resource (a NULL bias /
+    // no operand: 0 bytes long, every offset reads 0), a 32-bit byte offset, and 0xffffffff for a thread, row or unit that does
+    // not exist.  Left to pointers, each of these loads sat under its own exec-mask branch behind a 64-bit multiply-add whose
+    // register pair overlapped the load in front of it, and wave 0 of every workgroup took three dependent round trips before
+    // it requested its first fragment.  32-bit extents of C / Y: small_fast_ok.
+    const uint32_t e_off = e_row * f.e_ld4 + e_col * 4u;
+    const __amdgpu_buffer_rsrc_t e_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.e_ptr), 0, f.e_bytes, 0x00020000);
+    const bool head_on = f.h_bytes != 0u;                     // kernel-uniform
+    const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.head_w), 0, f.h_bytes, 0x00020000);
     const int swid = __builtin_amdgcn_readfirstlane(wid);     // the branches below are scalar: no exec mask around a load
     float e_pre = 0.f;
     float head_pre[4] = {0.f, 0.f, 0.f, 0.f};                 // wave 0: head_w[n0 + 4 grp + j][i16], the B fragment of the partial-logit product
@@ -372,14 +356,14 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
             // one vector multiply for the lane's first unit (opaque, so that it is not fused with the add: a 32-bit multiply-add
             // comes out as v_mad_u64_u32 on a register pair whose upper half is the load in flight in front of it — a full
             // wait for nothing), the unit step added as a scalar
-            const uint32_t unit0 = (uint32_t)n0 + 4u * (uint32_t)grp, hc4 = (uint32_t)g.head_c * 4u;
+            const uint32_t unit0 = n0 + 4u * (uint32_t)grp, hc4 = f.hc4;
             uint32_t unit_b = unit0 * hc4;
             asm("" : "+v"(unit_b));
             const uint32_t off0 = unit_b + (uint32_t)i16 * 4u;
-            const bool cls_ok = i16 < g.head_c;
+            const bool cls_ok = (uint32_t)i16 * 4u < hc4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool ok = cls_ok & (unit0 + (uint32_t)j < (uint32_t)g.N);
+                const bool ok = cls_ok & (unit0 + (uint32_t)j < f.N);
                 uint32_t off = ok ? off0 + (uint32_t)j * hc4 : OOB;
                 asm("" : "+v"(off));
                 head_pre[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(h_rsrc, off, 0, 0));
@@ -455,10 +439,10 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
         for (int w = 0; w < WAVES; ++w) s += red[w][e_r][e_ln];
         if (e_live) {
             e_val = finish_epilogue(g, s, e_pre);
-            g.C[e_row * g.ldc + e_col] = e_val;
+            g.C[(int64_t)e_row * g.ldc + e_col] = e_val;
         }
     }
-    if (colsum != nullptr && tm == 0 && tid < 16 && n0 + tid < g.N) {
+    if (colsum != nullptr && tm == 0 && tid < 16 && n0 + (uint32_t)tid < f.N) {
         float s = 0.f;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) s += (bsum[w][tid] + bsum[w][16 + tid]) + (bsum[w][32 + tid] + bsum[w][48 + tid]);
@@ -481,7 +465,7 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
             if (i16 < g.head_c) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int64_t row = m0 + 4 * grp + q;
+                    const int64_t row = (int64_t)m0 + 4 * grp + q;
                     if (row < g.M) {
                         float* dst = g.head_z + ((int64_t)tn * g.M + row) * g.head_c + i16;
                         if constexpr (SYS_HEADZ) tnn::p2p::store_sys(reinterpret_cast<uint32_t*>(dst), __float_as_uint(hacc[q]));
@@ -500,8 +484,10 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_small_f32_kernel(GemmArgs g, 
     __shared__ float bsum[WAVES][64];
     if constexpr (FAST) {
         __shared__ __attribute__((aligned(16))) float head_lds[16 * 20];   // tnn_dense_fwd_head_partials: the finished tile
-        if (g.bump != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *g.bump += 1u;     // single writer; read by the NEXT launch
         small_tile_fast<AKC, BKC, WAVES>(g, colsum, (int)blockIdx.x, red, bsum, head_lds);
+        // single writer; read by the NEXT launch only, so it stands behind the tile: in front it was an argument fetch, a wait
+        // and an exec-mask branch on every wave's way to its first request
+        if (g.bump != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *g.bump += 1u;
     } else {
         small_tile<AKC, BKC, WAVES>(g, colsum, (int)blockIdx.x, red, bsum);
     }

@@ -181,9 +181,6 @@ __global__ __launch_bounds__(512) void dense_fwd_rowpanel_head_kernel(RowPanelAr
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     const int m0 = 16 * (int)blockIdx.x, n0 = 16 * wid;
-    if constexpr (!MERGE) {
-        if (g.bump != nullptr && blockIdx.x == 0 && tid == 0) *g.bump += 1u;       // single writer; read by the NEXT launch
-    }
     const uint32_t K = (uint32_t)g.K, lda4 = (uint32_t)g.lda * 4u, ldb4 = (uint32_t)g.ldb * 4u;
     const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(g.A), 0, (uint32_t)(((int64_t)(g.M - 1) * g.lda + g.K) * 4), 0x00020000);
@@ -309,6 +306,8 @@ __global__ __launch_bounds__(512) void dense_fwd_rowpanel_head_kernel(RowPanelAr
         } else {
             g.pairs[2 * blockIdx.x] = M;
             g.pairs[2 * blockIdx.x + 1] = S;
+            // single writer; read by the NEXT launch only, so it stands at the end and not in front of the first request
+            if (g.bump != nullptr && blockIdx.x == 0) *g.bump += 1u;
         }
     }
     if constexpr (MERGE) {

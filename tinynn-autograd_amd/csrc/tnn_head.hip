@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "tnn_internal.h"
+#include "tnn_tile_order.h"
 #include "tnn_p2p.h"
 #include <mutex>
 #include <unordered_map>
@@ -356,7 +357,8 @@ struct HeadBwdArgs {
     const float* w1;                 // [n_in][H]
     float *dw1, *db1, *dx;           // [n_in][H], [H], [m][n_in]
     int n_in, tiles_in;              // tiles_in = n_in / 16
-    int xcd;                         // XCD-aware tile order (workgroup b runs on XCD b % 8)
+    int n_dw;                        // dW1 tiles: tiles_in x H / 16; the dx tiles follow them
+    tnn::TileOrder ord_dw, ord_dx;   // mlp_head_bwd_kernel: the tile of a dW / dx workgroup (tnn_tile_order.h: head_tile_orders)
     int dx_wide;                     // dx tiles of 16 rows x 32 inputs (tiles_in even).  <= 128 rows: for the MNIST net 16 + 128 + 64 = 208
                                      // workgroups instead of 272 — the 16 that were a CU's SECOND workgroup ended 1.1 us behind the rest
                                      // (profiles/r06_stepA_stamps.txt).  Row-blocked kernel: half the dx workgroups for its two slots per CU
@@ -390,28 +392,14 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     const int m = p.m;
     const bool slive = srow < m;
     const int sr = min(srow, m - 1);
-    const int n_dw = q.tiles_in * TH;
+    const int n_dw = q.n_dw;
     const int blk = (int)blockIdx.x - G;
     const bool is_dw = blk < n_dw;
     const bool wide = q.dx_wide != 0;                                 // block-uniform
     const int n_in = q.n_in;
     // tile coordinates.  dW: tm over the inputs, tn over the hidden units; dx: tm over the rows, tn over the inputs
     int tm, tn;
-    if (is_dw) {
-        if (q.xcd && q.tiles_in % 2 == 0) {          // XCD-aware order: XCD x takes inputs' half x % 2, units' quarter x / 2
-            const int xcd = blk & 7, idx = blk >> 3, pm = q.tiles_in / 2;
-            tm = (xcd & 1) * pm + idx % pm;
-            tn = (xcd >> 1) * (TH / 4) + idx / pm;
-        } else { tm = blk % q.tiles_in; tn = blk / q.tiles_in; }
-    } else {
-        const int b2 = blk - n_dw, tr = (m + 15) / 16;
-        const int tcols = wide ? q.tiles_in / 2 : q.tiles_in;        // dx tile columns (16 or 32 inputs each)
-        if (q.xcd && tr % 2 == 0 && tcols % 4 == 0 && n_dw % 8 == 0) {
-            const int xcd = b2 & 7, idx = b2 >> 3, pm = tr / 2;
-            tm = (xcd & 1) * pm + idx % pm;
-            tn = (xcd >> 1) * (tcols / 4) + idx / pm;
-        } else { tm = b2 % tr; tn = b2 / tr; }
-    }
+    tnn::tile_coords(is_dw ? q.ord_dw : q.ord_dx, is_dw ? blk : blk - n_dw, tm, tn);
     const int m0 = tm * 16, n0 = tn * ((!is_dw && wide) ? 32 : 16);
 
     // ---- every global read, up front.  The dz1 slice of a tile is itself a 16x16x4 MFMA product
@@ -919,8 +907,12 @@ __global__ __launch_bounds__(512, RB ? 4 : 2) void mlp_head_bwd_rb_kernel(HeadMA
     const int n_in = q.n_in;
     // tile coordinates.  dW: tm over the inputs, tn over the hidden units; dx: tm over the rows, tn over the inputs
     int tm, tn;
+    // (This kernel keeps the order's division formulas — the ones tnn::head_tile_orders encodes for mlp_head_bwd_kernel.  With
+    // tnn::tile_coords here the register allocator, at this kernel's 128-VGPR cap, spilled half of bias4 and reloaded it INSIDE the
+    // row-block loop behind an s_waitcnt vmcnt(0) that also drains the next block's requests: + 1.07 us per step at 1024 rows,
+    // + 0.13 us at 256, profiles/step_args_once_ab.txt.  The divisions run once per workgroup, in front of a loop of 2 - 8 blocks.)
     if (is_dw) {
-        if (q.xcd && q.tiles_in % 2 == 0) {          // XCD-aware order: XCD x takes inputs' half x % 2, units' quarter x / 2
+        if (q.tiles_in % 2 == 0) {                   // XCD-aware order: XCD x takes inputs' half x % 2, units' quarter x / 2
             const int xcd = blk & 7, idx = blk >> 3, pm = q.tiles_in / 2;
             tm = (xcd & 1) * pm + idx % pm;
             tn = (xcd >> 1) * (TH / 4) + idx / pm;
@@ -928,7 +920,7 @@ __global__ __launch_bounds__(512, RB ? 4 : 2) void mlp_head_bwd_rb_kernel(HeadMA
     } else {
         const int b2 = blk - n_dw, tr = (mt + 15) / 16;
         const int tcols = wide ? q.tiles_in / 2 : q.tiles_in;        // dx tile columns (16 or 32 inputs each)
-        if (q.xcd && tr % 2 == 0 && tcols % 4 == 0 && n_dw % 8 == 0) {
+        if (tr % 2 == 0 && tcols % 4 == 0 && n_dw % 8 == 0) {
             const int xcd = b2 & 7, idx = b2 >> 3, pm = tr / 2;
             tm = (xcd & 1) * pm + idx % pm;
             tn = (xcd >> 1) * (tcols / 4) + idx / pm;
@@ -1470,8 +1462,17 @@ bool head_bwd_generic_fits(int64_t rows, int64_t n_in, int64_t n_hidden, int64_t
            n_hidden <= 256 && n_classes >= 1 && n_classes <= 16 && n_in >= 16 && n_in % 16 == 0;
 }
 
+// widest input of the merged launch: with up to 64 row tiles its dx tiles stay within the tile order's 16-bit reciprocal
+constexpr int kHeadBwdMaxIn = 16 * (tnn::kTileOrderMaxTiles / 64);
+
 bool head_multi_fits(int64_t rows, int64_t n_hidden, int64_t n_classes, int dtype) {
     return dtype == TNN_F32 && n_classes == 10 && n_hidden == 128 && rows >= 1 && rows <= 128;
+}
+
+// the tile orders of the merged launch's two tile roles (tnn::head_tile_orders) for `tr` row tiles; returns the number of tile workgroups
+int head_bwd_orders(HeadBwdArgs& q, const int tr) {
+    q.n_dw = tnn::head_tile_orders(q.tiles_in, tr, q.dx_wide != 0, q.ord_dw, q.ord_dx);
+    return q.n_dw + tr * (q.dx_wide ? q.tiles_in / 2 : q.tiles_in);
 }
 
 int head_bwd_launch(const char* fn, const float* ext_pairs, int ext_n, bool whole_logits, int64_t m_global, int64_t rows, int64_t n_in, int64_t n_hidden, int64_t n_classes, const void* x, const void* w1,
@@ -1511,8 +1512,9 @@ int head_bwd_launch(const char* fn, const float* ext_pairs, int ext_n, bool whol
     // rows: <= 128 when the workgroups reduce the statistics themselves; with the statistics taken from memory (ext_pairs)
     // nothing couples the rows inside the launch and they are walked in blocks of 128 (<= 1024: 8 blocks)
     TNN_REQUIRE(head_multi_fits(ext_pairs ? (rows <= 1024 ? 1 : rows) : rows, n_hidden, n_classes, dtype) && n_in % 16 == 0 &&
-                    al(a) && al(w) && al(w1),
-                "%s: this head does not fit the merged form (tnn_mlp_head_fits, n_in %% 16 == 0, 16-B aligned a / w / w1)", fn);
+                    n_in <= kHeadBwdMaxIn && al(a) && al(w) && al(w1),
+                "%s: this head does not fit the merged form (tnn_mlp_head_fits, n_in %% 16 == 0 up to %d, 16-B aligned a / w / w1)", fn,
+                kHeadBwdMaxIn);
     HeadMArgs p;
     p.m = (int)rows;
     p.rpb = (int)((rows + 15) / 16);
@@ -1530,12 +1532,11 @@ int head_bwd_launch(const char* fn, const float* ext_pairs, int ext_n, bool whol
     q.x = (const float*)x; q.w1 = (const float*)w1;
     q.dw1 = (float*)dw1; q.db1 = (float*)db1; q.dx = (float*)dx;
     q.n_in = (int)n_in; q.tiles_in = (int)(n_in / 16);
-    q.xcd = 1;
     // dx tiles of 32 inputs (HeadBwdArgs::dx_wide; TNN_HEAD_DX_WIDE=0 / TNN_HEAD_DX_WIDE_RB=0: the 16-wide tiles at every row count / above 128 rows, A/B)
     static const bool dx_wide_off = getenv("TNN_HEAD_DX_WIDE") && atoi(getenv("TNN_HEAD_DX_WIDE")) == 0;
     static const bool dx_wide_rb_off = getenv("TNN_HEAD_DX_WIDE_RB") && atoi(getenv("TNN_HEAD_DX_WIDE_RB")) == 0;
     q.dx_wide = (q.tiles_in % 2 == 0 && !dx_wide_off && (rows <= 128 || !dx_wide_rb_off)) ? 1 : 0;
-    const int grid = 16 + q.tiles_in * 8 + (int)((rows + 15) / 16) * (q.dx_wide ? q.tiles_in / 2 : q.tiles_in);
+    const int grid = 16 + head_bwd_orders(q, (int)((rows + 15) / 16));
     if (xc != nullptr) {
         // data parallel, DEFERRED exchange: <= 128 rows — statistics inside as on one GPU, then exchanged; more — the panels' pairs
         // of THIS shard from memory (row-panel forward), merged, then exchanged
@@ -1594,7 +1595,7 @@ int tnn_mlp_head_fits(int64_t rows, int64_t n_hidden, int64_t n_classes, int dty
 
 int tnn_mlp_head_bwd_fits(int64_t rows, int64_t n_in, int64_t n_hidden, int64_t n_classes, int dtype, int* fits) {
     TNN_REQUIRE(fits != nullptr, "tnn_mlp_head_bwd_fits: fits is NULL");
-    *fits = ((head_multi_fits(rows, n_hidden, n_classes, dtype) && n_in % 16 == 0 && n_in >= 16) ||
+    *fits = ((head_multi_fits(rows, n_hidden, n_classes, dtype) && n_in % 16 == 0 && n_in >= 16 && n_in <= kHeadBwdMaxIn) ||
              head_bwd_generic_fits(rows, n_in, n_hidden, n_classes, dtype)) ? 1 : 0;
     return 0;
 }
