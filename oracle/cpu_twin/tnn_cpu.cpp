@@ -588,7 +588,7 @@ int tnn_softmax_nll_stats(const void* z, int64_t m, int64_t c, void* stats, int 
     FLOAT_SWITCH(dtype, "tnn_softmax_nll_stats", {
         double mx = -INFINITY;
         for (int64_t i = 0; i < m * c; ++i) mx = fmax(mx, (double)((const T*)z)[i]);
-        double s = 0;
+        long double s = 0;      // (the device sums short per-thread runs and a tree: a serial double sum is far less accurate)
         for (int64_t i = 0; i < m * c; ++i) s += exp((double)((const T*)z)[i] - mx);
         ((T*)stats)[0] = (T)mx;
         ((T*)stats)[1] = (T)s;
@@ -602,8 +602,9 @@ int tnn_lse_merge(const void* all, int n, void* stats, int dtype) {
     FLOAT_SWITCH(dtype, "tnn_lse_merge", {
         double mx = -INFINITY;
         for (int i = 0; i < n; ++i) mx = fmax(mx, (double)((const T*)all)[2 * i]);
-        double s = 0;
-        for (int i = 0; i < n; ++i) s += (double)((const T*)all)[2 * i + 1] * exp((double)((const T*)all)[2 * i] - mx);
+        long double s = 0;
+        for (int i = 0; i < n; ++i)
+            if ((double)((const T*)all)[2 * i] > -INFINITY) s += (double)((const T*)all)[2 * i + 1] * exp((double)((const T*)all)[2 * i] - mx);
         ((T*)stats)[0] = (T)mx;
         ((T*)stats)[1] = (T)s;
     });
@@ -615,15 +616,16 @@ int tnn_softmax_nll_fwd_bwd(const void* z, const void* y, int64_t m, int64_t c, 
     REQ(m > 0 && c > 0 && mg > 0, "tnn_softmax_nll_fwd_bwd: empty batch");
     RECORD(tnn_softmax_nll_fwd_bwd(z, y, m, c, mg, stats, loss_out, dz, dtype));
     FLOAT_SWITCH(dtype, "tnn_softmax_nll_fwd_bwd", {
-        double M = ((const T*)stats)[0], S = ((const T*)stats)[1], loss = 0;
+        double M = ((const T*)stats)[0], S = ((const T*)stats)[1];
+        long double loss = 0;
         for (int64_t r = 0; r < m; ++r) {
-            double q = 0;
+            long double q = 0;
             for (int64_t k = 0; k < c; ++k) q += exp((double)((const T*)z)[r * c + k] - M) * (double)((const T*)y)[r * c + k];
-            loss += (log(S) - log(q)) / (double)mg;
+            loss += (log(S) - log((double)q)) / (double)mg;
             if (dz)
                 for (int64_t k = 0; k < c; ++k) {
                     double e = exp((double)((const T*)z)[r * c + k] - M);
-                    ((T*)dz)[r * c + k] = (T)(e / S - e * (double)((const T*)y)[r * c + k] / q / (double)mg);
+                    ((T*)dz)[r * c + k] = (T)(e / S - e * (double)((const T*)y)[r * c + k] / (double)q / (double)mg);
                 }
         }
         if (loss_out) ((T*)loss_out)[0] = (T)loss;
@@ -947,6 +949,7 @@ int tnn_adam_ex(void* p, const void* g, void* m, void* v, int64_t n, double lr, 
                 void* pows, void* step_out, int dtype, int advance, const void* scalar_src, void* scalar_dst) {
     NEED_INIT();
     REQ(pows, "tnn_adam: pows state is NULL");
+    REQ((scalar_src == nullptr) == (scalar_dst == nullptr), "tnn_adam_ex: scalar_src / scalar_dst go together");
     RECORD(tnn_adam_ex(p, g, m, v, n, lr, b1, b2, eps, pows, step_out, dtype, advance, scalar_src, scalar_dst));
     if (scalar_dst) memcpy(scalar_dst, scalar_src, dtype == TNN_F64 ? 8 : 4);
     double* st = (double*)pows;
@@ -1269,6 +1272,8 @@ int tnn_allgather(const void* s, void* r, int64_t n, int dtype) {
 int tnn_softmax_nll_fused_tick(const void* z, const void* y, int64_t m, int64_t c, int64_t m_global, int sharded,
                                void* stats_out, void* loss_out, void* dz, int dtype, void* pows, double b1, double b2) {
     NEED_INIT();
+    REQ(dtype == TNN_F32 || dtype == TNN_F64, "tnn_softmax_nll_fused_tick: dtype %d", dtype);
+    REQ(m > 0 && c > 0, "tnn_softmax_nll_fused_tick: empty batch");
     REQ(m_global == m, "cpu twin: one-rank group only");
     REQ(((c <= 16) || m * c <= (dtype == TNN_F32 ? 4096 : 2048)) && m <= 1024, "tnn_softmax_nll_fused_tick: does not fit one workgroup");
     RECORD(tnn_softmax_nll_fused_tick(z, y, m, c, m_global, sharded, stats_out, loss_out, dz, dtype, pows, b1, b2));

@@ -39,6 +39,11 @@ __device__ __forceinline__ void nll_rows_body(const T* __restrict__ z, const T* 
     }
     T e[CMAX], ey[CMAX];
     double mi = -INFINITY, si = 0.0, li = 0.0, ui = 1.0;
+    // f64 arrays: L is summed RELATIVE to the maxima (log u_i + (m_i - wave max), then wave sum + rows * (wave max - M)) and
+    // the loss is log S - L / m.  Carrying the absolute m_i through L and cancelling it against M at the end made the f64
+    // loss lose |M| eps: at logits near 30 it left the bound of a same-precision evaluation (1.4 x at 65 x 10).  f32 arrays
+    // accumulate in f64, where |M| 2^-53 is nothing next to their own eps: they keep the shorter dependency chain.
+    constexpr bool kRelL = sizeof(T) == 8;
     const bool live = tid < m;
     // f32 batches above 128 rows: z and y are flat [m][c] arrays, so the workgroup first copies them into LDS with coalesced
     // 16-B loads (5 per thread at 1024 x 10) and every thread then picks its row there.  Row-wise from global memory each
@@ -91,14 +96,14 @@ __device__ __forceinline__ void nll_rows_body(const T* __restrict__ z, const T* 
             u += (double)ey[k];
         }
         mi = (double)mx; si = s; ui = u;
-        li = nll_log((T)u) + (double)mx;
+        li = kRelL ? nll_log((T)u) : nll_log((T)u) + (double)mx;
     }
     // one combined reduction: waves first (DPP steps — a 64-bit shuffle tree costs ~700 cycles, three of them per wave and
     // up to 16 waves sharing one CU here), then <= 16 wave triples through LDS.  All 64 lanes of every wave are active (the
     // kernel is launched with whole waves; rows beyond m carry the identities).
     double wm = wave_max_dpp(mi);
     double ws = wave_sum_dpp(live ? si * nll_exp((T)(mi - wm)) : 0.0);
-    double wl = wave_sum_dpp(li);
+    double wl = wave_sum_dpp(kRelL && live ? li + (mi - wm) : li);
     if (lane == 0) { wave_m[wid] = wm; wave_s[wid] = ws; wave_l[wid] = wl; }
     __syncthreads();
     // every lane takes wave entry (lane & 15) and a 16-lane DPP butterfly leaves M, S, L in ALL lanes: one exp per lane instead
@@ -112,6 +117,10 @@ __device__ __forceinline__ void nll_rows_body(const T* __restrict__ z, const T* 
     q = dpp_move<0x141, 0xf>((double)-INFINITY, M); M = fmax(M, q);
     q = dpp_move<0x140, 0xf>((double)-INFINITY, M); M = fmax(M, q);
     double S = rm > -INFINITY ? rs * nll_exp((T)(rm - M)) : 0.0, L = rl;
+    if constexpr (kRelL) {                 // every wave of the launch has a live row, so its maximum is finite
+        const int rows_w = m - 64 * w16 < 64 ? m - 64 * w16 : 64;
+        L = have ? rl + (double)rows_w * (rm - M) : 0.0;
+    }
     S += dpp_move<0xB1, 0xf>(0.0, S); L += dpp_move<0xB1, 0xf>(0.0, L);
     S += dpp_move<0x4E, 0xf>(0.0, S); L += dpp_move<0x4E, 0xf>(0.0, L);
     S += dpp_move<0x141, 0xf>(0.0, S); L += dpp_move<0x141, 0xf>(0.0, L);
@@ -124,6 +133,7 @@ __device__ __forceinline__ void nll_rows_body(const T* __restrict__ z, const T* 
         const Peers& P = ctx.peers;
         const int W = P.world;
         const uint32_t ep = *ctx.ag_epoch;
+        if constexpr (kRelL) L += (double)m * M;      // back to the absolute form the merged maximum is applied to
         if (tid < 2 * W)           // {M_r, S_r} to every rank and theirs back: one 8-byte tagged store per word and peer
             peer_stats[tid >> 1][tid & 1] =
                 ll_exchange2(P, ep, (tid & 1) ? (float)S : (float)M, ctx.dead, ctx.timeout_ticks);
@@ -136,7 +146,7 @@ __device__ __forceinline__ void nll_rows_body(const T* __restrict__ z, const T* 
         inv_m = inv_m_global;
         loss = ((nll_log((T)S) + M) * (double)m - L) * inv_m;   // this rank's share
     } else {
-        loss = nll_log((T)S) + M - L * inv_m;
+        loss = kRelL ? nll_log((T)S) - L * inv_m : nll_log((T)S) + M - L * inv_m;
     }
     if constexpr (kStage) {
         if (staged && dz) {                   // block-uniform: dz leaves the way z came in — through LDS, coalesced 16-B stores
