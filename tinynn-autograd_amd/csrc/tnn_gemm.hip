@@ -584,6 +584,12 @@ extern "C" __attribute__((visibility("default"))) int tnn_debug_step_trace(unsig
     TNN_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_trace), (size_t)std::min(n, 4 * 1024 * 4) * 8));
     return 0;
 }
+// [kernel id][workgroup]: wave 0's first chunk home (fwd0, fwd1, bwd0's tiles); its last chunk home is word [1] of the rows above
+extern "C" __attribute__((visibility("default"))) int tnn_debug_step_trace_first(unsigned long long* out, int n) {
+    TNN_CHECK_HIP(hipDeviceSynchronize());
+    TNN_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_trace_first), (size_t)std::min(n, 4 * 1024) * 8));
+    return 0;
+}
 #endif
 #ifdef TNN_AR_TRACE
 __attribute__((visibility("default"))) int tnn_debug_fh_trace(unsigned long long* out, int n) {

@@ -125,4 +125,5 @@ __device__ __forceinline__ void small_tile_coords(const GemmArgs& g, const int b
 
 #ifdef TNN_STEP_TRACE
 __device__ unsigned long long g_step_trace[4 * 1024 * 4];        // tnn_internal.h: TNN_STEP_STAMP
+__device__ unsigned long long g_step_trace_first[4 * 1024];      // tnn_internal.h: TNN_STEP_STAMP_VALUE (a wave 0's first chunk home)
 #endif

@@ -35,21 +35,45 @@ struct TnFrag {
 
 // The K walk of those tiles: wave `wid` (wave-uniform) owns chunks wid, wid + WAVES, ... and takes them TN_MAXC at a time:
 // load(u, c) requests chunk c into fragment slot u, for every chunk of the batch, before mma(u) — the MFMAs and column-sum
-// adds of slot u — runs for the first of them.  A chunk that does not exist is skipped in both phases (wave-uniform branches).
+// adds of slot u — runs for the first of them.  The number of live chunks of a batch (wave-uniform, 1 .. TN_MAXC) selects ONE
+// straight-line body that issues exactly that many chunk groups and then that many MFMA groups: no branch stands between a
+// load and the MFMAs behind it, so the compiler's wait in front of chunk u's MFMAs leaves chunks u + 1 .. live - 1 in flight.
+// (With `if (u < live)` around each group the wait at every join had to assume the path with the fewest later loads, and
+// the matrix pipe started when the LAST chunk was home.)  mma_mark(u, live) runs in front of slot u's MFMAs (trace stamps).
 // Four chunks of a 16 x 32 tile are 48 fragment registers.  SINGLE: nchunks <= WAVES * TN_MAXC is the caller's contract.
+template <int V> struct IntC { static constexpr int value = V; };       // a compile-time count handed to a generic lambda
 constexpr int TN_MAXC = 4;
-template <int WAVES, bool SINGLE, class L, class S, class M>
-__device__ __forceinline__ void tn_batches(const int wid, const int nchunks, L&& load, S&& loads_out, M&& mma) {
+// The column-sum adds of a chunk stay where they are written, behind that chunk's MFMAs: left free, instruction selection
+// places the adds of chunk u + 1 among chunk u's MFMAs, and the wait for chunk u + 1's loads with them (an empty statement
+// that the adds depend on and that keeps its place among the sched_barriers; no instruction)
+__device__ __forceinline__ void tn_pin(float (&b)[4]) { asm volatile("" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])); }
+template <int LIVE, int WAVES, class L, class K, class M>
+__device__ __forceinline__ void tn_batch_body(const int c0, L&& load, K&& mma_mark, M&& mma) {
+#pragma unroll
+    for (int u = 0; u < LIVE; ++u) {
+        load(u, c0 + u * WAVES);
+        __builtin_amdgcn_sched_barrier(0);                // chunk by chunk, and no MFMA (with its wait) moves up between the loads
+    }
+#pragma unroll
+    for (int u = 0; u < LIVE; ++u) {
+        mma_mark(u, LIVE);
+        mma(u);
+        __builtin_amdgcn_sched_barrier(0);                // slot u + 1's adds (and the wait for its loads) stay behind slot u's MFMAs
+    }
+}
+template <int WAVES, bool SINGLE, class L, class K, class M>
+__device__ __forceinline__ void tn_batches(const int wid, const int nchunks, L&& load, K&& mma_mark, M&& mma) {
     for (int c0 = wid; c0 < nchunks; c0 += WAVES * TN_MAXC) {
         const int live = (nchunks - c0 + WAVES - 1) / WAVES;
-#pragma unroll
-        for (int u = 0; u < TN_MAXC; ++u)
-            if (u < live) load(u, c0 + u * WAVES);
-        __builtin_amdgcn_sched_barrier(0);                // no MFMA (and its wait) moves up between the loads
-        loads_out(c0 == wid);
-#pragma unroll
-        for (int u = 0; u < TN_MAXC; ++u)
-            if (u < live) mma(u);
+        // (trace build only: a scalar branch between the loads and the MFMAs, but one that contains no load or store — the
+        // waits behind it count the same on both of its paths; in the product build mma_mark is empty and the branch is gone)
+        auto mark = [&](const int u, const int n) { if (c0 == wid) mma_mark(u, n); };
+        switch (live < TN_MAXC ? live : TN_MAXC) {
+            case 1: tn_batch_body<1, WAVES>(c0, load, mark, mma); break;
+            case 2: tn_batch_body<2, WAVES>(c0, load, mark, mma); break;
+            case 3: tn_batch_body<3, WAVES>(c0, load, mark, mma); break;
+            default: tn_batch_body<4, WAVES>(c0, load, mark, mma); break;
+        }
         if constexpr (SINGLE) break;
     }
 }
@@ -71,6 +95,7 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
     const int nchunks = (int)((g.K + 15) / 16);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float bs = 0.f;
+    [[maybe_unused]] unsigned long long t_first = 0, t_last = 0;
     float a_p = 0.f, a_m = 0.f, a_v = 0.f, ab_p = 0.f, ab_m = 0.f, ab_v = 0.f, ic1 = 0.f, ic2 = 0.f;
     if constexpr (ADAM) {
         ic1 = (float)(1.0 / (1.0 - ad->pows[0]));
@@ -101,10 +126,14 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
                     b[u][j] = fb.load((uint32_t)c * 16u + (uint32_t)j, 0u);
                 }
             },
-            [&](const bool first) { if (first) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); },   // (first batch's operands + the Adam state)
+            [&](const int u, const int n) {                   // (trace build, first batch: the wave's first / last chunk home)
+                if (u == 0) TNN_STEP_CLOCK_HOME(t_first, a[0][3], b[0][3]);
+                if (u == n - 1) TNN_STEP_CLOCK_HOME(t_last, a[u][3], b[u][3]);
+            },
             [&](const int u) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
+                tn_pin(b[u]);
                 bs += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
             });
     } else {
@@ -155,6 +184,10 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
     bsum[wid][lane] = bs;
     __syncthreads();
     if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 2);
+    if constexpr (ADAM) {
+        TNN_STEP_STAMP_VALUE(g_step_trace_first, 3, 1, 0, t_first);
+        TNN_STEP_STAMP_VALUE(g_step_trace, 3, 4, 1, t_last);
+    }
     if (tid < 256) {
         const int r = tid >> 6, ln = tid & 63;
         float s = 0.f;
@@ -234,6 +267,7 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
     const TnFrag fa(g.A, g.K, g.lda, g.M, grp, am, a_ok), fb(g.B, g.K, g.ldb, g.N, grp, bn, true);
     const int swid = __builtin_amdgcn_readfirstlane(wid);
     float a[TN_MAXC][4], b0[TN_MAXC][4], b1[TN_MAXC][4];
+    [[maybe_unused]] unsigned long long t_first = 0, t_last = 0;
     tn_batches<WAVES, true>(                              // at most 16 chunks on 4 waves (dispatch sites): one batch
         swid, nchunks,
         [&](const int u, const int c) {
@@ -245,13 +279,20 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
                 b1[u][j] = fb.load(row, 64u);
             }
         },
-        [&](const bool first) { if constexpr (ADAM) { if (first) TNN_STEP_STAMP_ACKED(g_step_trace, 3, 1); } },
+        [&](const int u, const int n) {                       // (trace build: the wave's first / last chunk home)
+            if constexpr (ADAM) {
+                if (u == 0) TNN_STEP_CLOCK_HOME(t_first, a[0][3], b1[0][3]);
+                if (u == n - 1) TNN_STEP_CLOCK_HOME(t_last, a[u][3], b1[u][3]);
+            }
+        },
         [&](const int u) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b0[u][j], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b1[u][j], acc1, 0, 0, 0);
             }
+            tn_pin(b0[u]);
+            tn_pin(b1[u]);
             bs0 += (b0[u][0] + b0[u][1]) + (b0[u][2] + b0[u][3]);
             bs1 += (b1[u][0] + b1[u][1]) + (b1[u][2] + b1[u][3]);
         });
@@ -261,6 +302,10 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
     bsum[wid][1][lane] = bs1;
     __syncthreads();
     if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 2);
+    if constexpr (ADAM) {
+        TNN_STEP_STAMP_VALUE(g_step_trace_first, 3, 1, 0, t_first);
+        TNN_STEP_STAMP_VALUE(g_step_trace, 3, 4, 1, t_last);
+    }
     if (e_live) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -299,12 +344,14 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
 //   * fragments come through buffer loads (SGPR resource + 32-bit offset): an out-of-range row / column / k gets the
 //     offset 0xffffffff and the hardware returns 0 — no exec-mask branches, no 64-bit pointer arithmetic;
 //   * a wave issues the loads of ALL its K-chunks (up to MAXC = 4 per batch) before the first MFMA; one chunk per
-//     loop trip made every trip a dependent L2/HBM round trip (fwd0 of the MNIST net: 4 trips per wave);
+//     loop trip made every trip a dependent L2/HBM round trip (fwd0 of the MNIST net: 4 trips per wave).  The first
+//     batch is one straight-line body per number of live chunks, so chunk u's MFMAs run under the later chunks' loads;
 //   * the epilogue's operand (bias / ReLU-mask source / old C) is requested up front by the threads that apply it,
 //     instead of after the cross-wave reduction.
 // SYS_HEADZ: the partial logits leave through write-through (system-scope) stores, because a workgroup of THIS launch
 // on another XCD reads them back (dense_fwd_head_kernel)
-template <bool AKC, bool BKC, int WAVES, bool SYS_HEADZ = false>
+// HEAD = false: a caller that never has a head (no head_lds) gets no bodies for that role
+template <bool AKC, bool BKC, int WAVES, bool SYS_HEADZ = false, bool HEAD = true>
 __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __restrict__ colsum, int block,
                                                 float (*red)[4][64], float (*bsum)[64], float* head_lds = nullptr) {
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -346,13 +393,16 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
     const int swid = __builtin_amdgcn_readfirstlane(wid);     // the branches below are scalar: no exec mask around a load
     float e_pre = 0.f;
     float head_pre[4] = {0.f, 0.f, 0.f, 0.f};                 // wave 0: head_w[n0 + 4 grp + j][i16], the B fragment of the partial-logit product
-    auto request_epilogue = [&]() {
-        if (WAVES <= 4 || swid < 4) {                         // the waves whose threads apply the epilogue
+    // ROLE (wave-uniform, part of the first batch's specialisation): 0 requests nothing, 1 the epilogue's operand (the waves
+    // whose threads apply the epilogue), 2 that and wave 0's head_w fragment
+    auto request_epilogue = [&](auto role_c) {
+        constexpr int ROLE = decltype(role_c)::value;
+        if constexpr (ROLE >= 1) {
             uint32_t off = e_live ? e_off : OOB;
             asm("" : "+v"(off));                              // opaque (TnFrag::load): the select stays a select
             e_pre = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(e_rsrc, off, 0, 0));
         }
-        if (head_on && swid == 0) {
+        if constexpr (ROLE == 2) {
             // one vector multiply for the lane's first unit (opaque, so that it is not fused with the add: a 32-bit multiply-add
             // comes out as v_mad_u64_u32 on a register pair whose upper half is the load in flight in front of it — a full
             // wait for nothing), the unit step added as a scalar
@@ -373,65 +423,107 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float bs = 0.f;
+    [[maybe_unused]] unsigned long long t_first = 0, t_last = 0;
     constexpr int MAXC = 4;
+    auto load_chunk = [&](float (&a)[4], float (&b)[4], const uint32_t c) {
+        const uint32_t k = c * 16u + (uint32_t)grp * 4u;
+        if constexpr (AKC) {
+            uint32_t off = (a_ok && k < K) ? a_lane + c * a_chunk : OOB;     // K % 4 == 0: all in or all out
+            asm("" : "+v"(off));                              // opaque (TnFrag::load): a select, not a branch over two loads
+            const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = __uint_as_float(v[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t off = (a_ok && k + j < K) ? a_lane + c * a_chunk + (uint32_t)j * lda4 : OOB;
+                asm("" : "+v"(off));
+                a[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(a_rsrc, off, 0, 0));
+            }
+        }
+        if constexpr (BKC) {
+            uint32_t off = (b_ok && k < K) ? b_lane + c * b_chunk : OOB;
+            asm("" : "+v"(off));
+            const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, off, 0, 0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) b[j] = __uint_as_float(v[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t off = (b_ok && k + j < K) ? b_lane + c * b_chunk + (uint32_t)j * ldb4 : OOB;
+                asm("" : "+v"(off));
+                b[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b_rsrc, off, 0, 0));
+            }
+        }
+    };
+    auto mma_chunk = [&](const float (&a)[4], float (&b)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
+        tn_pin(b);
+        bs += (b[0] + b[1]) + (b[2] + b[3]);
+    };
     // Every global read of the workgroup is requested before anything waits: the first batch's fragments, then — behind them,
-    // because loads return in order and nothing needs these before the reduction barrier — the epilogue's.  A wave without a
-    // chunk (K < 16 WAVES) still requests its epilogue operand.
-    for (int c0 = swid; c0 < nchunks; c0 += WAVES * MAXC) {
+    // because loads return in order and nothing needs these before the reduction barrier — the epilogue's.  From the first
+    // request to the last MFMA of that batch a wave runs ONE straight-line body, picked by a single scalar branch on its number
+    // of live chunks (0 .. MAXC) and its ROLE: exactly that many chunk groups, the epilogue requests, that many MFMA groups.
+    // With no branch between a load and the MFMAs behind it the compiler counts its waits exactly, and chunk u's MFMAs run
+    // while chunks u + 1 .. are still in flight; with wave-uniform branches around the groups every wait at a join assumed
+    // the path with the fewest later loads, and the matrix pipe started when the wave's LAST load was home.  A chunk that does
+    // not exist costs neither loads nor MFMAs; a wave without a chunk (K < 16 WAVES) still requests its epilogue operand.
+    auto first_batch = [&](auto live_c, auto role_c) {
+        constexpr int LIVE = decltype(live_c)::value;
+        float a[LIVE > 0 ? LIVE : 1][4], b[LIVE > 0 ? LIVE : 1][4];
+#pragma unroll
+        for (int u = 0; u < LIVE; ++u) {
+            load_chunk(a[u], b[u], (uint32_t)(swid + u * WAVES));
+            __builtin_amdgcn_sched_barrier(0);                // chunk by chunk, and the fragment requests stay in front
+        }
+        request_epilogue(role_c);
+        __builtin_amdgcn_sched_barrier(0);                    // ... and no MFMA (with its wait) moves up between the loads
+#pragma unroll
+        for (int u = 0; u < LIVE; ++u) {
+            if (u == 0) TNN_STEP_CLOCK_HOME(t_first, a[0][3], b[0][3]);           // (trace build: no wait the product build lacks)
+            if (u == LIVE - 1) TNN_STEP_CLOCK_HOME(t_last, a[u][3], b[u][3]);
+            mma_chunk(a[u], b[u]);
+            __builtin_amdgcn_sched_barrier(0);                // chunk u + 1's adds (and the wait for its loads) stay behind chunk u's MFMAs
+        }
+    };
+    auto by_live = [&](auto role_c) {
+        const int live = swid < nchunks ? (nchunks - swid + WAVES - 1) / WAVES : 0;
+        switch (live < MAXC ? live : MAXC) {
+            case 0: first_batch(IntC<0>{}, role_c); break;
+            case 1: first_batch(IntC<1>{}, role_c); break;
+            case 2: first_batch(IntC<2>{}, role_c); break;
+            case 3: first_batch(IntC<3>{}, role_c); break;
+            default: first_batch(IntC<4>{}, role_c); break;
+        }
+    };
+    if (HEAD && head_on && swid == 0) by_live(IntC<2>{});
+    else if (WAVES <= 4 || swid < 4) by_live(IntC<1>{});
+    else by_live(IntC<0>{});
+    // later batches (more than WAVES * MAXC chunks): their waits stand on their own loads
+    for (int c0 = swid + WAVES * MAXC; c0 < nchunks; c0 += WAVES * MAXC) {
         float a[MAXC][4], b[MAXC][4];
 #pragma unroll
         for (int u = 0; u < MAXC; ++u) {
             const uint32_t c = (uint32_t)(c0 + u * WAVES);
-            const uint32_t k = c * 16u + (uint32_t)grp * 4u;
             if ((int)c >= nchunks) {                                  // wave-uniform: no loads for chunks that do not exist
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { a[u][j] = 0.f; b[u][j] = 0.f; }
                 continue;
             }
-            if constexpr (AKC) {
-                const uint32_t off = (a_ok && k < K) ? a_lane + c * a_chunk : OOB;     // K % 4 == 0: all in or all out
-                const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, off, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[u][j] = __uint_as_float(v[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t off = (a_ok && k + j < K) ? a_lane + c * a_chunk + (uint32_t)j * lda4 : OOB;
-                    a[u][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(a_rsrc, off, 0, 0));
-                }
-            }
-            if constexpr (BKC) {
-                const uint32_t off = (b_ok && k < K) ? b_lane + c * b_chunk : OOB;
-                const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, off, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) b[u][j] = __uint_as_float(v[j]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t off = (b_ok && k + j < K) ? b_lane + c * b_chunk + (uint32_t)j * ldb4 : OOB;
-                    b[u][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(b_rsrc, off, 0, 0));
-                }
-            }
-        }
-        if (c0 == swid) {
-            __builtin_amdgcn_sched_barrier(0);                // the fragment requests stay in front
-            request_epilogue();
-            __builtin_amdgcn_sched_barrier(0);                // ... and no MFMA (with its wait) moves up between the loads
-            TNN_STEP_STAMP_ACKED(g_step_trace, KID, 1);
+            load_chunk(a[u], b[u], c);
         }
 #pragma unroll
-        for (int u = 0; u < MAXC; ++u) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
-            bs += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
-        }
+        for (int u = 0; u < MAXC; ++u) mma_chunk(a[u], b[u]);
     }
-    if (swid >= nchunks) request_epilogue();
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc[r];
     bsum[wid][lane] = bs;
     __syncthreads();
     TNN_STEP_STAMP(g_step_trace, KID, 2);
+    TNN_STEP_STAMP_VALUE(g_step_trace_first, KID, 1, 0, t_first);
+    TNN_STEP_STAMP_VALUE(g_step_trace, KID, 4, 1, t_last);
     float e_val = 0.f;
     if (tid < 256) {
         float s = 0.f;

@@ -341,9 +341,9 @@ __global__ __launch_bounds__(WAVES * 64) void dense_bwd_small_kernel(GemmArgs gw
     __shared__ float bsum[WAVES][64];
     if constexpr (FAST) {
         if ((int)blockIdx.x < n_dw)
-            small_tile_fast<false, false, WAVES>(gw, db, (int)blockIdx.x, red, bsum);
+            small_tile_fast<false, false, WAVES, false, false>(gw, db, (int)blockIdx.x, red, bsum);
         else
-            small_tile_fast<true, true, WAVES>(gx, nullptr, (int)blockIdx.x - n_dw, red, bsum);
+            small_tile_fast<true, true, WAVES, false, false>(gx, nullptr, (int)blockIdx.x - n_dw, red, bsum);
     } else {
         if ((int)blockIdx.x < n_dw)
             small_tile<false, false, WAVES>(gw, db, (int)blockIdx.x, red, bsum);

@@ -66,13 +66,30 @@ void set_update_guard(const int* device_word);
 // -DTNN_STEP_TRACE: the headline step's four launches, one row of four words per workgroup — [0] entry, [1] every operand of
 // the product in registers (s_waitcnt vmcnt(0) behind the last load), [2] last MFMA issued and the cross-wave reduction read
 // back, [3] last store acknowledged.  Kernel ids (blocks of 1024 rows): 0 fwd0, 1 fwd1 + partial logits, 2 head + hidden
-// backward, 3 first-layer backward + Adam.  tools/probes/step_stamps.py reads them.
+// backward, 3 first-layer backward + Adam.  tools/probes/step_stamps.py reads them.  (fwd0, fwd1 and bwd0's tiles: [1] is wave 0's
+// LAST chunk home and g_step_trace_first holds its first chunk home — TNN_STEP_CLOCK_HOME below.)
 #ifdef TNN_STEP_TRACE
 #define TNN_STEP_STAMP(buf, kid, slot) TNN_STAMP_STORE(buf, blockIdx.x, 4, 1024, (kid) * 1024 * 4 + (slot))
 #define TNN_STEP_STAMP_ACKED(buf, kid, slot) TNN_STAMP_STORE_ACKED(buf, blockIdx.x, 4, 1024, (kid) * 1024 * 4 + (slot))
+// The tiles whose MFMAs start under their later chunks' loads (tnn_gemm_small.h) must not take a full wait in front of the
+// first MFMA, and a stamp's own store between the loads would be counted with them.  There TNN_STEP_CLOCK_HOME(var, r0, r1)
+// only READS the clock (s_memrealtime, not a vector-memory operation) once the fragment registers r0, r1 are home — the
+// empty asm uses them, so the compiler's own wait for exactly these two loads stands in front — and TNN_STEP_STAMP_VALUE
+// stores the value later, behind the last MFMA: [1] = the wave's LAST chunk home, g_step_trace_first[kid][workgroup] = its first.
+#define TNN_STEP_CLOCK_HOME(var, r0, r1)                             \
+    do {                                                             \
+        asm volatile("" ::"v"(r0), "v"(r1) : "memory");              \
+        (var) = wall_clock64();                                      \
+    } while (0)
+#define TNN_STEP_STAMP_VALUE(buf, kid, stride, slot, val)                                                                 \
+    do {                                                                                                                  \
+        if (threadIdx.x == 0 && blockIdx.x < 1024) (buf)[((kid) * 1024 + blockIdx.x) * (stride) + (slot)] = (val);        \
+    } while (0)
 #else
 #define TNN_STEP_STAMP TNN_STAMP_OFF
 #define TNN_STEP_STAMP_ACKED TNN_STAMP_OFF
+#define TNN_STEP_CLOCK_HOME TNN_STAMP_OFF
+#define TNN_STEP_STAMP_VALUE TNN_STAMP_OFF
 #endif
 // -DTNN_AR_TRACE: the data-parallel step's fused launches (g_fh_trace, g_ar_trace in tnn_gemm_step.h, SkipRanges::trace in
 // tnn_p2p.h; tools/probes/ar_fused_trace.py)

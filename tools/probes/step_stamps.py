@@ -4,6 +4,9 @@ launches from the debug library (`make -C tinynn-autograd_amd/csrc trace`, -DTNN
     TNN_LIB_PATH=tinynn-autograd_amd/lib/libtnn_hip_trace.so python3 tools/probes/step_stamps.py > profiles/r06_stepA_stamps.txt
 For every launch, over its workgroups and 40 traced steps, relative to the launch's first workgroup entry (10 ns steps):
     entry | operands in registers (s_waitcnt vmcnt(0) behind the product's loads) | last MFMA + cross-wave sum read back | last store acknowledged
+In fwd0, fwd1 and bwd0's tiles the MFMAs start under the later chunks' loads, and a full wait in front of the first MFMA would put
+back the serialisation the product build does not have: there the second column is split in two clock reads that wait for
+nothing more than the product build does — wave 0's first chunk home | wave 0's last chunk of its first batch home.
 and how many workgroups the launch has against the 256 CUs.  The last launch's flat-range Adam workgroups (behind its tiles) are
 printed as a role of their own: entry | loads landed | last update computed | last store acknowledged.  (The stamps cost a few hundred ns per launch: the sum of the traced
 launches is longer than the untraced step; the STAGES are what this is for.)"""
@@ -29,17 +32,26 @@ fg = lib.cdll.tnn_debug_step_trace
 fg.argtypes = [ctypes.c_void_p, ctypes.c_int]
 fh = lib.cdll.tnn_debug_step_trace_head
 fh.argtypes = [ctypes.c_void_p, ctypes.c_int]
+try:
+    ff = lib.cdll.tnn_debug_step_trace_first
+    ff.argtypes = [ctypes.c_void_p, ctypes.c_int]
+except AttributeError:                                 # a trace library from before the chunk stamps: the four columns only
+    ff = lambda ptr, n: 0
 gbuf = np.zeros(4 * 1024 * 4, dtype=np.uint64)
 hbuf = np.zeros(1024 * 4, dtype=np.uint64)
+fbuf = np.zeros(4 * 1024, dtype=np.uint64)
 acc = []
+first = []
 for it in range(60):
     t.step(x, y)
     if it >= 20:
-        assert fg(gbuf.ctypes.data, gbuf.size) == 0 and fh(hbuf.ctypes.data, hbuf.size) == 0
+        assert fg(gbuf.ctypes.data, gbuf.size) == 0 and fh(hbuf.ctypes.data, hbuf.size) == 0 and ff(fbuf.ctypes.data, fbuf.size) == 0
+        first.append(fbuf.reshape(4, 1024).astype(np.int64).copy())
         g = gbuf.reshape(4, 1024, 4).astype(np.int64).copy()
         g[2] = hbuf.reshape(1024, 4).astype(np.int64)
         acc.append(g)
 tr = np.stack(acc)                                     # [step][kernel][block][stamp]
+tf = np.stack(first)                                   # [step][kernel][block]: wave 0's first chunk home (0: not such a tile)
 names = ["fwd0  gemm_small_f32_kernel<.., 16, ..>  (784 -> 256, bias + ReLU)",
          "fwd1  gemm_small_f32_kernel<.., 4, ..>   (256 -> 128, bias + ReLU, partial logits)",
          "head  mlp_head_bwd_kernel<128, 10>       (loss, dz, dW2 / db2, dW1 / db1, dx1)",
@@ -60,9 +72,16 @@ for k in range(4):
     t0 = np.where(live, blk[:, :, 0], np.iinfo(np.int64).max).min(axis=1)[:, None, None]
     rel = (blk - t0) / 100.0
     print("%s   workgroups %d (%.2f per CU)" % (names[k], n, n / 256.0))
-    for s, label in enumerate(("entry", "operands in registers", "last MFMA, sums read back", "last store acknowledged")):
-        v = rel[:, :, s]
-        ok = (blk[:, :, s] > 0)
+    chunked = (tf[:, k, :n] > 0).any()                 # fwd0, fwd1, bwd0's tiles: [1] is the last chunk's clock read
+    for s, label in ((0, "entry"), (-1, "first chunk home (wave 0)"), (1, "last chunk home (wave 0)" if chunked else "operands in registers"),
+                     (2, "last MFMA, sums read back"), (3, "last store acknowledged")):
+        if s < 0:
+            raw = tf[:, k, :n]
+            v = (raw - t0[:, :, 0]) / 100.0
+        else:
+            raw = blk[:, :, s]
+            v = rel[:, :, s]
+        ok = raw > 0
         if not ok.any():
             continue
         vv = np.where(ok, v, np.nan)
