@@ -81,7 +81,7 @@ def test_the_constants_are_the_headers():
     text = open(HEADER).read()
     assert int(re.search(r"#define\s+TNN_GQA_MAX_GROUP\s+(\d+)", text).group(1)) == gqa.MAX_GROUP == go.MAX_GROUP
     assert gqa.DECODE_STATES[-1] == gqa.MAX_GROUP and gqa.DECODE_STATES[0] == 1
-    src = open(os.path.join(ROOT, "tinynn-autograd_amd", "csrc", "tnn_gqa.hip")).read()
+    src = open(os.path.join(ROOT, "tinynn-autograd_amd", "csrc", "tnn_decode_kernel.h")).read()     # (launch_call: the Q dispatch)
     assert sorted(int(n) for n in re.findall(r"launch_states<T, (\d+)>", src)) == list(gqa.DECODE_STATES)
 
 

@@ -25,23 +25,11 @@
 namespace {
 
 using namespace tnn;      // Pack, Math, aligned16, item_of, round16, with_float (tnn_pack.h)
-using namespace tnn::decode;      // the key loop, its argument record and the lane-group geometry (tnn_decode_kernel.h)
+using namespace tnn::decode;      // THREADS, WAVES, DecodeArgs and the decode host path (tnn_decode_kernel.h)
 
 constexpr int ITEMS = TNN_SAMPLE_ITEMS;
 constexpr int BINS = 1 << TNN_SAMPLE_RADIX_BITS;
 static_assert(BINS == THREADS, "one thread clears one bin of the histogram");
-
-// ------------------------------------------------------------------------------------------------ decode attention
-// (the bodies are in tnn_decode_kernel.h: csrc/tnn_ragged.hip instantiates the same ones with the lengths read on the device)
-template <typename T, bool VECTOR, int R>
-__global__ __launch_bounds__(THREADS) void decode_kernel(DecodeArgs a) {
-    decode_body<T, VECTOR, R>(a);
-}
-
-template <typename T>
-__global__ __launch_bounds__(MAXD) void decode_combine_kernel(DecodeArgs a) {
-    combine_body<T>(a);
-}
 
 // ------------------------------------------------------------------------------------------------ sampling
 template <typename T> struct Key;
@@ -259,63 +247,21 @@ __global__ __launch_bounds__(THREADS) void sample_kernel(const T* __restrict__ l
     }
 }
 
-template <typename T>
-void launch_decode(const DecodeArgs& a, bool vec, int R, dim3 grid) {
-    hipStream_t s = tnn::stream();
-    if (vec) hipLaunchKernelGGL((decode_kernel<T, true, 1>), grid, dim3(THREADS), 0, s, a);
-    else if (R == 1) hipLaunchKernelGGL((decode_kernel<T, false, 1>), grid, dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((decode_kernel<T, false, 2>), grid, dim3(THREADS), 0, s, a);
-}
-
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ decode attention
+// (the kernels, the checks and the launches are in tnn_decode_kernel.h: csrc/tnn_ragged.hip and csrc/tnn_gqa.hip go through
+// the same ones with the lengths read on the device and with grouped heads)
 extern "C" int tnn_decode_attn_workspace(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype, int64_t* bytes) {
-    TNN_REQUIRE(bytes != nullptr, "tnn_decode_attn_workspace: null result pointer");
-    TNN_REQUIRE_FLOAT("tnn_decode_attn_workspace");
-    TNN_REQUIRE(B >= 0 && H >= 0 && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM && splits >= 1 && splits <= TNN_DECODE_MAX_SPLITS,
-                "tnn_decode_attn_workspace: B %lld, H %lld, Dv %lld, splits %lld (Dv <= %d, splits <= %d)", (long long)B,
-                (long long)H, (long long)Dv, (long long)splits, TNN_ATTN_MAX_HEAD_DIM, TNN_DECODE_MAX_SPLITS);
-    *bytes = decode_space(B, H, splits, Dv, dtype);
-    return 0;
+    return decode_workspace("tnn_decode_attn_workspace", B, H, splits, Dv, dtype, bytes);
 }
 
 extern "C" int tnn_decode_attn(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* o,
                                void* workspace, int64_t workspace_bytes, int64_t B, int64_t H, int64_t len, int64_t Tmax,
                                int64_t D, int64_t Dv, const int64_t* strides, double scale, int64_t splits, int dtype) {
-    TNN_NEED_INIT();
-    TNN_REQUIRE_FLOAT("tnn_decode_attn");
-    TNN_REQUIRE(B >= 0 && H >= 0 && B * H < 65536 && D >= 1 && D <= TNN_ATTN_MAX_HEAD_DIM && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM,
-                "tnn_decode_attn: B %lld, H %lld, D %lld, Dv %lld (B H < 65536, 1 <= D, Dv <= %d)", (long long)B, (long long)H,
-                (long long)D, (long long)Dv, TNN_ATTN_MAX_HEAD_DIM);
-    TNN_REQUIRE((k_new == nullptr) == (v_new == nullptr), "tnn_decode_attn: k_new and v_new come together or not at all");
-    const bool append = k_new != nullptr;
-    TNN_REQUIRE(Tmax >= 1 && len >= 0 && (append ? len < Tmax : (len >= 1 && len <= Tmax)),
-                "tnn_decode_attn: len %lld with a cache of %lld rows (%s)", (long long)len, (long long)Tmax,
-                append ? "the appended row needs len < Tmax" : "without k_new / v_new: 1 <= len <= Tmax");
-    const int64_t nkeys = len + (append ? 1 : 0), chunks = (nkeys + TNN_DECODE_CHUNK - 1) / TNN_DECODE_CHUNK;
-    const int64_t most = chunks < TNN_DECODE_MAX_SPLITS ? chunks : TNN_DECODE_MAX_SPLITS;
-    TNN_REQUIRE(splits >= 1 && splits <= most, "tnn_decode_attn: splits %lld outside [1, %lld] (%lld chunks of %d keys)",
-                (long long)splits, (long long)most, (long long)chunks, TNN_DECODE_CHUNK);
-    if (B * H == 0) return 0;
-    TNN_REQUIRE(q && k_cache && v_cache && o && strides, "tnn_decode_attn: null operand");
-    const int64_t need = decode_space(B, H, splits, Dv, dtype);
-    if (splits > 1) TNN_REQUIRE_WORKSPACE("tnn_decode_attn", workspace, workspace_bytes, need);
-
-    DecodeArgs a = {};
-    bool vec;
-    const int R = fill_args(a, q, k_new, v_new, k_cache, v_cache, o, workspace, H, D, Dv, strides, scale, splits, dtype, vec);
-    a.nkeys = nkeys; a.len = len; a.chunks = chunks;
-
-    const dim3 grid((unsigned)splits, (unsigned)(B * H));
-    with_float(dtype, [&](auto t) { launch_decode<decltype(t)>(a, vec, R, grid); });
-    TNN_LAUNCH_OK();
-    if (splits > 1) {
-        with_float(dtype, [&](auto t) {
-            hipLaunchKernelGGL(decode_combine_kernel<decltype(t)>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
-        });
-        TNN_LAUNCH_OK();
-    }
-    return 0;
+    const DecodeCall c = {q, k_new, v_new, k_cache, v_cache, o, workspace, workspace_bytes, nullptr,
+                          B, H, H, len, Tmax, D, Dv, strides, scale, splits, dtype};
+    return decode_attn<DecodeArgs>("tnn_decode_attn", c);
 }
 
 extern "C" int tnn_sample_rows(const void* logits, const void* u, void* out_ids, int64_t M, int64_t V, double temperature,

@@ -1,13 +1,16 @@
-// The key loop of decode attention, shared by csrc/tnn_decode.hip (the batch's length is a host integer in the launch
-// arguments) and csrc/tnn_ragged.hip (every sequence's length is read from a device array): ONE body, templated on the
-// argument record, so the key loop, the exchange tree, the waves' meeting and the combine order are the same instructions in
-// both — which is what makes the ragged kernel's result bit-equal to the uniform one's, sequence by sequence.
+// Decode attention, shared by csrc/tnn_decode.hip (the batch's length is a host integer in the launch arguments),
+// csrc/tnn_ragged.hip (every sequence's length is read from a device array) and csrc/tnn_gqa.hip (a workgroup serves the query
+// heads of one key / value head): ONE body, templated on the argument record, so the key loop, the exchange tree, the waves'
+// meeting and the combine order are the same instructions in every form — which is what makes the ragged kernel's result
+// bit-equal to the uniform one's, sequence by sequence.  The host side is ONE path too (the end of this file): the kernel
+// templates, every check with its message, the launches; an entry point fills a DecodeCall and names its record.
 // Internal: not installed under include/.
 #pragma once
 #include <math.h>
 
 #include "tnn_pack.h"
 #include "tnn_decode.h"
+#include "tnn_gqa.h"
 
 namespace tnn {
 namespace decode {
@@ -341,6 +344,151 @@ inline int fill_args(DecodeArgs& a, const void* q, const void* k_new, const void
 
 inline int64_t decode_space(int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype) {
     return splits == 1 ? 0 : round16(B * H * splits * (Dv + 2) * item_of(dtype));
+}
+
+// ------------------------------------------------------------------------------------------------ the host path
+// (a translation unit instantiates the kernels of the records its entry points name: DecodeArgs in tnn_decode.hip, RaggedArgs
+// in tnn_ragged.hip, the grouped records in tnn_gqa.hip)
+template <typename T, bool VECTOR, int R, int Q, typename A>
+__global__ __launch_bounds__(THREADS) void key_loop_kernel(A a) {
+    decode_body<T, VECTOR, R, Q>(a);
+}
+
+// (a.H is the QUERY head count here: one workgroup per (b, query head))
+template <typename T, typename A>
+__global__ __launch_bounds__(MAXD) void combine_kernel(A a) {
+    combine_body<T>(a);
+}
+
+// what an entry point was called with (the ungrouped forms: Hkv = H; the ragged ones: lens and no len)
+struct DecodeCall {
+    const void* q; const void* k_new; const void* v_new;
+    void* k_cache; void* v_cache; void* o; void* workspace;
+    int64_t workspace_bytes;
+    const void* lens;
+    int64_t B, H, Hkv, len, Tmax, D, Dv;
+    const int64_t* strides;
+    double scale;
+    int64_t splits;
+    int dtype;
+};
+
+// H, Hkv -> group (the message set when the pair is refused); the training entry points of tnn_gqa.hip use it too
+inline int group_of(const char* who, int64_t H, int64_t Hkv, int64_t* group) {
+    TNN_REQUIRE(H >= 0 && Hkv >= 0 && (H == 0) == (Hkv == 0), "%s: H %lld query heads over Hkv %lld key / value heads", who,
+                (long long)H, (long long)Hkv);
+    *group = 1;
+    if (H == 0) return 0;
+    TNN_REQUIRE(H % Hkv == 0, "%s: H %lld is no multiple of Hkv %lld", who, (long long)H, (long long)Hkv);
+    *group = H / Hkv;
+    TNN_REQUIRE(*group <= TNN_GQA_MAX_GROUP, "%s: group %lld = H %lld / Hkv %lld exceeds TNN_GQA_MAX_GROUP = %d", who,
+                (long long)*group, (long long)H, (long long)Hkv, TNN_GQA_MAX_GROUP);
+    return 0;
+}
+
+// Every refusal of a decode call, in the order the entry points make them; what a rule derives on its way (the group, the
+// live keys and their chunks, or where the lengths are) goes into the record.  An empty batch (B H = 0) passes with its
+// operands unseen.
+template <typename A>
+int check_call(const char* who, const DecodeCall& c, A& a) {
+    const int dtype = c.dtype;                                 // (the name TNN_REQUIRE_FLOAT reads)
+    int64_t rows = c.H;                                        // the grid's rows per batch: the key / value heads
+    if constexpr (A::GROUPED) {
+        int64_t group;
+        if (int rc = group_of(who, c.H, c.Hkv, &group)) return rc;
+        rows = c.Hkv;
+        a.nq = (int)group;
+    }
+    TNN_REQUIRE_FLOAT(who);
+    const char* heads = A::GROUPED ? "Hkv" : "H";
+    TNN_REQUIRE(c.B >= 0 && rows >= 0 && c.B * rows < 65536 && c.D >= 1 && c.D <= TNN_ATTN_MAX_HEAD_DIM && c.Dv >= 1 &&
+                    c.Dv <= TNN_ATTN_MAX_HEAD_DIM,
+                "%s: B %lld, %s %lld, D %lld, Dv %lld (B %s < 65536, 1 <= D, Dv <= %d)", who, (long long)c.B, heads,
+                (long long)rows, (long long)c.D, (long long)c.Dv, heads, TNN_ATTN_MAX_HEAD_DIM);
+    int64_t bound;                                             // the keys that bound the split: the live ones, or the cache's rows
+    if constexpr (A::RAGGED) {
+        TNN_REQUIRE(c.k_new != nullptr && c.v_new != nullptr, "%s: k_new and v_new are required (the step appends its row)", who);
+        TNN_REQUIRE(c.Tmax >= 1, "%s: a cache of %lld rows", who, (long long)c.Tmax);
+        bound = c.Tmax;
+        a.lens = static_cast<const int64_t*>(c.lens);
+        a.Tmax = c.Tmax;
+    } else {
+        TNN_REQUIRE((c.k_new == nullptr) == (c.v_new == nullptr), "%s: k_new and v_new come together or not at all", who);
+        const bool append = c.k_new != nullptr;
+        TNN_REQUIRE(c.Tmax >= 1 && c.len >= 0 && (append ? c.len < c.Tmax : (c.len >= 1 && c.len <= c.Tmax)),
+                    "%s: len %lld with a cache of %lld rows (%s)", who, (long long)c.len, (long long)c.Tmax,
+                    append ? "the appended row needs len < Tmax" : "without k_new / v_new: 1 <= len <= Tmax");
+        bound = c.len + (append ? 1 : 0);
+        a.nkeys = bound; a.len = c.len;
+    }
+    const int64_t chunks = (bound + TNN_DECODE_CHUNK - 1) / TNN_DECODE_CHUNK;
+    const int64_t most = chunks < TNN_DECODE_MAX_SPLITS ? chunks : TNN_DECODE_MAX_SPLITS;
+    TNN_REQUIRE(c.splits >= 1 && c.splits <= most, "%s: splits %lld outside [1, %lld] (%s%lld chunks of %d keys)", who,
+                (long long)c.splits, (long long)most, A::RAGGED ? "a cache of " : "", (long long)chunks, TNN_DECODE_CHUNK);
+    if constexpr (!A::RAGGED) a.chunks = chunks;               // (ragged: every workgroup derives its own)
+    if (c.B * c.H == 0) return 0;
+    TNN_REQUIRE(c.q && c.k_cache && c.v_cache && c.o && c.strides && (!A::RAGGED || c.lens), "%s: null operand", who);
+    if (c.splits > 1) TNN_REQUIRE_WORKSPACE(who, c.workspace, c.workspace_bytes, decode_space(c.B, c.H, c.splits, c.Dv, dtype));
+    return 0;
+}
+
+template <typename T, int Q, typename A>
+void launch_states(const A& a, bool vec, int R, dim3 grid) {
+    hipStream_t s = tnn::stream();
+    if (vec) hipLaunchKernelGGL((key_loop_kernel<T, true, 1, Q, A>), grid, dim3(THREADS), 0, s, a);
+    else if (R == 1) hipLaunchKernelGGL((key_loop_kernel<T, false, 1, Q, A>), grid, dim3(THREADS), 0, s, a);
+    else hipLaunchKernelGGL((key_loop_kernel<T, false, 2, Q, A>), grid, dim3(THREADS), 0, s, a);
+}
+
+// the key loop over (splits, B rows) workgroups — a row is a key / value head, served with Q = 1, 2, 4 or 8 query states when
+// the record is grouped — then, when the keys are split, the combine over the B H query heads
+static_assert(TNN_GQA_MAX_GROUP == 8, "the key loop is instantiated for 1, 2, 4 and 8 query states");
+template <typename A>
+int launch_call(const DecodeCall& c, A& a) {
+    const int64_t rows = A::GROUPED ? c.Hkv : c.H;
+    bool vec;
+    const int R = fill_args(a, c.q, c.k_new, c.v_new, c.k_cache, c.v_cache, c.o, c.workspace, rows, c.D, c.Dv, c.strides, c.scale,
+                            c.splits, c.dtype, vec);
+    const dim3 grid((unsigned)c.splits, (unsigned)(c.B * rows));
+    with_float(c.dtype, [&](auto t) {
+        typedef decltype(t) T;
+        int nq = 1;
+        if constexpr (A::GROUPED) nq = a.nq;
+        if (nq == 1) launch_states<T, 1>(a, vec, R, grid);
+        else if constexpr (A::GROUPED) {
+            if (nq == 2) launch_states<T, 2>(a, vec, R, grid);
+            else if (nq <= 4) launch_states<T, 4>(a, vec, R, grid);
+            else launch_states<T, 8>(a, vec, R, grid);
+        }
+    });
+    TNN_LAUNCH_OK();
+    if (c.splits > 1) {
+        a.H = (int)c.H;
+        with_float(c.dtype, [&](auto t) {
+            hipLaunchKernelGGL((combine_kernel<decltype(t), A>), dim3((unsigned)(c.B * c.H)), dim3(MAXD), 0, tnn::stream(), a);
+        });
+        TNN_LAUNCH_OK();
+    }
+    return 0;
+}
+
+template <typename A>
+int decode_attn(const char* who, const DecodeCall& c) {
+    TNN_NEED_INIT();
+    A a = {};
+    if (int rc = check_call(who, c, a)) return rc;
+    if (c.B * c.H == 0) return 0;
+    return launch_call(c, a);
+}
+
+inline int decode_workspace(const char* who, int64_t B, int64_t H, int64_t splits, int64_t Dv, int dtype, int64_t* bytes) {
+    TNN_REQUIRE(bytes != nullptr, "%s: null result pointer", who);
+    TNN_REQUIRE_FLOAT(who);
+    TNN_REQUIRE(B >= 0 && H >= 0 && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM && splits >= 1 && splits <= TNN_DECODE_MAX_SPLITS,
+                "%s: B %lld, H %lld, Dv %lld, splits %lld (Dv <= %d, splits <= %d)", who, (long long)B, (long long)H,
+                (long long)Dv, (long long)splits, TNN_ATTN_MAX_HEAD_DIM, TNN_DECODE_MAX_SPLITS);
+    *bytes = decode_space(B, H, splits, Dv, dtype);
+    return 0;
 }
 
 }  // namespace decode

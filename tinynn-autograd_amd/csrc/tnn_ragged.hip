@@ -18,27 +18,9 @@
 namespace {
 
 using namespace tnn;      // Pack, aligned16, item_of, with_float (tnn_pack.h)
-using namespace tnn::decode;      // the key loop, its argument records and the lane-group geometry (tnn_decode_kernel.h)
+using namespace tnn::decode;      // THREADS, RaggedArgs and the decode host path (tnn_decode_kernel.h)
 
 static_assert(TNN_TOKEN_VEC == 16, "wide accesses are global_load / store_dwordx4");
-
-template <typename T, bool VECTOR, int R>
-__global__ __launch_bounds__(THREADS) void ragged_decode_kernel(RaggedArgs a) {
-    decode_body<T, VECTOR, R>(a);
-}
-
-template <typename T>
-__global__ __launch_bounds__(MAXD) void ragged_combine_kernel(RaggedArgs a) {
-    combine_body<T>(a);
-}
-
-template <typename T>
-void launch_ragged(const RaggedArgs& a, bool vec, int R, dim3 grid) {
-    hipStream_t s = tnn::stream();
-    if (vec) hipLaunchKernelGGL((ragged_decode_kernel<T, true, 1>), grid, dim3(THREADS), 0, s, a);
-    else if (R == 1) hipLaunchKernelGGL((ragged_decode_kernel<T, false, 1>), grid, dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL((ragged_decode_kernel<T, false, 2>), grid, dim3(THREADS), 0, s, a);
-}
 
 // one thread per sequence; u_all == nullptr: no uniform numbers to hand on
 template <typename T>
@@ -86,38 +68,9 @@ extern "C" int tnn_ragged_decode_attn(const void* q, const void* k_new, const vo
                                       void* workspace, int64_t workspace_bytes, const void* lens, int64_t B, int64_t H,
                                       int64_t Tmax, int64_t D, int64_t Dv, const int64_t* strides, double scale, int64_t splits,
                                       int dtype) {
-    TNN_NEED_INIT();
-    TNN_REQUIRE_FLOAT("tnn_ragged_decode_attn");
-    TNN_REQUIRE(B >= 0 && H >= 0 && B * H < 65536 && D >= 1 && D <= TNN_ATTN_MAX_HEAD_DIM && Dv >= 1 && Dv <= TNN_ATTN_MAX_HEAD_DIM,
-                "tnn_ragged_decode_attn: B %lld, H %lld, D %lld, Dv %lld (B H < 65536, 1 <= D, Dv <= %d)", (long long)B,
-                (long long)H, (long long)D, (long long)Dv, TNN_ATTN_MAX_HEAD_DIM);
-    TNN_REQUIRE(k_new != nullptr && v_new != nullptr, "tnn_ragged_decode_attn: k_new and v_new are required (the step appends its row)");
-    TNN_REQUIRE(Tmax >= 1, "tnn_ragged_decode_attn: a cache of %lld rows", (long long)Tmax);
-    const int64_t chunks = (Tmax + TNN_DECODE_CHUNK - 1) / TNN_DECODE_CHUNK;
-    const int64_t most = chunks < TNN_DECODE_MAX_SPLITS ? chunks : TNN_DECODE_MAX_SPLITS;
-    TNN_REQUIRE(splits >= 1 && splits <= most, "tnn_ragged_decode_attn: splits %lld outside [1, %lld] (a cache of %lld chunks of %d keys)",
-                (long long)splits, (long long)most, (long long)chunks, TNN_DECODE_CHUNK);
-    if (B * H == 0) return 0;
-    TNN_REQUIRE(q && k_cache && v_cache && o && strides && lens, "tnn_ragged_decode_attn: null operand");
-    const int64_t need = decode_space(B, H, splits, Dv, dtype);
-    if (splits > 1) TNN_REQUIRE_WORKSPACE("tnn_ragged_decode_attn", workspace, workspace_bytes, need);
-
-    RaggedArgs a = {};
-    bool vec;
-    const int R = fill_args(a, q, k_new, v_new, k_cache, v_cache, o, workspace, H, D, Dv, strides, scale, splits, dtype, vec);
-    a.lens = static_cast<const int64_t*>(lens);
-    a.Tmax = Tmax;
-
-    const dim3 grid((unsigned)splits, (unsigned)(B * H));
-    with_float(dtype, [&](auto t) { launch_ragged<decltype(t)>(a, vec, R, grid); });
-    TNN_LAUNCH_OK();
-    if (splits > 1) {
-        with_float(dtype, [&](auto t) {
-            hipLaunchKernelGGL(ragged_combine_kernel<decltype(t)>, dim3((unsigned)(B * H)), dim3(MAXD), 0, tnn::stream(), a);
-        });
-        TNN_LAUNCH_OK();
-    }
-    return 0;
+    const DecodeCall c = {q, k_new, v_new, k_cache, v_cache, o, workspace, workspace_bytes, lens,
+                          B, H, H, 0, Tmax, D, Dv, strides, scale, splits, dtype};
+    return decode_attn<RaggedArgs>("tnn_ragged_decode_attn", c);
 }
 
 extern "C" int tnn_ragged_advance(const void* picked, void* lens, const void* start, void* done, void* out, void* cur,

@@ -1992,6 +1992,75 @@ def _decode_cache(a, dt, what):
     return a
 
 
+def _decode_operands(what, q, k_cache, v_cache, k_new, v_new, lens=None):
+    """(dt, q, k_cache, v_cache, k_new, v_new, lens) of a decode call — attention_decode, attention_decode_ragged, gqa_decode:
+    the dtype is the caches', which are taken as they are; q and the step's row (when there is one) are cast and made dense;
+    lens (when given) must be a dense int64 device array."""
+    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
+    dt = cands[0] if cands else _default_float
+    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
+    q = asarray(q)._as_float(dt)._contig()
+    if k_new is not None:
+        k_new, v_new = asarray(k_new)._as_float(dt)._contig(), asarray(v_new)._as_float(dt)._contig()
+    return dt, q, k_cache, v_cache, k_new, v_new, (None if lens is None else _ragged_state(lens, what, "lens"))
+
+
+def _decode_float_ok(dt):
+    return dt in (np.dtype(np.float32), np.dtype(np.float64))
+
+
+def _decode_native(entry, plan, dt, q, k_cache, v_cache, k_new, v_new, lens=None):
+    """ONE call of `entry` (lib.decode_attn, lib.ragged_decode_attn, lib.gqa_decode_attn or lib.gqa_ragged_decode_attn — the
+    ragged ones take the lengths' address after the workspace); the workspace of a split call comes from the buffer cache."""
+    out = DeviceArray._new(plan.out_shape, dt)
+    nbytes = plan.workspace_bytes(dt.itemsize)
+    ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+    entry(q._ptr, _ptr_of(k_new), _ptr_of(v_new), k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
+          *(() if lens is None else (lens._ptr,)), *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
+    return out
+
+
+_DECODE_AXES = {"bthd": (1, 2), "bhtd": (2, 1)}       # layout -> the (time, head) axes of a cache
+
+
+def _decode_append(plan, k_cache, v_cache, k_new, v_new):
+    """The step's row by a slice assignment into cache row plan.length (nothing without a row)."""
+    if k_new is not None:
+        row = (slice(None),) * _DECODE_AXES[plan.layout][0] + (plan.length,)
+        k_cache[row] = k_new
+        v_cache[row] = v_new
+
+
+def _decode_composed(plan, q, k_cache, v_cache, k_new, v_new):
+    """The append, then attention() on its composed route over the live prefix with the heads of the caches repeated over the
+    plan's group (1 for the ungrouped forms: nothing is repeated)."""
+    _decode_append(plan, k_cache, v_cache, k_new, v_new)
+    t_axis, h_axis = _DECODE_AXES[plan.layout]
+    live = (slice(None),) * t_axis + (slice(None, plan.keys),)
+    group = getattr(plan, "group", 1)
+    q_shape = [plan.B, plan.H, plan.D]
+    q_shape.insert(t_axis, 1)
+    o, _ = attention(q.reshape(*q_shape), _gqa_expand(k_cache[live], group, h_axis), _gqa_expand(v_cache[live], group, h_axis),
+                     False, plan.scale, plan.layout, "composed")
+    return o.reshape(plan.out_shape)
+
+
+def _decode_composed_ragged(what, step, plan, dt, lens, q, k_cache, v_cache, k_new, v_new):
+    """The ragged composed route: a loop over the sequences that calls `step` (attention_decode or gqa_decode) on its composed
+    route on batch slices with the host values of the lengths; it raises inside an open capture."""
+    if _lib.capturing:
+        raise RuntimeError("%s (composed route) loops over the sequences with host lengths, which a graph capture cannot do" % what)
+    host = _ragged_mirror(lens, what)
+    out = zeros(plan.out_shape, dt)
+    for b in range(plan.B):
+        if not 0 <= int(host[b]) < plan.Tmax:
+            continue                                           # zeros, the caches untouched
+        one = slice(b, b + 1)
+        out[one] = step(q[one], k_cache[one], v_cache[one], int(host[b]), k_new[one], v_new[one], scale=plan.scale,
+                        layout=plan.layout, route="composed")
+    return out
+
+
 def attention_decode(q, k_cache, v_cache, length, k_new=None, v_new=None, scale=None, layout="bthd", route=None, splits=None):
     """o [B, H, Dv] = softmax(scale q k^T) v for ONE query per (batch, head) over the live rows of a key / value cache
     (decoding.py: layouts, the key split, the routes).  q [B, H, D].  With k_new [B, H, D] and v_new [B, H, Dv] the step's own
@@ -2002,47 +2071,23 @@ def attention_decode(q, k_cache, v_cache, length, k_new=None, v_new=None, scale=
     if (k_new is None) != (v_new is None):
         raise ValueError("attention_decode: k_new and v_new come together or not at all")
     append = k_new is not None
-    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
-    dt = cands[0] if cands else _default_float
-    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
-    q = asarray(q)._as_float(dt)._contig()
-    if append:
-        k_new, v_new = asarray(k_new)._as_float(dt)._contig(), asarray(v_new)._as_float(dt)._contig()
+    dt, q, k_cache, v_cache, k_new, v_new, _ = _decode_operands("attention_decode", q, k_cache, v_cache, k_new, v_new)
     lib = _lib.get()
     plan = _dc.plan_decode(q.shape, k_cache.shape, v_cache.shape, length, append, k_new.shape if append else None,
                            v_new.shape if append else None, scale, layout, splits, native=lib.has_decode,
-                           float_ok=dt in (np.dtype(np.float32), np.dtype(np.float64)), route=route or DECODE_ROUTE)
+                           float_ok=_decode_float_ok(dt), route=route or DECODE_ROUTE)
     if plan.empty():
         return zeros(plan.out_shape, dt)
     if plan.route == "native":
-        out = DeviceArray._new(plan.out_shape, dt)
-        nbytes = plan.workspace_bytes(dt.itemsize)
-        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
-        lib.decode_attn(q._ptr, _ptr_of(k_new), _ptr_of(v_new), k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
-                        *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
-        return out
-    n, b, h = plan.keys, plan.B, plan.H
+        return _decode_native(lib.decode_attn, plan, dt, q, k_cache, v_cache, k_new, v_new)
     if plan.route == "fwd":                                    # the route that existed before: tnn_attn_fwd with Tq = 1, in place
-        if append:
-            row = (slice(None), plan.length) if layout == "bthd" else (slice(None), slice(None), plan.length)
-            k_cache[row] = k_new
-            v_cache[row] = v_new
-        out, lse = DeviceArray._new(plan.out_shape, dt), DeviceArray._new((b, h, 1), dt)
-        lib.attn_fwd(q._ptr, k_cache._ptr, v_cache._ptr, out._ptr, lse._ptr, b, h, 1, n, plan.D, plan.Dv,
+        _decode_append(plan, k_cache, v_cache, k_new, v_new)
+        out, lse = DeviceArray._new(plan.out_shape, dt), DeviceArray._new((plan.B, plan.H, 1), dt)
+        lib.attn_fwd(q._ptr, k_cache._ptr, v_cache._ptr, out._ptr, lse._ptr, plan.B, plan.H, 1, plan.keys, plan.D, plan.Dv,
                      _i64arr(plan.q_strides + plan.kcache_strides + plan.vcache_strides + plan.o_strides), plan.scale, 0,
                      out._code())
         return out
-    if layout == "bthd":
-        if append:
-            k_cache[:, plan.length] = k_new
-            v_cache[:, plan.length] = v_new
-        o, _ = attention(q.reshape(b, 1, h, plan.D), k_cache[:, :n], v_cache[:, :n], False, plan.scale, "bthd", "composed")
-    else:
-        if append:
-            k_cache[:, :, plan.length] = k_new
-            v_cache[:, :, plan.length] = v_new
-        o, _ = attention(q.reshape(b, h, 1, plan.D), k_cache[:, :, :n], v_cache[:, :, :n], False, plan.scale, "bhtd", "composed")
-    return o.reshape(plan.out_shape)
+    return _decode_composed(plan, q, k_cache, v_cache, k_new, v_new)
 
 
 def sample_rows(logits, u, temperature=1.0, top_k=None, route=None):
@@ -2110,35 +2155,15 @@ def attention_decode_ragged(q, k_cache, v_cache, lens, k_new, v_new, scale=None,
     what = "attention_decode_ragged"
     if k_new is None or v_new is None:
         raise ValueError("%s: k_new and v_new are required (the step appends its row)" % what)
-    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
-    dt = cands[0] if cands else _default_float
-    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
-    q, k_new, v_new = (asarray(a)._as_float(dt)._contig() for a in (q, k_new, v_new))
-    ld = _ragged_state(lens, what, "lens")
+    dt, q, k_cache, v_cache, k_new, v_new, ld = _decode_operands(what, q, k_cache, v_cache, k_new, v_new, lens)
     lib = _lib.get()
     plan = _rg.plan_ragged_decode(q.shape, k_cache.shape, v_cache.shape, ld.shape, k_new.shape, v_new.shape, scale, layout,
-                                  splits, native=lib.has_ragged, float_ok=dt in (np.dtype(np.float32), np.dtype(np.float64)),
-                                  route=route or RAGGED_ROUTE)
+                                  splits, native=lib.has_ragged, float_ok=_decode_float_ok(dt), route=route or RAGGED_ROUTE)
     if plan.empty():
         return zeros(plan.out_shape, dt)
     if plan.route == "native":
-        out = DeviceArray._new(plan.out_shape, dt)
-        nbytes = plan.workspace_bytes(dt.itemsize)
-        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
-        lib.ragged_decode_attn(q._ptr, k_new._ptr, v_new._ptr, k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
-                               ld._ptr, *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
-        return out
-    if _lib.capturing:
-        raise RuntimeError("%s (composed route) loops over the sequences with host lengths, which a graph capture cannot do" % what)
-    host = _ragged_mirror(lens, what)
-    out = zeros(plan.out_shape, dt)
-    for b in range(plan.B):
-        if not 0 <= int(host[b]) < plan.Tmax:
-            continue                                           # zeros, the caches untouched
-        one = slice(b, b + 1)
-        out[one] = attention_decode(q[one], k_cache[one], v_cache[one], int(host[b]), k_new[one], v_new[one], scale=plan.scale,
-                                    layout=layout, route="composed")
-    return out
+        return _decode_native(lib.ragged_decode_attn, plan, dt, q, k_cache, v_cache, k_new, v_new, ld)
+    return _decode_composed_ragged(what, attention_decode, plan, dt, lens, q, k_cache, v_cache, k_new, v_new)
 
 
 def embedding_at(table, ids, positions, pos=None, route=None):
@@ -2335,58 +2360,19 @@ def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=No
     append = k_new is not None
     if ragged and not append:
         raise ValueError("%s: with lens= k_new and v_new are required (the step appends its row)" % what)
-    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
-    dt = cands[0] if cands else _default_float
-    k_cache, v_cache = _decode_cache(k_cache, dt, "k_cache"), _decode_cache(v_cache, dt, "v_cache")
-    q = asarray(q)._as_float(dt)._contig()
-    if append:
-        k_new, v_new = asarray(k_new)._as_float(dt)._contig(), asarray(v_new)._as_float(dt)._contig()
-    ld = _ragged_state(lens, what, "lens") if ragged else None
+    dt, q, k_cache, v_cache, k_new, v_new, ld = _decode_operands(what, q, k_cache, v_cache, k_new, v_new, lens)
     lib = _lib.get()
     plan = _gq.plan_gqa_decode(q.shape, k_cache.shape, v_cache.shape, length, append, k_new.shape if append else None,
                                v_new.shape if append else None, scale, layout, splits, ld.shape if ragged else None,
-                               native=lib.has_gqa, float_ok=dt in (np.dtype(np.float32), np.dtype(np.float64)),
-                               route=route or GQA_ROUTE)
+                               native=lib.has_gqa, float_ok=_decode_float_ok(dt), route=route or GQA_ROUTE)
     if plan.empty():
         return zeros(plan.out_shape, dt)
     if plan.route == "native":
-        out = DeviceArray._new(plan.out_shape, dt)
-        nbytes = plan.workspace_bytes(dt.itemsize)
-        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
-        if ragged:
-            lib.gqa_ragged_decode_attn(q._ptr, k_new._ptr, v_new._ptr, k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
-                                       ld._ptr, *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
-        else:
-            lib.gqa_decode_attn(q._ptr, _ptr_of(k_new), _ptr_of(v_new), k_cache._ptr, v_cache._ptr, out._ptr, _ptr_of(ws), nbytes,
-                                *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits, out._code())
-        return out
+        entry = lib.gqa_ragged_decode_attn if ragged else lib.gqa_decode_attn
+        return _decode_native(entry, plan, dt, q, k_cache, v_cache, k_new, v_new, ld)
     if ragged:
-        if _lib.capturing:
-            raise RuntimeError("%s (composed route) loops over the sequences with host lengths, which a graph capture cannot do"
-                               % what)
-        host = _ragged_mirror(lens, what)
-        out = zeros(plan.out_shape, dt)
-        for b in range(plan.B):
-            if not 0 <= int(host[b]) < plan.Tmax:
-                continue                                       # zeros, the caches untouched
-            one = slice(b, b + 1)
-            out[one] = gqa_decode(q[one], k_cache[one], v_cache[one], int(host[b]), k_new[one], v_new[one], scale=plan.scale,
-                                  layout=layout, route="composed")
-        return out
-    n, b, h = plan.keys, plan.B, plan.H
-    if layout == "bthd":
-        if append:
-            k_cache[:, plan.length] = k_new
-            v_cache[:, plan.length] = v_new
-        o, _ = attention(q.reshape(b, 1, h, plan.D), _gqa_expand(k_cache[:, :n], plan.group, 2),
-                         _gqa_expand(v_cache[:, :n], plan.group, 2), False, plan.scale, "bthd", "composed")
-    else:
-        if append:
-            k_cache[:, :, plan.length] = k_new
-            v_cache[:, :, plan.length] = v_new
-        o, _ = attention(q.reshape(b, h, 1, plan.D), _gqa_expand(k_cache[:, :, :n], plan.group, 1),
-                         _gqa_expand(v_cache[:, :, :n], plan.group, 1), False, plan.scale, "bhtd", "composed")
-    return o.reshape(plan.out_shape)
+        return _decode_composed_ragged(what, gqa_decode, plan, dt, lens, q, k_cache, v_cache, k_new, v_new)
+    return _decode_composed(plan, q, k_cache, v_cache, k_new, v_new)
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)
