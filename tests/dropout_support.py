@@ -39,7 +39,8 @@ def count_calls(monkeypatch):
     are appended to."""
     lib, seen = _lib.get(), []
     tables = [_lib._SIGNATURES, _lib._INDEX_SIGNATURES, _lib._BMM_SIGNATURES, _lib._CONV_SIGNATURES, _lib._ATTN_SIGNATURES,
-              _lib._NORM_SIGNATURES, _lib._TOKEN_SIGNATURES, _lib._DECODE_SIGNATURES, _lib._DROPOUT_SIGNATURES]
+              _lib._NORM_SIGNATURES, _lib._TOKEN_SIGNATURES, _lib._DECODE_SIGNATURES, _lib._DROPOUT_SIGNATURES,
+              _lib._GQA_SIGNATURES, _lib._RAGGED_SIGNATURES, _lib._OSTEP_SIGNATURES]
     quiet = {"malloc", "free", "last_error", "pool_stats", "stream_sync", "backend_kind"}
     for table in tables:
         for name in table:

@@ -34,6 +34,7 @@ LAYOUTS = ("bhtd", "bthd")
 class AttnPlan(object):
     __slots__ = ("B", "H", "Tq", "Tk", "D", "Dv", "layout", "causal", "scale", "q_strides", "k_strides", "v_strides",
                  "o_strides", "out_shape", "lse_shape", "route")
+    group = 1                 # query heads per key / value head (gqa.GqaAttnPlan: H / Hkv)
 
     def geometry(self):
         """The six extents every native entry point takes, in its argument order."""

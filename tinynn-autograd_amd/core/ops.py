@@ -568,27 +568,25 @@ def max_pool2d_(x, kernel, stride=None, padding=0, route=None):
 
 
 class _AttnVjp(object):
-    """The vjps of one ops.attention_ node: `fused_vjp` for Tensor.backward (only the gradients whose edges require them: dq
-    from ONE launch — which also produces delta — and dk + dv from ONE launch, written into arena views when they are lent),
-    per-edge forms for everybody else."""
-    __slots__ = ("q", "k", "v", "out", "lse", "causal", "scale", "layout", "route", "edges")
+    """The vjps of one ops.attention_ / ops.attention_gqa_ node: `fused_vjp` for Tensor.backward (only the gradients whose
+    edges require them: dq from ONE launch — which also produces delta — and dk + dv from ONE launch, written into arena views
+    when they are lent), per-edge forms for everybody else.  bwd_q / bwd_kv: the two device_array functions of the node's form
+    (grouped: dk and dv have the shapes of the Hkv-head k and v); opts: what they take besides operands, need_* and *_out."""
+    __slots__ = ("q", "k", "v", "out", "lse", "bwd_q", "bwd_kv", "opts", "edges")
 
-    def __init__(self, q, k, v, out, lse, causal, scale, layout, route):
+    def __init__(self, q, k, v, out, lse, bwd_q, bwd_kv, opts):
         self.q, self.k, self.v = q, k, v                       # saved inputs by reference, read at backward time
         self.out, self.lse = out, lse                          # the output and the per-row log-sum-exp: p is recomputed
-        self.causal, self.scale, self.layout, self.route = causal, scale, layout, route
+        self.bwd_q, self.bwd_kv, self.opts = bwd_q, bwd_kv, opts
         self.edges = ()
 
-    def _opts(self):
-        return dict(causal=self.causal, scale=self.scale, layout=self.layout, route=self.route)
-
     def _bwd_q(self, g, need_dq, dq_out=None):
-        return da.attention_bwd_q(self.q.values, self.k.values, self.v.values, self.out, g, self.lse, need_dq=need_dq,
-                                  dq_out=dq_out, **self._opts())
+        return self.bwd_q(self.q.values, self.k.values, self.v.values, self.out, g, self.lse, need_dq=need_dq, dq_out=dq_out,
+                          **self.opts)
 
     def _bwd_kv(self, g, delta, need_dk, need_dv, dk_out=None, dv_out=None):
-        return da.attention_bwd_kv(self.q.values, self.k.values, self.v.values, g, self.lse, delta, need_dk=need_dk,
-                                   need_dv=need_dv, dk_out=dk_out, dv_out=dv_out, **self._opts())
+        return self.bwd_kv(self.q.values, self.k.values, self.v.values, g, self.lse, delta, need_dk=need_dk, need_dv=need_dv,
+                           dk_out=dk_out, dv_out=dv_out, **self.opts)
 
     def d_q(self, g):
         return self._bwd_q(g, True)[0]
@@ -612,6 +610,16 @@ class _AttnVjp(object):
         return [res[name] for name in edges]
 
 
+def _attn_node(q, k, v, fwd, bwd_q, bwd_kv, **opts):
+    """The node of attention_ / attention_gqa_: `fwd` with the options, and an _AttnVjp that hands them to the backward."""
+    out, lse = fwd(q.values, k.values, v.values, **opts)
+    ctx = _AttnVjp(q, k, v, out, lse, bwd_q, bwd_kv, opts)
+    node = _make_node(q.__class__, out, [(q, ctx.d_q), (k, ctx.d_k), (v, ctx.d_v)])
+    ctx.edges = [name for name, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
 def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **unknown):
     """Scaled-dot-product attention node: softmax(scale q k^T) v, softmax over the key axis, scale = 1 / sqrt(D) by default.
 
@@ -627,29 +635,8 @@ def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **u
     route="composed" (or device_array.ATTN_ROUTE) the same mathematics runs on batched products, exp and sums."""
     if unknown:
         raise TypeError("attention_: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
-    out, lse = da.attention(q.values, k.values, v.values, causal=causal, scale=scale, layout=layout, route=route)
-    ctx = _AttnVjp(q, k, v, out, lse, causal, scale, layout, route)
-    node = _make_node(q.__class__, out, [(q, ctx.d_q), (k, ctx.d_k), (v, ctx.d_v)])
-    ctx.edges = [name for name, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad]
-    node._fused_vjp = ctx.fused_vjp
-    return node
-
-
-class _GqaVjp(_AttnVjp):
-    """The vjps of one ops.attention_gqa_ node: _AttnVjp's forms on the grouped entry points (dk and dv have the shapes of the
-    Hkv-head k and v: the group's query heads are summed inside the one dk + dv launch)."""
-    __slots__ = ()
-
-    def _opts(self):
-        return dict(causal=self.causal, scale=self.scale, route=self.route)
-
-    def _bwd_q(self, g, need_dq, dq_out=None):
-        return da.gqa_attention_bwd_q(self.q.values, self.k.values, self.v.values, self.out, g, self.lse, need_dq=need_dq,
-                                      dq_out=dq_out, **self._opts())
-
-    def _bwd_kv(self, g, delta, need_dk, need_dv, dk_out=None, dv_out=None):
-        return da.gqa_attention_bwd_kv(self.q.values, self.k.values, self.v.values, g, self.lse, delta, need_dk=need_dk,
-                                       need_dv=need_dv, dk_out=dk_out, dv_out=dv_out, **self._opts())
+    return _attn_node(q, k, v, da.attention, da.attention_bwd_q, da.attention_bwd_kv, causal=causal, scale=scale, layout=layout,
+                      route=route)
 
 
 def attention_gqa_(q, k, v, causal=False, scale=None, route=None, **unknown):
@@ -666,12 +653,8 @@ def attention_gqa_(q, k, v, causal=False, scale=None, route=None, **unknown):
     if unknown:
         raise TypeError("attention_gqa_: unsupported arguments %s (masks, dropout, bf16 and other layouts than \"bthd\" are out "
                         "of scope)" % sorted(unknown))
-    out, lse = da.gqa_attention(q.values, k.values, v.values, causal=causal, scale=scale, route=route)
-    ctx = _GqaVjp(q, k, v, out, lse, causal, scale, "bthd", route)
-    node = _make_node(q.__class__, out, [(q, ctx.d_q), (k, ctx.d_k), (v, ctx.d_v)])
-    ctx.edges = [name for name, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad]
-    node._fused_vjp = ctx.fused_vjp
-    return node
+    return _attn_node(q, k, v, da.gqa_attention, da.gqa_attention_bwd_q, da.gqa_attention_bwd_kv, causal=causal, scale=scale,
+                      route=route)
 
 
 class _NormVjp(object):

@@ -17,6 +17,7 @@ Design points
     Integer and bool operands of arithmetic are cast to the default float on device.
 """
 
+import collections
 import ctypes
 import math
 import numbers
@@ -1279,6 +1280,18 @@ def _grad_dest(out, shape, dt):
     return None
 
 
+def _dest(need, out, shape, dt, exact=False):
+    """What a launch writes a gradient of this shape into: None when it is not needed, `out` when it was lent and _grad_dest
+    accepts it (exact: and it has exactly this shape — the attention kernels address it with the operand's strides), else a
+    new array."""
+    if not need:
+        return None
+    d = _grad_dest(out, shape, dt)
+    if d is None or (exact and tuple(d.shape) != tuple(shape)):
+        return DeviceArray._new(shape, dt)
+    return d
+
+
 def conv2d_bwd_filter(x, dy, w_shape, stride=1, padding=0, with_db=True, dw_out=None, db_out=None, route=None):
     """(dw, db) of conv2d: dw[f, c, kh, kw] = sum over batch and output pixels of dy * the input under that tap, db[f] = the
     sum of dy (None when with_db is false) — both from ONE tnn_conv2d_bwd_filter launch, whose split contraction is reduced
@@ -1290,12 +1303,7 @@ def conv2d_bwd_filter(x, dy, w_shape, stride=1, padding=0, with_db=True, dw_out=
     w_shape = (plan.F, plan.C, plan.KH, plan.KW)
     if plan.route == "native":
         lib = _lib.get()
-        dw = _grad_dest(dw_out, w_shape, dt)
-        if dw is None:
-            dw = DeviceArray._new(w_shape, dt)
-        db = _grad_dest(db_out, (plan.F,), dt) if with_db else None
-        if db is None and with_db:
-            db = DeviceArray._new((plan.F,), dt)
+        dw, db = _dest(True, dw_out, w_shape, dt), _dest(with_db, db_out, (plan.F,), dt)
         splits = 1
         if dt == np.float32 and plan.N:
             splits = CONV_SPLITS if CONV_SPLITS is not None else _cv.filter_splits(plan, with_db, CONV_FORM)
@@ -1383,12 +1391,13 @@ _ATTN_MASKS = {}      # (Tq, Tk, dtype) -> [Tq, Tk] array, 0 where key j <= quer
 _ATTN_MASKS_MAX = 8   # masks kept (4 MiB each at T = 1024); trim_cache() drops them all
 
 
-def _attn_operands(*arrays):
-    """The operands as dense arrays of one float dtype, promoted the way matmul promotes (_float_result_dtype)."""
-    arrays = [asarray(a) for a in arrays]
-    cands = [a.dtype for a in arrays if a._hv is None and a.dtype.kind == "f"]
+def _operands(*arrays):
+    """The operands (None stays None) as dense arrays of one float dtype, promoted the way matmul promotes
+    (_float_result_dtype)."""
+    arrays = [None if a is None else asarray(a) for a in arrays]
+    cands = [a.dtype for a in arrays if a is not None and a._hv is None and a.dtype.kind == "f"]
     dt = _default_float if not cands else np.dtype(np.float64) if np.dtype(np.float64) in cands else np.dtype(np.float32)
-    return dt, [a._as_float(dt)._contig() for a in arrays]
+    return dt, [None if a is None else a._as_float(dt)._contig() for a in arrays]
 
 
 def _attn_plan(q, k, v, causal, scale, layout, route):
@@ -1432,31 +1441,26 @@ def _attn_scores(q, k, plan):
     return s
 
 
-def _attn_dest(out, shape, dt):
-    """`out` when the launch may write a gradient of this shape into it (a lent arena view of exactly that shape: the
-    kernels address it with the operand's strides), else None."""
-    out = _grad_dest(out, shape, dt)
-    return out if out is not None and tuple(out.shape) == tuple(shape) else None
+# What differs between the plain and the grouped-query training entry points (the rest is _attn_fwd, _attn_bwd_q, _attn_bwd_kv):
+# the planner, the library's three entry points, the prefix of the messages, and whether dk and dv are summed over the group.
+_AttnForm = collections.namedtuple("_AttnForm", "plan fwd bwd_q bwd_kv what fold")
+_PLAIN = _AttnForm(_attn_plan, "attn_fwd", "attn_bwd_q", "attn_bwd_kv", "attention", False)
 
 
-def _attn_empty(plan, dt):
-    return zeros(plan.out_shape, dt), zeros(plan.lse_shape, dt)
-
-
-def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None):
-    """(o, lse): o = softmax(scale q k^T) v over the key axis and the per-row log-sum-exp of the scaled scores (what the
-    backward recomputes the probabilities from).  Layouts, the causal rule and the routes: attention.py.  Native: ONE
-    tnn_attn_fwd launch, the scores never reach memory; composed: two batched products, max-subtract, exp, sum, divide."""
-    dt, (q, k, v) = _attn_operands(q, k, v)
-    plan = _attn_plan(q, k, v, causal, scale, layout, route)
+def _attn_fwd(form, q, k, v, causal, scale, layout, route):
+    """attention / gqa_attention.  Native: ONE call of the form's forward entry point.  Composed: k and v repeated over the
+    plan's group (1 for the plain form: nothing is repeated), two batched products, max-subtract, exp, sum, divide."""
+    dt, (q, k, v) = _operands(q, k, v)
+    plan = form.plan(q, k, v, causal, scale, layout, route)
     if plan.empty():
-        return _attn_empty(plan, dt)
+        return zeros(plan.out_shape, dt), zeros(plan.lse_shape, dt)
     if plan.route == "native":
         out = DeviceArray._new(plan.out_shape, dt)
         lse = DeviceArray._new(plan.lse_shape, dt)
-        _lib.get().attn_fwd(q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr, *plan.geometry(),
-                            _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
+        getattr(_lib.get(), form.fwd)(q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr, *plan.geometry(),
+                                      _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
         return out, lse
+    k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     s = _attn_scores(q, k, plan)
     m = s.max(axis=-1, keepdims=True)
     e = exp(s - m)
@@ -1465,34 +1469,26 @@ def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None):
     return _attn_from3(o3, plan, plan.Tq, plan.Dv), (m + log(l)).reshape(plan.lse_shape)
 
 
-def _attn_bwd_check(plan, o_shape, lse, what):
-    if tuple(o_shape) != plan.out_shape or tuple(lse.shape) != plan.lse_shape:
-        raise ValueError("%s: do / o %s and lse %s do not match the output %s and row statistics %s of this attention"
-                         % (what, tuple(o_shape), tuple(lse.shape), plan.out_shape, plan.lse_shape))
-
-
-def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd", route=None, need_dq=True, dq_out=None):
-    """(dq, delta) for the gradient `do` of attention's output: delta[i] = sum_c do[i, c] o[i, c] (what attention_bwd_kv
-    reads) and dq = scale dS k with dS = p (dP - delta), dP = do v^T, p recomputed from lse.  need_dq=False: dq is None and
-    only delta is produced (native: the key loop is skipped).  dq_out: a dense array the result is written into."""
-    dt, (q, k, v, o, do, lse) = _attn_operands(q, k, v, o, do, lse)
-    plan = _attn_plan(q, k, v, causal, scale, layout, route)
-    _attn_bwd_check(plan, o.shape, lse, "attention_bwd_q")
+def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out):
+    """attention_bwd_q / gqa_attention_bwd_q.  Native: ONE call of the form's backward-q entry point; dq_out is used when it
+    has exactly q's shape.  Composed: as _attn_fwd, on the repeated k and v."""
+    dt, (q, k, v, o, do, lse) = _operands(q, k, v, o, do, lse)
+    plan = form.plan(q, k, v, causal, scale, layout, route)
+    if tuple(o.shape) != plan.out_shape or tuple(lse.shape) != plan.lse_shape:
+        raise ValueError("%s_bwd_q: do / o %s and lse %s do not match the output %s and row statistics %s of this attention"
+                         % (form.what, tuple(o.shape), tuple(lse.shape), plan.out_shape, plan.lse_shape))
     if do.shape != plan.out_shape:
         do = do._broadcast_to(plan.out_shape)
     if plan.empty():
         return (zeros(q.shape, dt) if need_dq else None), zeros(plan.lse_shape, dt)
     if plan.route == "native":
-        dq = None
-        if need_dq:
-            dq = _attn_dest(dq_out, q.shape, dt)
-            if dq is None:
-                dq = DeviceArray._new(q.shape, dt)
+        dq = _dest(need_dq, dq_out, q.shape, dt, exact=True)
         delta = DeviceArray._new(plan.lse_shape, dt)
-        _lib.get().attn_bwd_q(q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, None if dq is None else dq._ptr, delta._ptr,
-                              *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale,
-                              int(plan.causal), delta._code())
+        getattr(_lib.get(), form.bwd_q)(q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, _ptr_of(dq), delta._ptr,
+                                        *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale,
+                                        int(plan.causal), delta._code())
         return dq, delta
+    k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     do3 = _attn3(do, plan, plan.Tq, plan.Dv)
     delta3 = (do3 * _attn3(o, plan, plan.Tq, plan.Dv)).sum(axis=-1, keepdims=True)
     dq = None
@@ -1503,16 +1499,15 @@ def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd"
     return dq, delta3.reshape(plan.lse_shape)
 
 
-def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="bhtd", route=None, need_dk=True,
-                     need_dv=True, dk_out=None, dv_out=None):
-    """(dk, dv): dv = p^T do and dk = scale dS^T q from ONE launch, with the delta attention_bwd_q produced (on the native
-    route the launch must follow that call).  need_dk / need_dv = False: that product is skipped and None returned.  A key
-    that no query sees (causal, Tk > Tq) gets exact zeros.  dk_out / dv_out: dense arrays the results are written into."""
-    dt, (q, k, v, do, lse, delta) = _attn_operands(q, k, v, do, lse, delta)
-    plan = _attn_plan(q, k, v, causal, scale, layout, route)
+def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out):
+    """attention_bwd_kv / gqa_attention_bwd_kv.  Native: ONE call of the form's backward-kv entry point; dk_out / dv_out are
+    used when they have exactly k's / v's shape.  Composed: as _attn_fwd, on the repeated k and v; the grouped form then sums
+    dk and dv over the group axis (also for a group of one)."""
+    dt, (q, k, v, do, lse, delta) = _operands(q, k, v, do, lse, delta)
+    plan = form.plan(q, k, v, causal, scale, layout, route)
     if tuple(lse.shape) != plan.lse_shape or tuple(delta.shape) != plan.lse_shape:
-        raise ValueError("attention_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
-                         % (tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
+        raise ValueError("%s_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
+                         % (form.what, tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
     if do.shape != plan.out_shape:
         do = do._broadcast_to(plan.out_shape)
     if not need_dk and not need_dv:
@@ -1520,20 +1515,12 @@ def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="
     if plan.empty():
         return (zeros(k.shape, dt) if need_dk else None), (zeros(v.shape, dt) if need_dv else None)
     if plan.route == "native":
-        dk = dv = None
-        if need_dk:
-            dk = _attn_dest(dk_out, k.shape, dt)
-            if dk is None:
-                dk = DeviceArray._new(k.shape, dt)
-        if need_dv:
-            dv = _attn_dest(dv_out, v.shape, dt)
-            if dv is None:
-                dv = DeviceArray._new(v.shape, dt)
-        _lib.get().attn_bwd_kv(q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, None if dk is None else dk._ptr,
-                               None if dv is None else dv._ptr, *plan.geometry(),
-                               _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale, int(plan.causal),
-                               lse._code())
+        dk, dv = _dest(need_dk, dk_out, k.shape, dt, exact=True), _dest(need_dv, dv_out, v.shape, dt, exact=True)
+        getattr(_lib.get(), form.bwd_kv)(q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, _ptr_of(dk), _ptr_of(dv),
+                                         *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale,
+                                         int(plan.causal), lse._code())
         return dk, dv
+    k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     rows = plan.B * plan.H
     do3 = _attn3(do, plan, plan.Tq, plan.Dv)
     p = exp(_attn_scores(q, k, plan) - lse.reshape(rows, plan.Tq, 1))
@@ -1543,21 +1530,38 @@ def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="
     if need_dk:
         ds = p * (matmul(do3, _attn3(v, plan, plan.Tk, plan.Dv), swap_b=True) - delta.reshape(rows, plan.Tq, 1))
         dk = _attn_from3(matmul(ds, _attn3(q, plan, plan.Tq, plan.D), swap_a=True) * plan.scale, plan, plan.Tk, plan.D)
+    if form.fold:
+        fold = lambda g, w: g.reshape(plan.B, plan.Tk, plan.Hkv, plan.group, w).sum(axis=3)
+        dk, dv = (None if dk is None else fold(dk, plan.D)), (None if dv is None else fold(dv, plan.Dv))
     return dk, dv
+
+
+def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None):
+    """(o, lse): o = softmax(scale q k^T) v over the key axis and the per-row log-sum-exp of the scaled scores (what the
+    backward recomputes the probabilities from).  Layouts, the causal rule and the routes: attention.py.  Native: ONE
+    tnn_attn_fwd launch, the scores never reach memory; composed: two batched products, max-subtract, exp, sum, divide."""
+    return _attn_fwd(_PLAIN, q, k, v, causal, scale, layout, route)
+
+
+def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd", route=None, need_dq=True, dq_out=None):
+    """(dq, delta) for the gradient `do` of attention's output: delta[i] = sum_c do[i, c] o[i, c] (what attention_bwd_kv
+    reads) and dq = scale dS k with dS = p (dP - delta), dP = do v^T, p recomputed from lse.  need_dq=False: dq is None and
+    only delta is produced (native: the key loop is skipped).  dq_out: a dense array the result is written into."""
+    return _attn_bwd_q(_PLAIN, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out)
+
+
+def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="bhtd", route=None, need_dk=True,
+                     need_dv=True, dk_out=None, dv_out=None):
+    """(dk, dv): dv = p^T do and dk = scale dS^T q from ONE launch, with the delta attention_bwd_q produced (on the native
+    route the launch must follow that call).  need_dk / need_dv = False: that product is skipped and None returned.  A key
+    that no query sees (causal, Tk > Tq) gets exact zeros.  dk_out / dv_out: dense arrays the results are written into."""
+    return _attn_bwd_kv(_PLAIN, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out)
 
 
 # ---------------------------------------------------------------------- kernels: layer norm, RMS norm, GELU (csrc/tnn_norm.hip)
 NORM_ROUTE = None     # tests / probes: "native" or "composed" overrides the planner's choice (norm.py)
 _GELU_C = math.sqrt(2.0 / math.pi)
 _GELU_A = 0.044715
-
-
-def _norm_operands(*arrays):
-    """The operands (None stays None) as dense arrays of one float dtype, promoted the way matmul promotes."""
-    there = [a for a in arrays if a is not None]
-    dt, dense = _attn_operands(*there)
-    dense = iter(dense)
-    return dt, [None if a is None else next(dense) for a in arrays]
 
 
 def _norm_plan(x, gamma, beta, kind, eps, route):
@@ -1570,7 +1574,7 @@ def _ptr_of(a):
 
 
 def _norm_fwd(x, gamma, beta, kind, eps, route):
-    dt, (x, gamma, beta) = _norm_operands(x, gamma, beta)
+    dt, (x, gamma, beta) = _operands(x, gamma, beta)
     plan = _norm_plan(x, gamma, beta, kind, eps, route)
     layer = kind == "layer"
     if plan.empty():
@@ -1622,7 +1626,7 @@ def norm_bwd(x, dy, gamma, mean, rstd, kind="layer", route=None, need_dx=True, n
     repeated calls give identical bits.  *_out: dense arrays the results are written into."""
     layer = kind == "layer"
     need_dbeta = need_dbeta and layer
-    dt, (x, dy, gamma, mean, rstd) = _norm_operands(x, dy, gamma, mean if layer else None, rstd)
+    dt, (x, dy, gamma, mean, rstd) = _operands(x, dy, gamma, mean if layer else None, rstd)
     plan = _norm_plan(x, gamma, None, kind, 0.0, route)
     if tuple(rstd.shape) != plan.stats_shape or (layer and (mean is None or tuple(mean.shape) != plan.stats_shape)):
         raise ValueError("norm_bwd: the row statistics must have shape %s, got mean %s and rstd %s"
@@ -1636,13 +1640,8 @@ def norm_bwd(x, dy, gamma, mean, rstd, kind="layer", route=None, need_dx=True, n
         return ((zeros(plan.x_shape, dt) if need_dx else None), (zeros(p_shape, dt) if need_dgamma else None),
                 (zeros(p_shape, dt) if need_dbeta else None))
     if plan.route == "native":
-        def dest(need, out, shape):
-            if not need:
-                return None
-            d = _grad_dest(out, shape, dt)
-            return DeviceArray._new(shape, dt) if d is None else d
-        dx, dgamma, dbeta = dest(need_dx, dx_out, plan.x_shape), dest(need_dgamma, dgamma_out, p_shape), \
-            dest(need_dbeta, dbeta_out, p_shape)
+        dx, dgamma, dbeta = _dest(need_dx, dx_out, plan.x_shape, dt), _dest(need_dgamma, dgamma_out, p_shape, dt), \
+            _dest(need_dbeta, dbeta_out, p_shape, dt)
         nbytes = plan.workspace_bytes(dt.itemsize, need_dgamma, need_dbeta)
         ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
         _lib.get().norm_bwd(x._ptr, dy._ptr, _ptr_of(gamma), _ptr_of(mean), rstd._ptr, _ptr_of(dx), _ptr_of(dgamma),
@@ -1677,7 +1676,7 @@ def gelu(x, approximate="none", route=None):
     """GELU, elementwise.  approximate="none": 0.5 x (1 + erf(x / sqrt(2))); "tanh": 0.5 x (1 + tanh(sqrt(2 / pi)
     (x + 0.044715 x^3))).  Native: ONE tnn_gelu_fwd launch.  The composed route (CPU test twin, route="composed") exists for
     the tanh form only — there is no erf among the generic elementwise operations — and the exact form raises there."""
-    dt, (x,) = _norm_operands(x)
+    dt, (x,) = _operands(x)
     if _gelu_route(x, approximate, route) == "native":
         y = DeviceArray._new(x.shape, dt)
         _lib.get().gelu_fwd(x._ptr, y._ptr, x.size, _nm.GELU_CODE[approximate], y._code())
@@ -1688,7 +1687,7 @@ def gelu(x, approximate="none", route=None):
 def gelu_bwd(x, dy, approximate="none", route=None, dx_out=None):
     """dx = dy * gelu'(x), recomputed from x (ONE tnn_gelu_bwd launch on the native route).  dx_out: a dense array the result
     is written into."""
-    dt, (x, dy) = _norm_operands(x, dy)
+    dt, (x, dy) = _operands(x, dy)
     if dy.shape != x.shape:
         dy = dy._broadcast_to(x.shape)
     if _gelu_route(x, approximate, route) == "native":
@@ -1743,7 +1742,7 @@ def dropout(x, p, residual=None, generator=None, route=None, first=0, out=None):
     into; it may be x or the residual."""
     from . import rng as _rng
     gen = _rng.default_generator if generator is None else generator
-    dt, (x, residual) = _norm_operands(x, residual)
+    dt, (x, residual) = _operands(x, residual)
     plan = _dp.plan_dropout(x.shape, p, dt, first=first, native=_lib.get().has_dropout, route=route or DROPOUT_ROUTE)
     if residual is not None and residual.shape != x.shape:
         raise ValueError("dropout: the residual must have x's shape %s, got %s" % (x.shape, residual.shape))
@@ -1786,9 +1785,7 @@ def dropout_bwd(dy, mask, dx_out=None):
         dy = dy._broadcast_to(shape)
     dy = dy._contig()
     if mask.ticket is not None:
-        dx = _grad_dest(dx_out, shape, dt)
-        if dx is None:
-            dx = DeviceArray._new(shape, dt)
+        dx = _dest(True, dx_out, shape, dt)
         plan = mask.plan
         _lib.get().dropout_bwd(mask.ticket._ptr, dy._ptr, dx._ptr, plan.first, plan.n, plan.threshold, plan.scale, dx._code())
         return dx
@@ -1818,19 +1815,12 @@ def _token_ids(ids, limit, what, also=None):
     return asarray(host), host
 
 
-def _token_dest(need, out, shape, dt):
-    if not need:
-        return None
-    d = _grad_dest(out, shape, dt)
-    return DeviceArray._new(shape, dt) if d is None else d
-
-
 def embedding(table, ids, pos=None, route=None):
     """out[..., :] = table[ids[...], :] (+ pos[t, :], t the index along the LAST axis of ids; pos may hold more rows than
     that axis is long).  table [V, E]; ids: integers of any shape, numpy / list (range-checked on the host: IndexError) or a
     device int64 array (not read back; an id outside [0, V) gives a zero token row).  Native: ONE tnn_embed_fwd launch;
     composed (tokens.py: the CPU test twin, route="composed"): a row gather and a broadcast addition."""
-    dt, (table, pos) = _norm_operands(table, pos)
+    dt, (table, pos) = _operands(table, pos)
     if table.ndim != 2:
         raise ValueError("embedding: the table must be [V, E], got shape %s" % (tuple(table.shape),))
     idd, _ = _token_ids(ids, table.shape[0], "embedding")
@@ -1856,7 +1846,7 @@ def embedding_bwd(dy, ids, table_shape, pos_shape=None, padding_idx=None, need_d
     Native: ONE tnn_embed_bwd call (a deterministic sort of the positions by token, then segmented sums: no floating-point
     atomics, identical bits on every call).  Composed: one-hot^T @ dy through matmul; the one-hot is built from a HOST copy of
     the ids, so the composed backward cannot be captured into a graph.  *_out: dense arrays the results are written into."""
-    dt, (dy,) = _norm_operands(dy)
+    dt, (dy,) = _operands(dy)
     idd, host = _token_ids(ids, int(table_shape[0]), "embedding")
     need_dpos = need_dpos and pos_shape is not None
     plan = _tk.plan_embedding(table_shape, idd.shape, pos_shape, padding_idx, native=_lib.get().has_token,
@@ -1870,7 +1860,7 @@ def embedding_bwd(dy, ids, table_shape, pos_shape=None, padding_idx=None, need_d
     if plan.empty():
         return (zeros(t_shape, dt) if need_dtable else None), (zeros(p_shape, dt) if need_dpos else None)
     if plan.route == "native":
-        dtable, dpos = _token_dest(need_dtable, dtable_out, t_shape, dt), _token_dest(need_dpos, dpos_out, p_shape, dt)
+        dtable, dpos = _dest(need_dtable, dtable_out, t_shape, dt), _dest(need_dpos, dpos_out, p_shape, dt)
         if dpos is not None and p_shape[0] > plan.T:
             dpos.fill(0.0)                                       # the launch writes the first T rows
         nbytes = plan.workspace_bytes(dt.itemsize) if need_dtable else 0
@@ -1919,7 +1909,7 @@ def cross_entropy(logits, targets, ignore_index=None, reduction="mean", route=No
     row of nothing but -inf is out of scope.  Native: ONE tnn_xent_fwd call that reads every logit once; composed: max, exp,
     sum, log and the gather x[arange, t] as a row gather of the flattened logits, which the CPU test twin has too
     (device-resident targets are read back there)."""
-    dt, (x,) = _norm_operands(logits)
+    dt, (x,) = _operands(logits)
     if x.ndim < 1:
         raise ValueError("cross_entropy: the logits need a last axis of classes, got a scalar")
     tg, host = _token_ids(targets, x.shape[-1], "cross_entropy", also=ignore_index)
@@ -1951,7 +1941,7 @@ def cross_entropy_bwd(logits, targets, lse, count, g=1.0, ignore_index=None, red
     were not counted get zeros, and count == 0 gives all zeros.  g (the gradient of the loss) and count (cross_entropy's) are
     used as DEVICE scalars on the native route — nothing is read on the host, a training step stays capturable — which is
     ONE tnn_xent_bwd launch: the logits are read once, dlogits written once.  dlogits_out: a dense array to write into."""
-    dt, (x, lse) = _norm_operands(logits, lse)
+    dt, (x, lse) = _operands(logits, lse)
     tg, host = _token_ids(targets, x.shape[-1], "cross_entropy", also=ignore_index)
     plan = _xent_plan(x, tg, ignore_index, reduction, route)
     if tuple(lse.shape) != plan.rows_shape:
@@ -1963,9 +1953,7 @@ def cross_entropy_bwd(logits, targets, lse, count, g=1.0, ignore_index=None, red
         return zeros(plan.logits_shape, dt)
     if plan.route == "native":
         gd, cd = g.astype(dt)._contig(), asarray(count).astype(dt)._contig()
-        dx = _grad_dest(dlogits_out, plan.logits_shape, dt)
-        if dx is None:
-            dx = DeviceArray._new(plan.logits_shape, dt)
+        dx = _dest(True, dlogits_out, plan.logits_shape, dt)
         _lib.get().xent_bwd(x._ptr, tg._ptr, lse._ptr, cd._ptr, gd._ptr, dx._ptr, plan.M, plan.V, plan.ignore_index,
                             _tk.REDUCTION_CODE[reduction], x._code())
         return dx
@@ -2096,7 +2084,7 @@ def sample_rows(logits, u, temperature=1.0, top_k=None, route=None):
     top_k largest).  Native: ONE tnn_sample_rows launch — nothing is read back, the ids can feed embedding() as they are.
     Composed: the logits (and u) are READ BACK and the rule runs in numpy; that is a host synchronisation and cannot be
     captured into a graph."""
-    dt, (x,) = _norm_operands(logits)
+    dt, (x,) = _operands(logits)
     lib = _lib.get()
     greedy = float(temperature) == 0.0
     ud = None
@@ -2172,7 +2160,7 @@ def embedding_at(table, ids, positions, pos=None, route=None):
     ragged.Lengths), neither is read back — an id outside [0, V) gives a zero token row, a position outside [0, Tpos) a zero
     position row.  Native: ONE tnn_ragged_embed_fwd launch; composed: two row gathers and an addition (in-range indices only)."""
     what = "embedding_at"
-    dt, (table, pos) = _norm_operands(table, pos)
+    dt, (table, pos) = _operands(table, pos)
     if table.ndim != 2 or (pos is not None and (pos.ndim != 2 or pos.shape[1] != table.shape[1])):
         raise ValueError("%s: the table must be [V, E] and pos [Tpos, E], got shapes %s and %s"
                          % (what, tuple(table.shape), None if pos is None else tuple(pos.shape)))
@@ -2259,47 +2247,22 @@ def _gqa_expand(x, group, axis=2):
     return x if group == 1 else _np_repeat(x, group, axis)
 
 
+_GROUPED = _AttnForm(lambda q, k, v, causal, scale, layout, route: _gqa_plan(q, k, v, causal, scale, route),
+                     "gqa_fwd", "gqa_bwd_q", "gqa_bwd_kv", "gqa_attention", True)
+
+
 def gqa_attention(q, k, v, causal=False, scale=None, route=None):
     """(o, lse) of grouped-query attention in layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] ->
     o [B, Tq, H, Dv], lse [B, H, Tq]; query head h reads key / value head h // (H / Hkv) (gqa.py: the checks, the routes).
     Native: ONE tnn_gqa_fwd launch, k and v are never expanded; composed: k and v repeated over the group, then attention()
     on its composed route."""
-    dt, (q, k, v) = _attn_operands(q, k, v)
-    plan = _gqa_plan(q, k, v, causal, scale, route)
-    if plan.empty():
-        return _attn_empty(plan, dt)
-    if plan.route == "native":
-        out = DeviceArray._new(plan.out_shape, dt)
-        lse = DeviceArray._new(plan.lse_shape, dt)
-        _lib.get().gqa_fwd(q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr, *plan.geometry(),
-                           _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
-        return out, lse
-    return attention(q, _gqa_expand(k, plan.group), _gqa_expand(v, plan.group), plan.causal, plan.scale, "bthd", "composed")
+    return _attn_fwd(_GROUPED, q, k, v, causal, scale, "bthd", route)
 
 
 def gqa_attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, route=None, need_dq=True, dq_out=None):
     """(dq, delta) of gqa_attention, as attention_bwd_q: delta [B, H, Tq] is what gqa_attention_bwd_kv reads; need_dq=False:
     only delta.  Native: ONE tnn_gqa_bwd_q launch."""
-    dt, (q, k, v, o, do, lse) = _attn_operands(q, k, v, o, do, lse)
-    plan = _gqa_plan(q, k, v, causal, scale, route)
-    _attn_bwd_check(plan, o.shape, lse, "gqa_attention_bwd_q")
-    if do.shape != plan.out_shape:
-        do = do._broadcast_to(plan.out_shape)
-    if plan.empty():
-        return (zeros(q.shape, dt) if need_dq else None), zeros(plan.lse_shape, dt)
-    if plan.route == "native":
-        dq = None
-        if need_dq:
-            dq = _attn_dest(dq_out, q.shape, dt)
-            if dq is None:
-                dq = DeviceArray._new(q.shape, dt)
-        delta = DeviceArray._new(plan.lse_shape, dt)
-        _lib.get().gqa_bwd_q(q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, None if dq is None else dq._ptr, delta._ptr,
-                             *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale,
-                             int(plan.causal), delta._code())
-        return dq, delta
-    return attention_bwd_q(q, _gqa_expand(k, plan.group), _gqa_expand(v, plan.group), o, do, lse, plan.causal, plan.scale, "bthd",
-                           "composed", need_dq)
+    return _attn_bwd_q(_GROUPED, q, k, v, o, do, lse, causal, scale, "bthd", route, need_dq, dq_out)
 
 
 def gqa_attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, route=None, need_dk=True, need_dv=True,
@@ -2308,35 +2271,7 @@ def gqa_attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, rout
     Native: ONE tnn_gqa_bwd_kv launch (it must follow gqa_attention_bwd_q on the stream: it reads that call's delta) — one
     workgroup per (b, key / value head, key block) adds the group's heads in ascending order and writes once.  Composed:
     attention_bwd_kv on k and v repeated over the group, then a sum over the group axis."""
-    dt, (q, k, v, do, lse, delta) = _attn_operands(q, k, v, do, lse, delta)
-    plan = _gqa_plan(q, k, v, causal, scale, route)
-    if tuple(lse.shape) != plan.lse_shape or tuple(delta.shape) != plan.lse_shape:
-        raise ValueError("gqa_attention_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
-                         % (tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
-    if do.shape != plan.out_shape:
-        do = do._broadcast_to(plan.out_shape)
-    if not need_dk and not need_dv:
-        return None, None
-    if plan.empty():
-        return (zeros(k.shape, dt) if need_dk else None), (zeros(v.shape, dt) if need_dv else None)
-    if plan.route == "native":
-        dk = dv = None
-        if need_dk:
-            dk = _attn_dest(dk_out, k.shape, dt)
-            if dk is None:
-                dk = DeviceArray._new(k.shape, dt)
-        if need_dv:
-            dv = _attn_dest(dv_out, v.shape, dt)
-            if dv is None:
-                dv = DeviceArray._new(v.shape, dt)
-        _lib.get().gqa_bwd_kv(q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, None if dk is None else dk._ptr,
-                              None if dv is None else dv._ptr, *plan.geometry(),
-                              _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale, int(plan.causal), lse._code())
-        return dk, dv
-    dk, dv = attention_bwd_kv(q, _gqa_expand(k, plan.group), _gqa_expand(v, plan.group), do, lse, delta, plan.causal, plan.scale,
-                              "bthd", "composed", need_dk, need_dv)
-    fold = lambda g, w: g.reshape(plan.B, plan.Tk, plan.Hkv, plan.group, w).sum(axis=3)
-    return (None if dk is None else fold(dk, plan.D)), (None if dv is None else fold(dv, plan.Dv))
+    return _attn_bwd_kv(_GROUPED, q, k, v, do, lse, delta, causal, scale, "bthd", route, need_dk, need_dv, dk_out, dv_out)
 
 
 def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=None, scale=None, layout="bthd", route=None,

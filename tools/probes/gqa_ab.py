@@ -11,6 +11,10 @@ alternating (the pattern of tools/probes/decode_ab.py, whose helpers it uses), f
                    4 heads), cache=True, with and without --kv-heads
 
     python tools/probes/gqa_ab.py [--repeats 5] [--inner 4] [--out profiles/gqa_vs_expanded.txt] [--quick | --subset]
+
+--host-path LABEL prints instead the wall time per call of the six training entry points of device_array (plain and grouped) at
+a shape where the launch is negligible and the Python path dominates, one line per entry point, and nothing else: run it once
+per process from the two trees to compare, alternating (profiles/attn_host_path.txt).
 """
 
 import argparse
@@ -80,6 +84,39 @@ def training_legs(b, h, t, d, group, rs):
     return {"expanded": expanded, "grouped": grouped}
 
 
+HOST_SHAPE = (2, 6, 2, 9, 12, 5, 7)          # B, H, Hkv, Tq, Tk, D, Dv of tests/test_attn_host_paths.py
+
+
+def host_path(label, batches=9, calls=2000, warm=500):
+    """us per call, native route, float32, causal: `warm` calls, then `batches` times `calls` calls back to back with one
+    synchronise at the end of each; the plain form runs H heads of k and v, the grouped one Hkv."""
+    b, h, hkv, tq, tk, d, dv = HOST_SHAPE
+    rs = np.random.RandomState(0)
+    arr = lambda *shape: tn.asarray(rs.standard_normal(shape).astype(np.float32))
+    q, g = arr(b, tq, h, d), arr(b, tq, h, dv)
+    for name, heads, fwd, bwd_q, bwd_kv, layout in (
+            ("attention", h, da.attention, da.attention_bwd_q, da.attention_bwd_kv, {"layout": "bthd"}),
+            ("gqa_attention", hkv, da.gqa_attention, da.gqa_attention_bwd_q, da.gqa_attention_bwd_kv, {})):
+        k, v = arr(b, tk, heads, d), arr(b, tk, heads, dv)
+        opts = dict(layout, causal=True, route="native")
+        o, lse = fwd(q, k, v, **opts)
+        _, delta = bwd_q(q, k, v, o, g, lse, need_dq=False, **opts)
+        for leg, fn in ((name, lambda: fwd(q, k, v, **opts)), (name + "_bwd_q", lambda: bwd_q(q, k, v, o, g, lse, **opts)),
+                        (name + "_bwd_kv", lambda: bwd_kv(q, k, v, g, lse, delta, **opts))):
+            for _ in range(warm):
+                fn()
+            took = []
+            for _ in range(batches):
+                _lib.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                _lib.synchronize()
+                took.append((time.perf_counter() - t0) / calls * 1e6)
+            print("%-7s %-24s us per call: %s  median %.3f" % (label, leg, " ".join("%.3f" % t for t in took),
+                                                              float(np.median(took))), flush=True)
+
+
 def generation_rates(lines, prompt, new):
     path = os.path.join(ROOT, "tinynn-autograd_amd", "examples", "charlm_run.py")
     spec = importlib.util.spec_from_file_location("charlm_run_example", path)
@@ -109,9 +146,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gqa_vs_expanded.txt"))
     ap.add_argument("--quick", action="store_true", help="the smallest shape of every section only (a dry run of the probe)")
     ap.add_argument("--subset", action="store_true", help="B H 8 and 64, len 4096 and 32768, D 128 only (a shorter table)")
+    ap.add_argument("--host-path", metavar="LABEL", help="only the host time per call of the six training entry points")
     args = ap.parse_args()
     assert tn.backend_name() != "cpu-twin(test only)"
     assert _lib.get().has_gqa and _lib.get().has_decode
+    if args.host_path:
+        return host_path(args.host_path)
     props = _lib.device_props()
     device = props["name"].strip() or "%d CUs" % props["cus"]
     rate = ab.copy_rate()
