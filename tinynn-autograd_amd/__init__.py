@@ -63,6 +63,8 @@ from .graph import capture
 from . import dropout
 from . import ostep
 from . import rng
+from . import rope
+from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net
 
 __version__ = "0.1.0"

@@ -75,6 +75,10 @@ from ._gqa_signatures import _GQA_SIGNATURES                  # noqa: E402  (inc
 
 GQA_SYMBOLS = sorted(_GQA_SIGNATURES)
 
+from ._rope_signatures import _ROPE_SIGNATURES                # noqa: E402  (include/tnn_rope.h: libtnn_hip.so only)
+
+ROPE_SYMBOLS = sorted(_ROPE_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -144,6 +148,8 @@ class _Lib(object):
         # host mirror of the lengths and advances the step's state in numpy (ragged.py)
         # and grouped-query attention (include/tnn_gqa.h): under the twin device_array repeats k and v over the group, runs
         # the composed attention / decode and sums dk and dv over the group (gqa.py)
+        # and the rotary position embedding (include/tnn_rope.h): under the twin device_array rotates with slice reads,
+        # products and slice assignments (rope.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -154,7 +160,8 @@ class _Lib(object):
                                     (_DROPOUT_SIGNATURES, "tnn_dropout.h", "random generator / dropout"),
                                     (_OSTEP_SIGNATURES, "tnn_ostep.h", "optimizer step"),
                                     (_RAGGED_SIGNATURES, "tnn_ragged.h", "ragged decoding step"),
-                                    (_GQA_SIGNATURES, "tnn_gqa.h", "grouped-query attention")):
+                                    (_GQA_SIGNATURES, "tnn_gqa.h", "grouped-query attention"),
+                                    (_ROPE_SIGNATURES, "tnn_rope.h", "rotary position embedding")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -175,6 +182,7 @@ class _Lib(object):
         self.has_ostep = hasattr(self.cdll, "tnn_ostep_adamw")
         self.has_ragged = hasattr(self.cdll, "tnn_ragged_decode_attn")
         self.has_gqa = hasattr(self.cdll, "tnn_gqa_decode_attn")
+        self.has_rope = hasattr(self.cdll, "tnn_rope_apply")
 
     @staticmethod
     def _absent(name, what):

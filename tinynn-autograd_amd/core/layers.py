@@ -216,11 +216,18 @@ class MultiHeadAttention(Layer):
     [E, Hkv E / num_heads] and "bk", "bv" [1, Hkv E / num_heads]; the parameter order and the order of host RNG draws are
     unchanged.  Training runs ops.attention_gqa_, the cached path keeps Hkv heads in its LayerCache — num_heads / Hkv times
     fewer bytes per token step — and runs ops.attention_decode_gqa_ / ops.attention_decode_ragged_gqa_.  None (the default)
-    is the multi-head path as it was, launch for launch; kv_heads == num_heads computes the same through the grouped ops."""
+    is the multi-head path as it was, launch for launch; kv_heads == num_heads computes the same through the grouped ops.
+
+    rope (a rope.Rotary; one may be shared by every layer of a model): q and k are rotated by ONE ops.rope_ launch after the
+    projections and before the attention op; v is never rotated and the key stored in a cache is the rotated one.  Positions:
+    0 .. T - 1 without a cache and in the prefill, cache.length in a uniform decoding step, cache.lens — read on the device —
+    in a ragged one.  Positions beyond rope.max_len raise before any launch.  None (the default): no rotation, the layer as it
+    was, launch for launch."""
 
     def __init__(self, num_heads, num_in=None, causal=False, w_init=XavierUniformInit(), b_init=ZerosInit(), fused=True,
-                 kv_heads=None):
+                 kv_heads=None, rope=None):
         super().__init__("MultiHeadAttention")
+        self.rope = rope
         num_heads = int(num_heads)
         if num_heads < 1:
             raise ValueError("MultiHeadAttention: num_heads must be >= 1, got %r" % (num_heads,))
@@ -273,11 +280,19 @@ class MultiHeadAttention(Layer):
                 raise ValueError("MultiHeadAttention: a key / value cache needs causal=True (a non-causal layer's earlier "
                                  "positions would depend on later tokens)")
             cache.check(b, t, hk, e // h)                # raises before any launch: a full cache, T > 1 after the prefill
+        if self.rope is not None:
+            self._check_rope(t, cache)                   # likewise: positions beyond the rotary tables
         self.inputs = inputs
         rows = ops.reshape(inputs, (b * t, e))
         grouped = self.kv_heads is not None
         if cache is not None and cache.length > 0:
             q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h if n == "q" else hk, e // h)) for n in "qkv")
+            if self.rope is not None:                            # the step's row sits at the cache row it is appended to
+                where = (dict(positions=cache.lens) if getattr(cache, "lens", None) is not None
+                         else dict(offset=cache.length))
+                q, k = ops.rope_(ops.reshape(q, (b, 1, h, e // h)), ops.reshape(k, (b, 1, hk, e // h)), rotary=self.rope,
+                                 route=route, **where)
+                q, k = ops.reshape(q, (b, h, e // h)), ops.reshape(k, (b, hk, e // h))
             if getattr(cache, "lens", None) is not None:         # a ragged batch: the lengths are read on the device
                 decode = ops.attention_decode_ragged_gqa_ if grouped else ops.attention_decode_ragged_
                 att = decode(q, cache.k, cache.v, cache.lens, k, v, layout="bthd", route=route)
@@ -288,6 +303,8 @@ class MultiHeadAttention(Layer):
         else:
             q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h if n == "q" else hk, e // h))
                        for n in "qkv")
+            if self.rope is not None:
+                q, k = ops.rope_(q, k, rotary=self.rope, route=route)
             if grouped:
                 att = ops.attention_gqa_(q, k, v, causal=self.causal, route=route)
             else:
@@ -296,6 +313,20 @@ class MultiHeadAttention(Layer):
                 cache.fill(k.values, v.values)
         out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
         return ops.reshape(out, (b, t, e))
+
+    def _check_rope(self, t, cache):
+        """The positions of this call against rope.max_len, on the host, before any launch."""
+        limit = self.rope.max_len
+        if cache is None or cache.length == 0:
+            first, last = 0, t - 1
+        elif getattr(cache, "lens", None) is not None:
+            host = cache.lens.host
+            first, last = (int(host.min()), int(host.max())) if host.size else (0, 0)
+        else:
+            first = last = cache.length
+        if first < 0 or last >= limit:
+            raise ValueError("MultiHeadAttention: positions %d .. %d lie outside the rotary tables' max_len %d"
+                             % (first, last, limit))
 
 
 class LayerNorm(Layer):
@@ -407,12 +438,14 @@ class TransformerBlock(Layer):
     dropout > 0: h = x + drop(MHA(LN1(x))) and out = h + drop(MLP(LN2(h))) in the TRAIN phase, both through the fused residual
     form of ops.dropout_ — its launch REPLACES the block's residual add — drawing from `generator` (None: the default
     generator of rng.py).  With dropout == 0 (the default) and in the TEST phase the block runs exactly its launches without
-    the argument.  kv_heads: handed to the attention part (grouped-query attention; None: multi-head, as it was)."""
+    the argument.  kv_heads: handed to the attention part (grouped-query attention; None: multi-head, as it was).  rope: a
+    rope.Rotary handed to the attention part (rotary position embedding of q and k; None: no rotation, as it was)."""
 
     def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True, dropout=0.0, generator=None,
-                 kv_heads=None):
+                 kv_heads=None, rope=None):
         super().__init__("TransformerBlock")
         self.kv_heads = kv_heads
+        self.rope = rope
         self.drop = Dropout(dropout, generator=generator, fused=fused)
         self.num_heads, self.hidden, self.causal, self.eps, self.fused = int(num_heads), hidden, bool(causal), float(eps), fused
         if self.num_heads < 1:
@@ -432,7 +465,7 @@ class TransformerBlock(Layer):
         parts = {}
         parts["ln1"] = LayerNorm(width, eps=self.eps, fused=self.fused)
         parts["attn"] = MultiHeadAttention(self.num_heads, num_in=width, causal=self.causal, fused=self.fused,
-                                           kv_heads=self.kv_heads)
+                                           kv_heads=self.kv_heads, rope=self.rope)
         parts["ln2"] = LayerNorm(width, eps=self.eps, fused=self.fused)
         parts["fc1"] = Dense(hidden, num_in=width, fused=self.fused)
         parts["fc2"] = Dense(width, num_in=hidden, fused=self.fused)
@@ -456,6 +489,8 @@ class TransformerBlock(Layer):
         for key in BLOCK_PARAM_ORDER:                # the flat dict is the truth (Net.set_parameters replaces its tensors)
             part, name = key.split(".")
             parts[part].params[name] = self.params[key]
+        if self.rope is not None:
+            parts["attn"]._check_rope(t, cache)          # positions beyond the rotary tables raise before ANY launch
         normed = parts["ln1"].forward(inputs)
         h = self.drop.forward(parts["attn"].forward(normed, cache=cache), residual=inputs)     # (inactive: inputs + attn)
         z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))

@@ -657,6 +657,39 @@ def attention_gqa_(q, k, v, causal=False, scale=None, route=None, **unknown):
                       route=route)
 
 
+def rope_(q, k=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, route=None, **unknown):
+    """Rotary position embedding node(s): q alone -> one tensor, q and k -> a pair, rotated by ONE tnn_rope_apply launch.
+    q [B, T, H, D] and k [B, T, Hkv, D] (layout "bthd") or [B, H, T, D] and [B, Hkv, T, D] ("bhtd"); rotary: a rope.Rotary
+    (the host-computed cos / sin tables, the rotary width R <= D and the pairing).  Row (b, t) sits at position offset + t.
+    For a pair (x_lo, x_hi) of a row at position p: y_lo = x_lo c - x_hi s, y_hi = x_hi c + x_lo s with c, s the table
+    entries; elements [R, D) pass through.  inverse=True rotates back.  float32 and float64.
+
+    Each output's vjp is the inverse rotation of its own gradient — one launch each, dq and dk arrive separately.
+    positions (a ragged.Lengths or a dense int64 device array [B]; T == 1, offset == 0) is INFERENCE ONLY: every sequence's
+    position is read on the device, so a captured decoding step keeps its arguments; the results are then LEAF tensors without
+    a grad_fn.  Under the CPU test twin and with route="composed" (or device_array.ROPE_ROUTE) the rotation runs on slice
+    reads, products and slice assignments.  Out of scope: frequency scaling (NTK / YaRN), bf16 — unknown keyword arguments
+    raise."""
+    if unknown:
+        raise TypeError("rope_: unsupported arguments %s (frequency scaling and bf16 are out of scope)" % sorted(unknown))
+    opts = dict(rotary=rotary, offset=offset, layout=layout, route=route)
+    out = da.rope(q.values, None if k is None else k.values, positions=_raw_values(positions), inverse=inverse, **opts)
+    outs = (out,) if k is None else out
+    if positions is not None:
+        res = tuple(q.__class__(o, False, []) for o in outs)
+        return res[0] if k is None else res
+
+    def node(ts, values):
+        def vjp(g):
+            g = da.asarray(g)._as_float(values.dtype)._broadcast_to(values.shape)
+            return da.rope(g, None, inverse=not inverse, **opts)
+        return build_unary_ops_tensor(ts, vjp, values)
+
+    if k is None:
+        return node(q, outs[0])
+    return node(q, outs[0]), node(k, outs[1])
+
+
 class _NormVjp(object):
     """The vjps of one ops.layer_norm_ / ops.rms_norm_ node: `fused_vjp` for Tensor.backward (ONE tnn_norm_bwd call for
     whichever of x, gamma, beta require gradients, written into arena views when they are lent), per-edge forms for
@@ -1276,6 +1309,15 @@ def attention_gqa(obj, k, v, causal=False, scale=None, **unknown):
     if unknown:
         raise TypeError("attention_gqa: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
     return attention_gqa_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale)
+
+
+def rope(obj, k=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, **unknown):
+    """not in the reference: see rope_ (rotary position embedding of one tensor or of a q / k pair; unknown keyword arguments
+    raise)"""
+    if unknown:
+        raise TypeError("rope: unsupported arguments %s (frequency scaling and bf16 are out of scope)" % sorted(unknown))
+    return rope_(as_tensor(obj), _opt_tensor(k), rotary=rotary, offset=offset, positions=positions, layout=layout,
+                 inverse=inverse)
 
 
 def attention_decode_gqa(obj, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=None, scale=None, layout="bthd",

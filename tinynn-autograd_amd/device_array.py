@@ -36,6 +36,7 @@ from . import gqa as _gq
 from . import indexing as _ix
 from . import norm as _nm
 from . import ragged as _rg
+from . import rope as _rp
 from . import tokens as _tk
 from ._lib import F32, F64, I64, U8
 
@@ -2308,6 +2309,120 @@ def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=No
     if ragged:
         return _decode_composed_ragged(what, gqa_decode, plan, dt, lens, q, k_cache, v_cache, k_new, v_new)
     return _decode_composed(plan, q, k_cache, v_cache, k_new, v_new)
+
+
+# ---------------------------------------------------------------------- kernels: rotary position embedding (csrc/tnn_rope.hip)
+ROPE_ROUTE = None     # tests / probes: "native" or "composed" overrides the planner's choice (rope.py)
+
+
+def _rope_tables(rotary, R, dt):
+    """The device tables of `rotary` for (R, dt): uploaded once, at first use, and kept at their addresses."""
+    if _lib.capturing and (int(R), dt) not in rotary._device:
+        raise RuntimeError("rope: the tables of a Rotary are uploaded at first use, which a graph capture cannot do; run one "
+                           "step outside the capture first")
+    return rotary.device_tables(R, dt, lambda host: asarray(host, dtype=dt))
+
+
+def _rope_composed(plan, x, y, cos_t, sin_t, host_positions):
+    """One tensor on the composed route: slice reads, products and slice assignments; both halves are computed before either
+    is written, so y may be x."""
+    half, R = plan.R // 2, plan.R
+    lo, hi = (slice(0, half), slice(half, R)) if plan.pairing == "half" else (slice(0, R, 2), slice(1, R, 2))
+    table_shape = (1, -1, 1, half) if plan.layout == "bthd" else (1, 1, -1, half)
+
+    def rotate(src, dst, first, rows):
+        c = cos_t[first:first + rows].reshape(*table_shape)
+        s = sin_t[first:first + rows].reshape(*table_shape)
+        if plan.inverse:
+            s = -s
+        x_lo, x_hi = src[..., lo], src[..., hi]
+        y_lo, y_hi = x_lo * c - x_hi * s, x_hi * c + x_lo * s
+        if dst is not src and R < plan.D:
+            dst[..., R:] = src[..., R:]
+        dst[..., lo] = y_lo
+        dst[..., hi] = y_hi
+
+    if host_positions is None:
+        rotate(x, y, plan.offset, plan.T)
+        return
+    for b in range(plan.B):
+        one = slice(b, b + 1)
+        pos = int(host_positions[b])
+        if 0 <= pos < plan.P:
+            rotate(x[one], y[one] if y is not x else x[one], pos, 1)
+        else:
+            y[one] = zeros(y[one].shape, y.dtype)
+
+
+def rope(xa, xb=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, route=None, blocks=0, out=None):
+    """The rotary position embedding of xa — and of xb in the same launch: ya, or (ya, yb).  xa [B, T, Ha, D] and xb
+    [B, T, Hb, D] (layout "bthd") or [B, Ha, T, D] and [B, Hb, T, D] ("bhtd"); rotary: a rope.Rotary (tables, width, pairing).
+    Row (b, t) sits at position offset + t, or — positions: a ragged.Lengths or a dense int64 device array [B], T == 1 — at
+    positions[b], read on the device (a position outside [0, max_len) gives zeros).  inverse=True is the inverse rotation,
+    which is also the vjp.  out: None (fresh arrays), "inplace" (the operands are overwritten and returned), or the output
+    array(s); rope.plan_rope states every check.  blocks: the workgroup count of the native launch (0: the library's).
+    Native: ONE tnn_rope_apply launch.  Composed (rope.py: the CPU test twin, route="composed"): slice reads, products and
+    slice assignments; with positions= it reads their host values per sequence and raises inside an open capture."""
+    what = "rope"
+    if rotary is None:
+        raise ValueError("%s: rotary= (a rope.Rotary) is required" % what)
+    arrays = [xa] if xb is None else [xa, xb]
+    cands = [a.dtype for a in arrays if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
+    dt = cands[0] if cands else _default_float
+    inplace = isinstance(out, str)
+    if inplace and out != "inplace":
+        raise ValueError("%s: out must be None, \"inplace\" or the output array(s), got %r" % (what, out))
+    xs = []
+    for a in arrays:
+        if inplace and (not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != dt):
+            raise TypeError("%s: in-place operation needs dense device arrays of one float dtype" % what)
+        xs.append(asarray(a)._as_float(dt)._contig())
+    if inplace:
+        ys = list(xs)
+    elif out is None:
+        ys = [None] * len(xs)
+    else:
+        ys = list(out) if isinstance(out, (tuple, list)) else [out]
+        if len(ys) != len(xs):
+            raise ValueError("%s: %d output arrays for %d operands" % (what, len(ys), len(xs)))
+        for x, y in zip(xs, ys):
+            if not isinstance(y, DeviceArray) or y._hv is not None or y._t or y.dtype != dt or tuple(y.shape) != tuple(x.shape):
+                raise TypeError("%s: an output must be a dense device array of the operand's shape %s and dtype %s"
+                                % (what, tuple(x.shape), dt))
+    pd = None if positions is None else _ragged_state(positions, what, "positions")
+    lib = _lib.get()
+    if len(xs[0].shape) != 4:
+        raise ValueError("%s: the operands must have four axes (layout %r), got shape %s" % (what, layout, tuple(xs[0].shape)))
+    d = int(xs[0].shape[3])
+    R = rotary.width(d)
+    float_ok = _decode_float_ok(dt)
+    known = (R, dt) in rotary._device
+    tabs = rotary._device[(R, dt)] if known else (None, None)
+    plan = _rp.plan_rope(xs[0].shape, None if xb is None else xs[1].shape, R, rotary.max_len, offset,
+                         None if pd is None else pd.shape, layout, rotary.pairing, inverse, blocks, dt.itemsize,
+                         addresses=(xs[0]._ptr, _ptr_of(ys[0]), None if xb is None else xs[1]._ptr,
+                                    None if xb is None else _ptr_of(ys[1]), _ptr_of(tabs[0]), _ptr_of(tabs[1])),
+                         native=lib.has_rope, float_ok=float_ok, route=route or ROPE_ROUTE)
+    ys = [DeviceArray._new(tuple(x.shape), dt) if y is None else y for x, y in zip(xs, ys)]
+    result = ys[0] if xb is None else (ys[0], ys[1])
+    if plan.empty():
+        return result
+    cos_t, sin_t = _rope_tables(rotary, R, dt)
+    if plan.route == "native":
+        xb_, yb_ = (xs[1], ys[1]) if xb is not None else (None, None)
+        lib.rope_apply(xs[0]._ptr, ys[0]._ptr, _ptr_of(xb_), _ptr_of(yb_), cos_t._ptr, sin_t._ptr, _ptr_of(pd),
+                       _i64arr(plan.geometry()), _i64arr(plan.strides()), plan.offset, int(plan.inverse), plan.pairing_code(),
+                       plan.blocks, ys[0]._code())
+        return result
+    host = None
+    if pd is not None:
+        if _lib.capturing:
+            raise RuntimeError("%s (composed route) reads the positions on the host, which a graph capture cannot do" % what)
+        host = _ragged_mirror(positions, what)
+    for x, y in zip(xs, ys):
+        if x.size:
+            _rope_composed(plan, x, y, cos_t, sin_t, host)
+    return result
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)

@@ -14,6 +14,11 @@ emitted after it) and --capture records the token step into a graph once and rep
 --dropout P: dropout with rate P on the embedding's output and on both residual branches of every block (the fused residual
 form of ops.dropout_), drawn from the device generator of rng.py, which --seed seeds; 0, the default, adds no launch.
 
+--rope: rotary position embeddings instead of learned positions — the blocks share ONE rope.Rotary(max_len=--seq), which
+rotates q and k of every attention layer (one launch forward, two backward, one per decoding step and block), and the
+Embedding is built without max_len, so there is no "pos" table.  It composes with --kv-heads, --generate, --ragged and
+--capture.  Default off: the run is what it was.
+
 --adamw: core/optimizer.AdamW instead of Adam — decoupled weight decay (--weight_decay, biases and norm parameters exempt),
 clipping by the global gradient norm (--clip MAX_NORM, 0 = none) and a linear warm-up over --warmup steps followed by a cosine
 decay to zero at the last step, all resident on the device (include/tnn_ostep.h).  Without --adamw the run and its launch
@@ -32,6 +37,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import tinynn_autograd_amd as tn                                                            # noqa: E402
 from tinynn_autograd_amd import ostep, rng                                                  # noqa: E402
+from tinynn_autograd_amd.rope import Rotary                                                 # noqa: E402
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
 from tinynn_autograd_amd.generation import generate                                         # noqa: E402
 from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
@@ -62,9 +68,12 @@ def make_data(rs, count, seq, vocab, period):
 def build(args):
     fused = not args.composed
     drop = args.dropout
-    net = Net([Embedding(args.vocab, args.width, max_len=args.seq, fused=fused, dropout=drop),
-               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads),
-               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads),
+    rotary = Rotary(args.seq) if getattr(args, "rope", False) else None      # shared by the blocks; then no "pos" table
+    net = Net([Embedding(args.vocab, args.width, max_len=None if rotary else args.seq, fused=fused, dropout=drop),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
+                                rope=rotary),
+               TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
+                                rope=rotary),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     loss_layer = CrossEntropyLoss(fused=fused)
     return Model(net=net, loss=loss_layer, optimizer=make_optimizer(args)), loss_layer
@@ -117,7 +126,7 @@ def main(args):
         return history
     prompt_len = 2 * args.period
     if prompt_len + args.generate > args.seq:
-        raise ValueError("--generate %d: %d prompt + %d new tokens exceed --seq %d (the learned positions)"
+        raise ValueError("--generate %d: %d prompt + %d new tokens exceed --seq %d (the learned positions, or the rotary tables)"
                          % (args.generate, prompt_len, args.generate, args.seq))
     rows = test_x[:min(len(test_x), 8)]
     if args.ragged or args.eos is not None or args.capture:
@@ -159,6 +168,8 @@ def parse(argv=None):
     parser.add_argument("--heads", default=4, type=int)
     parser.add_argument("--kv-heads", dest="kv_heads", default=None, type=int, metavar="N",
                         help="grouped-query attention: N key / value heads shared by the --heads query heads (a divisor of it)")
+    parser.add_argument("--rope", action="store_true",
+                        help="rotary position embeddings (one Rotary shared by the blocks) instead of learned positions")
     parser.add_argument("--period", default=4, type=int)
     parser.add_argument("--seed", default=0, type=int)
     parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")

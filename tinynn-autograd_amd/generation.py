@@ -22,6 +22,10 @@ dispatch per kernel.  Without these arguments the path above runs, bit for bit.
 Grouped-query heads need no concept here: a layer built with kv_heads= calls LayerCache.check and fill with its key / value
 head count and runs the grouped decode ops, whose ragged form has fixed arguments and is captured like the multi-head one.
 
+Rotary position embeddings need none either: a layer built with rope= (a rope.Rotary) rotates q and k at offset 0 in the
+prefill, at cache.length in a uniform step and at cache.lens — read on the device, at a fixed address — in a ragged step, so
+the captured step stays a replay.  generate refuses P + N (ragged: Pmax + N) beyond a layer's rope.max_len before any launch.
+
 Out of scope: chunked prefill (it needs a bottom-right causal rule), top-p, bf16, and skipping the work
 of sequences that have ended (they go on emitting the pad token; `stop_every` ends the loop once ALL have ended).
 """
@@ -164,6 +168,10 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
         limit = getattr(layer, "max_len", None)
         if limit is not None and _takes(layer, "offset") and P + N > int(limit):
             raise ValueError("generate: %d prompt + %d new tokens exceed the embedding's max_len %d" % (P, N, int(limit)))
+        rotary = getattr(layer, "rope", None)                  # (a MultiHeadAttention's or a TransformerBlock's Rotary)
+        if rotary is not None and P + N > int(rotary.max_len):
+            raise ValueError("generate: %d prompt + %d new tokens exceed the rotary tables' max_len %d"
+                             % (P, N, int(rotary.max_len)))
     temperature = float(temperature)
     if generator is not None and (u is not None or seed is not None):
         raise ValueError("generate: `generator` draws u on the device — it excludes `u` and `seed`")
