@@ -63,6 +63,7 @@ from .graph import capture
 from . import dropout
 from . import ostep
 from . import rng
+from . import gated
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

@@ -79,6 +79,10 @@ from ._rope_signatures import _ROPE_SIGNATURES                # noqa: E402  (inc
 
 ROPE_SYMBOLS = sorted(_ROPE_SIGNATURES)
 
+from ._gated_signatures import _GATED_SIGNATURES              # noqa: E402  (include/tnn_gated.h: libtnn_hip.so only)
+
+GATED_SYMBOLS = sorted(_GATED_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -150,6 +154,8 @@ class _Lib(object):
         # the composed attention / decode and sums dk and dv over the group (gqa.py)
         # and the rotary position embedding (include/tnn_rope.h): under the twin device_array rotates with slice reads,
         # products and slice assignments (rope.py)
+        # and the gated activations (include/tnn_gated.h): under the twin device_array composes them from sigmoid or tanh,
+        # products and sums on slices (gated.py; the exact-GELU gate has no composed form and raises there)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -161,7 +167,8 @@ class _Lib(object):
                                     (_OSTEP_SIGNATURES, "tnn_ostep.h", "optimizer step"),
                                     (_RAGGED_SIGNATURES, "tnn_ragged.h", "ragged decoding step"),
                                     (_GQA_SIGNATURES, "tnn_gqa.h", "grouped-query attention"),
-                                    (_ROPE_SIGNATURES, "tnn_rope.h", "rotary position embedding")):
+                                    (_ROPE_SIGNATURES, "tnn_rope.h", "rotary position embedding"),
+                                    (_GATED_SIGNATURES, "tnn_gated.h", "gated activation")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -183,6 +190,7 @@ class _Lib(object):
         self.has_ragged = hasattr(self.cdll, "tnn_ragged_decode_attn")
         self.has_gqa = hasattr(self.cdll, "tnn_gqa_decode_attn")
         self.has_rope = hasattr(self.cdll, "tnn_rope_apply")
+        self.has_gated = hasattr(self.cdll, "tnn_gated_fwd")
 
     @staticmethod
     def _absent(name, what):

@@ -11,7 +11,7 @@ Not in the reference: `Conv2D`, `MaxPool2D` and `Flatten` (NCHW; ops.conv2d_ / o
 (ops.layer_norm_ / ops.rms_norm_; "gamma" then "beta"), `GELU`, and `TransformerBlock`, a pre-norm block built from them whose
 ONE flat parameter dict has the order BLOCK_PARAM_ORDER; `Embedding` (ops.embedding_; "tok" then "pos", EMBED_PARAM_ORDER);
 `Dropout` (ops.dropout_), the one layer that reads the TRAIN / TEST flag, and the `dropout` argument of `TransformerBlock` and
-`Embedding`.
+`Embedding`; `SiLU` (ops.silu_) and the gated feed-forward `TransformerBlock(mlp="swiglu" | "geglu")` (ops.gated_).
 """
 
 from . import ops
@@ -391,6 +391,20 @@ class GELU(Activation):
         return ops.gelu_(x, approximate=self.approximate)
 
 
+class SiLU(Activation):
+    """SiLU (swish): x sigmoid(x), one launch forward and one backward (ops.silu_; `fused=False`: the composed route)."""
+
+    def __init__(self, fused=True):
+        super().__init__("SiLU")
+        self.fused = fused
+
+    def func(self, x):
+        return ops.silu_(x, route=None if self.fused else "composed")
+
+
+MLP_FORMS = {"gelu": None, "swiglu": "silu", "geglu": "gelu_tanh"}     # TransformerBlock(mlp=) -> the act of ops.gated_
+
+
 def _check_rate(p):
     from ..dropout import threshold_of
     threshold_of(p)                          # ValueError outside [0, 1)
@@ -439,11 +453,24 @@ class TransformerBlock(Layer):
     form of ops.dropout_ — its launch REPLACES the block's residual add — drawing from `generator` (None: the default
     generator of rng.py).  With dropout == 0 (the default) and in the TEST phase the block runs exactly its launches without
     the argument.  kv_heads: handed to the attention part (grouped-query attention; None: multi-head, as it was).  rope: a
-    rope.Rotary handed to the attention part (rotary position embedding of q and k; None: no rotation, as it was)."""
+    rope.Rotary handed to the attention part (rotary position embedding of q and k; None: no rotation, as it was).
+
+    mlp: "gelu" (the default) is the feed-forward above, launch for launch as it was.  "swiglu" / "geglu" is the GATED form
+
+        out = h + (act(LN2(h) Wg + bg) * (LN2(h) Wu + bu)) W2 + b2         act: silu ("swiglu") or the tanh GELU ("geglu")
+
+    with Wg and Wu held as ONE fc1.w [E, 2 hidden] — the gate columns, then the up columns — and fc1.b [1, 2 hidden]: one
+    GEMM for both projections, then the packed ops.gated_ (one launch forward; one backward that writes the packed dz, so fc1's
+    backward is one GEMM too), then fc2 [hidden, E].  BLOCK_PARAM_ORDER, the parameter names and the order of host-RNG draws
+    are unchanged; only fc1's shapes differ.  hidden defaults to 4 E for "gelu" and to 8 E / 3 rounded up to a multiple of 8
+    for the gated forms (gated.gated_hidden), which keeps the parameter count about the same."""
 
     def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True, dropout=0.0, generator=None,
-                 kv_heads=None, rope=None):
+                 kv_heads=None, rope=None, mlp="gelu"):
         super().__init__("TransformerBlock")
+        if mlp not in MLP_FORMS:
+            raise ValueError("TransformerBlock: mlp must be one of %s, got %r" % (sorted(MLP_FORMS), mlp))
+        self.mlp = mlp
         self.kv_heads = kv_heads
         self.rope = rope
         self.drop = Dropout(dropout, generator=generator, fused=fused)
@@ -460,14 +487,21 @@ class TransformerBlock(Layer):
             self._init_parameters(int(num_in))
 
     def _init_parameters(self, width):
-        hidden = 4 * width if self.hidden is None else int(self.hidden)
+        gate = MLP_FORMS[self.mlp] is not None
+        if self.hidden is not None:
+            hidden = int(self.hidden)
+        elif gate:
+            from ..gated import gated_hidden
+            hidden = gated_hidden(width)
+        else:
+            hidden = 4 * width
         # created in BLOCK_PARAM_ORDER: each part draws from the host RNG as it is built
         parts = {}
         parts["ln1"] = LayerNorm(width, eps=self.eps, fused=self.fused)
         parts["attn"] = MultiHeadAttention(self.num_heads, num_in=width, causal=self.causal, fused=self.fused,
                                            kv_heads=self.kv_heads, rope=self.rope)
         parts["ln2"] = LayerNorm(width, eps=self.eps, fused=self.fused)
-        parts["fc1"] = Dense(hidden, num_in=width, fused=self.fused)
+        parts["fc1"] = Dense(2 * hidden if gate else hidden, num_in=width, fused=self.fused)
         parts["fc2"] = Dense(width, num_in=hidden, fused=self.fused)
         self.parts, self.hidden, self.width = parts, hidden, width
         for key in BLOCK_PARAM_ORDER:
@@ -494,7 +528,11 @@ class TransformerBlock(Layer):
         normed = parts["ln1"].forward(inputs)
         h = self.drop.forward(parts["attn"].forward(normed, cache=cache), residual=inputs)     # (inactive: inputs + attn)
         z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))
-        z = ops.gelu_(z, approximate="tanh", route=None if self.fused else "composed")
+        act = MLP_FORMS[self.mlp]
+        if act is None:
+            z = ops.gelu_(z, approximate="tanh", route=None if self.fused else "composed")
+        else:
+            z = ops.gated_(z, act=act, packed=True, route=None if self.fused else "composed")
         return self.drop.forward(ops.reshape(parts["fc2"].forward(z), (b, t, e)), residual=h)
 
     def set_phase(self, phase):

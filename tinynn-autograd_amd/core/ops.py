@@ -12,7 +12,8 @@ convolution and max pooling, csrc/tnn_conv.hip; the reference has neither), `att
 csrc/tnn_attn.hip; likewise), `layer_norm_` / `rms_norm_` / `gelu_` (csrc/tnn_norm.hip; likewise), `embedding_` /
 `cross_entropy_` (csrc/tnn_token.hip; likewise — `embedding_` is the gather whose vjp ACCUMULATES over repeated ids, which
 `getitem_`'s does not), `dropout_` (csrc/tnn_dropout.hip; likewise — its mask comes from the device random generator of rng.py
-and is regenerated, not stored, for the vjp).
+and is regenerated, not stored, for the vjp), `gated_` / `silu_` (csrc/tnn_gated.hip; likewise — SwiGLU / GEGLU, both gradients
+from one launch).
 """
 
 import math
@@ -777,6 +778,47 @@ def gelu_(x, approximate="none", route=None, **unknown):
     return build_unary_ops_tensor(x, lambda g: da.gelu_bwd(xv, g, approximate=approximate, route=route), out)
 
 
+def gated_(gate, up=None, act="silu", packed=False, route=None, **unknown):
+    """Gated activation node: act(gate) * up elementwise over tensors [.., F] — SwiGLU with act="silu", GEGLU with
+    "gelu_tanh" or "gelu" (the exact form, native route only); up=None: act(gate) alone.  packed=True: `gate` is ONE tensor
+    [.., 2 F], the gate columns followed by the up columns (what one Dense(2 F) produces); both halves are read in place.
+    float32 and float64.
+
+    Forward is ONE tnn_gated_fwd launch.  Backward is ONE tnn_gated_bwd launch: the packed node's vjp writes dz [.., 2 F]
+    (dgate columns, then dup columns), so the Dense backward behind it is one GEMM; the two-tensor node gets dgate and dup from
+    the same launch, and a side that does not require a gradient is not computed.  Under the CPU test twin and with
+    route="composed" (or device_array.GATED_ROUTE) the same mathematics runs on sigmoid / tanh and products.  Out of scope:
+    bf16, a GEMM-epilogue form — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("gated_: unsupported arguments %s (bf16 and GEMM-epilogue fusion are out of scope)" % sorted(unknown))
+    gv = gate.values
+    if packed and up is not None:
+        raise ValueError("gated_: packed=True takes ONE array [.., 2 F] (gate columns, then up columns), not gate and up")
+    if packed or up is None:
+        out = da.gated(gv, None, act=act, packed=packed, route=route)
+        if packed:
+            return build_unary_ops_tensor(gate, lambda g: da.gated_bwd(gv, None, g, act=act, packed=True, route=route), out)
+        return build_unary_ops_tensor(gate, lambda g: da.gated_bwd(gv, None, g, act=act, route=route)[0], out)
+    uv = up.values
+    out = da.gated(gv, uv, act=act, route=route)
+
+    def both(g, need_dgate, need_dup):
+        return da.gated_bwd(gv, uv, g, act=act, route=route, need_dgate=need_dgate, need_dup=need_dup)
+
+    node = build_binary_ops_tensor(gate, up, lambda g: both(g, True, False)[0], lambda g: both(g, False, True)[1], out)
+    needs = (gate.requires_grad, up.requires_grad)
+    node._fused_vjp = lambda g, homes: [d for d, need in zip(both(g, *needs), needs) if need]
+    return node
+
+
+def silu_(x, route=None, **unknown):
+    """SiLU node: x * sigmoid(x) in the overflow-free form of include/tnn_gated.h — gated_ without `up`: one launch forward,
+    one backward.  Unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("silu_: unsupported arguments %s" % sorted(unknown))
+    return gated_(x, None, act="silu", route=route)
+
+
 def dropout_(x, p, residual=None, generator=None, route=None, first=0, **unknown):
     """Dropout node: keep ? x / (1 - p) : 0 elementwise, plus `residual` (a tensor of x's shape) when there is one — the fused
     residual form, in which ONE launch replaces a block's residual add.  The keep decision of an element is the 24-bit draw of
@@ -1281,6 +1323,20 @@ def gelu(obj, approximate="none", **unknown):
     if unknown:
         raise TypeError("gelu: unsupported arguments %s" % sorted(unknown))
     return gelu_(as_tensor(obj), approximate=approximate)
+
+
+def gated(obj, up=None, act="silu", packed=False, **unknown):
+    """not in the reference: see gated_ (SwiGLU / GEGLU; unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("gated: unsupported arguments %s (bf16 and GEMM-epilogue fusion are out of scope)" % sorted(unknown))
+    return gated_(as_tensor(obj), _opt_tensor(up), act=act, packed=packed)
+
+
+def silu(obj, **unknown):
+    """not in the reference: see silu_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("silu: unsupported arguments %s" % sorted(unknown))
+    return silu_(as_tensor(obj))
 
 
 def dropout(obj, p=0.5, residual=None, generator=None, **unknown):

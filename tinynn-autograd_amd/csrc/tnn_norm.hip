@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "tnn_pack.h"
+#include "tnn_gelu_math.h"
 #include "tnn_norm.h"
 
 namespace {
@@ -258,34 +259,7 @@ __global__ __launch_bounds__(256) void norm_partials_kernel(PartialJobs j) {
 }
 
 // ------------------------------------------------------------------------------------------------ GELU
-constexpr double kSqrtHalf = 0.70710678118654752440;        // 1 / sqrt(2)
-constexpr double kSqrt2OverPi = 0.79788456080286535588;     // sqrt(2 / pi)
-constexpr double kInvSqrt2Pi = 0.39894228040143267794;      // 1 / sqrt(2 pi)
-constexpr double kCubic = 0.044715;
-
-template <typename T, bool APPROX>
-__device__ __forceinline__ T gelu_value(T x) {
-    if constexpr (APPROX) {
-        const T u = (T)kSqrt2OverPi * (x + (T)kCubic * x * x * x);
-        return T(0.5) * x * (T(1) + Math<T>::tanh_(u));
-    } else {
-        return T(0.5) * x * (T(1) + Math<T>::erf_(x * (T)kSqrtHalf));
-    }
-}
-
-template <typename T, bool APPROX>
-__device__ __forceinline__ T gelu_slope(T x) {
-    if constexpr (APPROX) {
-        const T u = (T)kSqrt2OverPi * (x + (T)kCubic * x * x * x);
-        const T th = Math<T>::tanh_(u);
-        const T du = (T)kSqrt2OverPi * (T(1) + T(3) * (T)kCubic * x * x);
-        return T(0.5) * (T(1) + th) + T(0.5) * x * (T(1) - th * th) * du;
-    } else {
-        const T cdf = T(0.5) * (T(1) + Math<T>::erf_(x * (T)kSqrtHalf));
-        const T pdf = (T)kInvSqrt2Pi * Math<T>::exp_(T(-0.5) * x * x);
-        return cdf + x * pdf;
-    }
-}
+// (gelu_value / gelu_slope: tnn_gelu_math.h, shared with tnn_gated.hip)
 
 // n_wide 16-byte accesses (0 when a base is not 16-byte aligned), then the remaining elements one by one
 template <typename T, bool APPROX, bool BWD>

@@ -32,6 +32,7 @@ from . import batching as _bt
 from . import conv as _cv
 from . import decoding as _dc
 from . import dropout as _dp
+from . import gated as _gt
 from . import gqa as _gq
 from . import indexing as _ix
 from . import norm as _nm
@@ -2423,6 +2424,126 @@ def rope(xa, xb=None, rotary=None, offset=0, positions=None, layout="bthd", inve
         if x.size:
             _rope_composed(plan, x, y, cos_t, sin_t, host)
     return result
+
+
+# ---------------------------------------------------------------------- kernels: gated activations (csrc/tnn_gated.hip)
+GATED_ROUTE = None    # tests / probes: "native" or "composed" overrides the planner's choice (gated.py)
+
+
+def _gated_act(g, act):
+    """(a, act') of the composed route: a is always there, act' is a thunk evaluated only by the backward."""
+    if act == "silu":
+        sig = sigmoid(g)
+        return g * sig, lambda: sig * ((g * (1.0 - sig)) + 1.0)
+    t = _gelu_inner(g)
+    return (g * 0.5) * (t + 1.0), lambda: (t + 1.0) * 0.5 + (g * 0.5) * (1.0 - t * t) * ((g * g) * (3.0 * _GELU_A) + 1.0) * _GELU_C
+
+
+def _gated_operands(what, gate, up, dy, packed):
+    """(dt, gate, up, dy, lead shape, M, F): dense operands of one float dtype; packed: gate is [.., 2 F] and up is None."""
+    if packed and up is not None:
+        raise ValueError("%s: packed=True takes ONE array [.., 2 F] (gate columns, then up columns), not gate and up" % what)
+    dt, (gate, up, dy) = _operands(gate, up, dy)
+    if len(gate.shape) < 1:
+        raise ValueError("%s: the operands need at least one axis, got shape %s" % (what, tuple(gate.shape)))
+    last = int(gate.shape[-1])
+    if packed and last % 2:
+        raise ValueError("%s: a packed operand holds gate and up columns, its last axis must be even, got shape %s"
+                         % (what, tuple(gate.shape)))
+    f = last // 2 if packed else last
+    lead = tuple(int(s) for s in gate.shape[:-1])
+    if up is not None and tuple(up.shape) != tuple(gate.shape):
+        raise ValueError("%s: gate and up must have one shape, got %s and %s" % (what, tuple(gate.shape), tuple(up.shape)))
+    if dy is not None and tuple(dy.shape) != lead + (f,):
+        dy = dy._broadcast_to(lead + (f,))
+    return dt, gate, up, dy, lead, _prod(lead), f
+
+
+def gated(gate, up=None, act="silu", packed=False, route=None, blocks=0):
+    """y = act(gate) * up, elementwise over arrays [.., F]; up=None: y = act(gate) (act="silu": the SiLU activation).
+    act: "silu" (SwiGLU), "gelu_tanh" or "gelu" (GEGLU; gated.py).  packed=True: `gate` is ONE array [.., 2 F] — the gate
+    columns, then the up columns, what a Dense(2 F) produces — and both halves are read in place, nothing is sliced or copied.
+    Native: ONE tnn_gated_fwd launch (blocks: its workgroup count, 0 = the library's).  Composed (gated.py: the CPU test twin,
+    route="composed"): sigmoid or tanh and products on the generic operations; the exact-GELU gate raises there."""
+    what = "gated"
+    dt, gate, up, _, lead, m, f = _gated_operands(what, gate, up, None, packed)
+    lib = _lib.get()
+    item = dt.itemsize
+    has_up = packed or up is not None
+    ld = 2 * f if packed else f
+    addr = dict(gate=gate._ptr)
+    if has_up:
+        addr["up"] = gate._ptr + f * item if packed else up._ptr
+    plan = _gt.plan_gated(m, f, act, False, has_up, lds=dict(gate=ld, up=ld), addresses=addr,
+                          blocks=blocks, itemsize=item, native=lib.has_gated, float_ok=_decode_float_ok(dt),
+                          route=route or GATED_ROUTE)
+    if plan.empty():
+        return zeros(lead + (f,), dt)
+    if plan.route == "native":
+        y = DeviceArray._new(lead + (f,), dt)
+        lib.gated_fwd(addr["gate"], addr.get("up"), y._ptr, m, f, _i64arr(plan.strides()), plan.act_code(), plan.blocks,
+                      y._code())
+        return y
+    g = gate[..., :f] if packed else gate
+    u = gate[..., f:] if packed else up
+    a, _ = _gated_act(g, act)
+    return a if u is None else a * u
+
+
+def gated_bwd(gate, up, dy, act="silu", packed=False, route=None, blocks=0, need_dgate=True, need_dup=True, dz_out=None):
+    """The gradients of `gated` for the gradient dy of y, recomputed from gate: (dgate, dup) with dup = dy * act(gate) and
+    dgate = (dy * up) * act'(gate) — None for one that is not needed (need_*) and for dup without up; packed=True: ONE array
+    dz [.., 2 F] holding dgate columns, then dup columns, so the Dense backward behind it is one GEMM (dz_out: a dense array
+    it is written into).  Native: ONE tnn_gated_bwd launch for whatever is asked."""
+    what = "gated_bwd"
+    dt, gate, up, dy, lead, m, f = _gated_operands(what, gate, up, dy, packed)
+    lib = _lib.get()
+    item = dt.itemsize
+    has_up = packed or up is not None
+    if packed:
+        need_dgate = need_dup = True
+    need_dup = need_dup and has_up
+    if not (need_dgate or need_dup):
+        return None, None
+    ld = 2 * f if packed else f
+    addr = dict(gate=gate._ptr, dy=dy._ptr)
+    if has_up:
+        addr["up"] = gate._ptr + f * item if packed else up._ptr
+    dz = None
+    if packed:
+        dz = _grad_dest(dz_out, lead + (2 * f,), dt)
+        if dz is not None:
+            addr["dgate"], addr["dup"] = dz._ptr, dz._ptr + f * item
+    plan = _gt.plan_gated(m, f, act, True, has_up, need_dgate, need_dup,
+                          lds=dict(gate=ld, up=ld, dgate=ld, dup=ld), addresses=addr, blocks=blocks, itemsize=item,
+                          native=lib.has_gated, float_ok=_decode_float_ok(dt), route=route or GATED_ROUTE)
+    if plan.empty():
+        if packed:
+            return zeros(lead + (2 * f,), dt)
+        return (zeros(lead + (f,), dt) if need_dgate else None), (zeros(lead + (f,), dt) if need_dup else None)
+    if plan.route == "native":
+        if packed:
+            if dz is None:
+                dz = DeviceArray._new(lead + (2 * f,), dt)
+            lib.gated_bwd(addr["gate"], addr["up"], dy._ptr, dz._ptr, dz._ptr + f * item, m, f, _i64arr(plan.strides()),
+                          plan.act_code(), plan.blocks, dz._code())
+            return dz
+        dgate = DeviceArray._new(lead + (f,), dt) if need_dgate else None
+        dup = DeviceArray._new(lead + (f,), dt) if need_dup else None
+        lib.gated_bwd(addr["gate"], addr.get("up"), dy._ptr, _ptr_of(dgate), _ptr_of(dup), m, f, _i64arr(plan.strides()),
+                      plan.act_code(), plan.blocks, dy._code())
+        return dgate, dup
+    g = gate[..., :f] if packed else gate
+    u = gate[..., f:] if packed else up
+    a, slope = _gated_act(g, act)
+    dgate = ((dy if u is None else dy * u) * slope()) if need_dgate else None
+    dup = dy * a if need_dup else None
+    if not packed:
+        return dgate, dup
+    out = dz if dz is not None else DeviceArray._new(lead + (2 * f,), dt)
+    out[..., :f] = dgate
+    out[..., f:] = dup
+    return out
 
 
 # ---------------------------------------------------------------------- kernels: advanced indexing (csrc/tnn_index.hip)

@@ -19,6 +19,10 @@ rotates q and k of every attention layer (one launch forward, two backward, one 
 Embedding is built without max_len, so there is no "pos" table.  It composes with --kv-heads, --generate, --ragged and
 --capture.  Default off: the run is what it was.
 
+--mlp {gelu,swiglu,geglu}: the feed-forward of the blocks.  gelu (the default) is GELU(x W1 + b1) W2 + b2 as before; swiglu and
+geglu are the gated forms act(x Wg) * (x Wu) projected by W2, with Wg and Wu held as one fc1 [E, 2 hidden] and the product done
+by ONE ops.gated_ launch (csrc/tnn_gated.hip); hidden is then 8 E / 3 rounded up to a multiple of 8.
+
 --adamw: core/optimizer.AdamW instead of Adam — decoupled weight decay (--weight_decay, biases and norm parameters exempt),
 clipping by the global gradient norm (--clip MAX_NORM, 0 = none) and a linear warm-up over --warmup steps followed by a cosine
 decay to zero at the last step, all resident on the device (include/tnn_ostep.h).  Without --adamw the run and its launch
@@ -69,11 +73,12 @@ def build(args):
     fused = not args.composed
     drop = args.dropout
     rotary = Rotary(args.seq) if getattr(args, "rope", False) else None      # shared by the blocks; then no "pos" table
+    mlp = getattr(args, "mlp", "gelu")
     net = Net([Embedding(args.vocab, args.width, max_len=None if rotary else args.seq, fused=fused, dropout=drop),
                TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
-                                rope=rotary),
+                                rope=rotary, mlp=mlp),
                TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
-                                rope=rotary),
+                                rope=rotary, mlp=mlp),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     loss_layer = CrossEntropyLoss(fused=fused)
     return Model(net=net, loss=loss_layer, optimizer=make_optimizer(args)), loss_layer
@@ -170,6 +175,8 @@ def parse(argv=None):
                         help="grouped-query attention: N key / value heads shared by the --heads query heads (a divisor of it)")
     parser.add_argument("--rope", action="store_true",
                         help="rotary position embeddings (one Rotary shared by the blocks) instead of learned positions")
+    parser.add_argument("--mlp", default="gelu", choices=("gelu", "swiglu", "geglu"),
+                        help="feed-forward of the blocks: gelu (default), or the gated forms swiglu / geglu (one packed fc1)")
     parser.add_argument("--period", default=4, type=int)
     parser.add_argument("--seed", default=0, type=int)
     parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")
