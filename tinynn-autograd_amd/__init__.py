@@ -64,6 +64,7 @@ from . import dropout
 from . import ostep
 from . import rng
 from . import gated
+from . import extend
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

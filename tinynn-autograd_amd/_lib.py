@@ -83,6 +83,10 @@ from ._gated_signatures import _GATED_SIGNATURES              # noqa: E402  (inc
 
 GATED_SYMBOLS = sorted(_GATED_SIGNATURES)
 
+from ._extend_signatures import _EXTEND_SIGNATURES            # noqa: E402  (include/tnn_extend.h: libtnn_hip.so only)
+
+EXTEND_SYMBOLS = sorted(_EXTEND_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -156,6 +160,8 @@ class _Lib(object):
         # products and slice assignments (rope.py)
         # and the gated activations (include/tnn_gated.h): under the twin device_array composes them from sigmoid or tanh,
         # products and sums on slices (gated.py; the exact-GELU gate has no composed form and raises there)
+        # and cache-extending attention (include/tnn_extend.h): under the twin device_array slice-assigns the new rows and
+        # runs the composed attention over the live prefix with the offset mask (extend.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -168,7 +174,8 @@ class _Lib(object):
                                     (_RAGGED_SIGNATURES, "tnn_ragged.h", "ragged decoding step"),
                                     (_GQA_SIGNATURES, "tnn_gqa.h", "grouped-query attention"),
                                     (_ROPE_SIGNATURES, "tnn_rope.h", "rotary position embedding"),
-                                    (_GATED_SIGNATURES, "tnn_gated.h", "gated activation")):
+                                    (_GATED_SIGNATURES, "tnn_gated.h", "gated activation"),
+                                    (_EXTEND_SIGNATURES, "tnn_extend.h", "cache-extending attention")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -191,6 +198,7 @@ class _Lib(object):
         self.has_gqa = hasattr(self.cdll, "tnn_gqa_decode_attn")
         self.has_rope = hasattr(self.cdll, "tnn_rope_apply")
         self.has_gated = hasattr(self.cdll, "tnn_gated_fwd")
+        self.has_extend = hasattr(self.cdll, "tnn_extend_attn")
 
     @staticmethod
     def _absent(name, what):

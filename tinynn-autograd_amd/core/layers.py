@@ -264,7 +264,9 @@ class MultiHeadAttention(Layer):
         ops.attention_decode_ with the append, the output projection.  A cache with `lens` set (a ragged batch) takes
         ops.attention_decode_ragged_, which reads every sequence's length on the device; cache.length stays the host's upper
         bound.  None: today's path, bit for bit.  With kv_heads the cache holds the key / value heads and the grouped ops run
-        in the same places."""
+        in the same places.  A cache made with extend=True also takes T > 1 when it is filled (chunked prefill, a continued
+        sequence): q and k are rotated at offset cache.length and ONE ops.attention_extend_ attends over the cached rows and
+        the new ones and appends them; T == 1 keeps taking the decode ops."""
         if len(inputs.shape) != 3:
             raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
         b, t, e = (int(s) for s in inputs.shape)
@@ -285,7 +287,14 @@ class MultiHeadAttention(Layer):
         self.inputs = inputs
         rows = ops.reshape(inputs, (b * t, e))
         grouped = self.kv_heads is not None
-        if cache is not None and cache.length > 0:
+        if cache is not None and cache.length > 0 and t > 1:     # (cache.check let it pass: a cache made with extend=True)
+            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h if n == "q" else hk, e // h))
+                       for n in "qkv")
+            if self.rope is not None:                            # the new rows sit at the cache rows they are appended to
+                q, k = ops.rope_(q, k, rotary=self.rope, offset=cache.length, route=route)
+            att = ops.attention_extend_(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
+            cache.length += t
+        elif cache is not None and cache.length > 0:
             q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h if n == "q" else hk, e // h)) for n in "qkv")
             if self.rope is not None:                            # the step's row sits at the cache row it is appended to
                 where = (dict(positions=cache.lens) if getattr(cache, "lens", None) is not None
@@ -323,7 +332,7 @@ class MultiHeadAttention(Layer):
             host = cache.lens.host
             first, last = (int(host.min()), int(host.max())) if host.size else (0, 0)
         else:
-            first = last = cache.length
+            first, last = cache.length, cache.length + t - 1
         if first < 0 or last >= limit:
             raise ValueError("MultiHeadAttention: positions %d .. %d lie outside the rotary tables' max_len %d"
                              % (first, last, limit))

@@ -925,7 +925,8 @@ def attention_decode_(q, k_cache, v_cache, length, k_new=None, v_new=None, scale
     extended.  ONE tnn_decode_attn call, whose keys are split over enough workgroups to cover the machine (decoding.py);
     under the CPU test twin and with route="composed" (or device_array.DECODE_ROUTE) a slice assignment and the composed
     attention.  A ragged batch — every sequence at its own length — takes attention_decode_ragged_, grouped-query heads
-    attention_decode_gqa_.  Out of scope: chunked prefill, bf16 — unknown keyword arguments raise."""
+    attention_decode_gqa_, T > 1 new rows over a filled cache (chunked prefill) attention_extend_.  Out of scope: bf16 —
+    unknown keyword arguments raise."""
     if unknown:
         raise TypeError("attention_decode_: unsupported arguments %s (bf16 is out of scope; a ragged batch takes "
                         "attention_decode_ragged_, grouped-query heads attention_decode_gqa_)" % sorted(unknown))
@@ -974,7 +975,8 @@ def attention_decode_gqa_(q, k_cache, v_cache, length, k_new=None, v_new=None, s
     one read of each cached row — the cache and the bytes of a step are H / Hkv times smaller than with repeated heads.
     Composed route (CPU test twin, route="composed" or device_array.GQA_ROUTE, groups above 8): the append by a slice
     assignment and the composed attention over the live prefix repeated over the group.  The result is a LEAF tensor without
-    a grad_fn.  Out of scope: chunked prefill, bf16 — unknown keyword arguments raise."""
+    a grad_fn.  T > 1 new rows over a filled cache (chunked prefill) take attention_extend_.  Out of scope: bf16 — unknown
+    keyword arguments raise."""
     if unknown:
         raise TypeError("attention_decode_gqa_: unsupported arguments %s (bf16 is out of scope; a ragged batch takes "
                         "attention_decode_ragged_gqa_)" % sorted(unknown))
@@ -995,6 +997,25 @@ def attention_decode_ragged_gqa_(q, k_cache, v_cache, lens, k_new, v_new, scale=
         raise TypeError("attention_decode_ragged_gqa_: unsupported arguments %s (bf16 is out of scope)" % sorted(unknown))
     out = da.gqa_decode(q.values, _raw_values(k_cache), _raw_values(v_cache), None, k_new.values, v_new.values,
                         lens=_raw_values(lens), scale=scale, layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
+def attention_extend_(q, k_cache, v_cache, length, k_new, v_new, scale=None, layout="bthd", route=None, **unknown):
+    """Attention of T NEW rows per sequence over a key / value cache and over themselves, with the append, INFERENCE ONLY —
+    chunked prefill, the continuation of a cached sequence, the verification of drafted tokens.  layout "bthd": q [B, T, H, D],
+    k_new [B, T, Hkv, D], v_new [B, T, Hkv, Dv], caches [B, Tmax, Hkv, D | Dv] -> o [B, T, H, Dv] ("bhtd": heads before rows);
+    query row i sits at position length + i and sees the keys j <= length + i (the bottom-right causal rule), query head h
+    reads key / value head h // (H / Hkv) — Hkv == H is plain multi-head attention.  The caches (DeviceArrays or Tensors)
+    are modified in place: rows [length, length + T) become k_new / v_new.  `length` is a host integer shared by the batch.
+
+    The result is a LEAF tensor without a grad_fn.  ONE tnn_extend_attn call whose rows do not depend on how they are cut into
+    calls (include/tnn_extend.h); under the CPU test twin and with route="composed" (or device_array.EXTEND_ROUTE) a slice
+    assignment and the composed attention with an offset mask.  Out of scope: lengths read on the device (ragged chunks),
+    bf16 — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_extend_: unsupported arguments %s (ragged chunks and bf16 are out of scope)" % sorted(unknown))
+    out = da.attention_extend(q.values, _raw_values(k_cache), _raw_values(v_cache), length, k_new.values, v_new.values,
+                              scale=scale, layout=layout, route=route)
     return q.__class__(out, False, [])
 
 

@@ -29,7 +29,8 @@ Routes
               test twin and the second, independent implementation the GPU tests compare the kernels with.
 
 Ragged batches — a length per sequence, read on the device — are ragged.py's (csrc/tnn_ragged.hip), which reuses this planner's
-strides and split rule; grouped-query heads are gqa.py's (csrc/tnn_gqa.hip).  Out of scope: chunked prefill (it needs a bottom-right causal rule), top-p, bf16.
+strides and split rule; grouped-query heads are gqa.py's (csrc/tnn_gqa.hip).  T > 1 new rows over a filled cache (chunked
+prefill, the bottom-right causal rule) are extend.py's (csrc/tnn_extend.hip).  Out of scope: top-p, bf16.
 (u is an operand: generation.generate draws it on the host, or on the device with an rng.Generator.)
 """
 

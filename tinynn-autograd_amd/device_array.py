@@ -32,6 +32,7 @@ from . import batching as _bt
 from . import conv as _cv
 from . import decoding as _dc
 from . import dropout as _dp
+from . import extend as _ex
 from . import gated as _gt
 from . import gqa as _gq
 from . import indexing as _ix
@@ -2312,8 +2313,76 @@ def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=No
     return _decode_composed(plan, q, k_cache, v_cache, k_new, v_new)
 
 
+# ---------------------------------------------------------------------- kernels: cache-extending attention (csrc/tnn_extend.hip)
+EXTEND_ROUTE = None   # tests / probes: "native" or "composed" overrides the planner's choice (extend.py)
+
+
+def _extend_mask(t, keys, offset, dt):
+    """[t, keys]: 0 where key j <= offset + i and -inf above that diagonal; kept with the causal masks, under a key that
+    holds the offset."""
+    key = ("extend", t, keys, offset, dt)
+    m = _ATTN_MASKS.get(key)
+    if m is None:
+        if _lib.capturing:
+            raise RuntimeError("attention_extend (composed route): the mask of a new (T, keys, offset, dtype) is uploaded from "
+                               "the host, which a graph capture cannot do; run one step outside the capture first")
+        host = np.zeros((t, keys), dtype=dt)
+        host[np.triu_indices(t, offset + 1, keys)] = -np.inf
+        if len(_ATTN_MASKS) >= _ATTN_MASKS_MAX:
+            _ATTN_MASKS.clear()
+        m = _ATTN_MASKS[key] = asarray(host, dtype=dt)
+    return m
+
+
+def _extend_composed(plan, q, k_cache, v_cache, k_new, v_new):
+    """The new rows by a slice assignment, k and v repeated over the group, then the composed attention over rows
+    [0, length + T) with the offset mask."""
+    t_axis, h_axis = _DECODE_AXES[plan.layout]
+    fresh = (slice(None),) * t_axis + (slice(plan.length, plan.keys),)
+    k_cache[fresh] = k_new
+    v_cache[fresh] = v_new
+    live = (slice(None),) * t_axis + (slice(None, plan.keys),)
+    _, (k, v) = _operands(_gqa_expand(k_cache[live], plan.group, h_axis), _gqa_expand(v_cache[live], plan.group, h_axis))
+    s = matmul(_attn3(q, plan, plan.T, plan.D), _attn3(k, plan, plan.keys, plan.D), swap_b=True) * plan.scale
+    s = s + _extend_mask(plan.T, plan.keys, plan.length, s.dtype)
+    e = exp(s - s.max(axis=-1, keepdims=True))
+    o3 = matmul(e / e.sum(axis=-1, keepdims=True), _attn3(v, plan, plan.keys, plan.Dv))
+    return _attn_from3(o3, plan, plan.T, plan.Dv)
+
+
+def attention_extend(q, k_cache, v_cache, length, k_new, v_new, scale=None, layout="bthd", route=None):
+    """o = attention of T NEW rows per sequence over the `length` cached rows and over themselves, with the append
+    (extend.py: the layouts, the routes).  "bthd": q [B, T, H, D], k_new [B, T, Hkv, D], v_new [B, T, Hkv, Dv], caches
+    [B, Tmax, Hkv, D | Dv] -> o [B, T, H, Dv]; query row i sees the absolute keys j <= length + i (bottom-right causal), head h
+    reads key / value head h // (H / Hkv).  The caches are modified IN PLACE: rows [length, length + T) become k_new / v_new
+    bit for bit.  `length` is a host integer; 0 is a prefill straight into the cache.  Native: ONE tnn_extend_attn call,
+    nothing synchronises; its rows do not depend on how they are cut into calls.  Composed: a slice assignment, then two
+    batched products, the offset mask, max-subtract, exp, sum, divide."""
+    what = "attention_extend"
+    cands = [a.dtype for a in (k_cache, v_cache) if isinstance(a, DeviceArray) and a.dtype.kind == "f"]
+    dt = cands[0] if cands else _default_float
+    for a, name in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+        if not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != dt:
+            raise TypeError("%s: %s must be a dense device array of dtype %s (it is written in place)" % (what, name, dt))
+    if k_new is None or v_new is None:
+        raise ValueError("%s: k_new and v_new are required (the new rows are the call's own keys)" % what)
+    q, k_new, v_new = (asarray(a)._as_float(dt)._contig() for a in (q, k_new, v_new))
+    lib = _lib.get()
+    plan = _ex.plan_extend(q.shape, k_cache.shape, v_cache.shape, length, k_new.shape, v_new.shape, scale, layout,
+                           native=lib.has_extend, route=route or EXTEND_ROUTE, float_ok=_decode_float_ok(dt),
+                           pointers=(k_new._ptr, v_new._ptr, k_cache._ptr, v_cache._ptr))
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        lib.extend_attn(q._ptr, k_new._ptr, v_new._ptr, k_cache._ptr, v_cache._ptr, out._ptr, *plan.geometry(),
+                        _i64arr(plan.strides()), plan.scale, out._code())
+        return out
+    return _extend_composed(plan, q, k_cache, v_cache, k_new, v_new)
+
+
 # ---------------------------------------------------------------------- kernels: rotary position embedding (csrc/tnn_rope.hip)
-ROPE_ROUTE = None     # tests / probes: "native" or "composed" overrides the planner's choice (rope.py)
+ROPE_ROUTE = None    # tests / probes: "native" or "composed" overrides the planner's choice (rope.py)
 
 
 def _rope_tables(rotary, R, dt):

@@ -11,6 +11,13 @@ the motif is printed.  --ragged cuts the prompts to differing lengths between `p
 of generation.generate: the sequences' lengths live on the device), --eos ID ends a sequence at token ID (the pad token 0 is
 emitted after it) and --capture records the token step into a graph once and replays it.
 
+--prefill-chunk C runs the prompt through the net in pieces of C tokens (generation.generate(prefill_chunk=): the first piece is
+the ordinary prefill, the others extend the cache through ops.attention_extend_, csrc/tnn_extend.hip); --second-turn M keeps the
+first turn's cache (a KVCache(extend=True)) and continues it in a second generate call: its prompt is the one token the cache
+does not hold yet plus the next `period` tokens of the motif (the "user's turn": several new rows, which extend the cache in
+one launch per block), followed by M new tokens — the tokens of one call on the concatenated prompt.  Both belong to the uniform
+path (no --ragged, --eos, --capture).
+
 --dropout P: dropout with rate P on the embedding's output and on both residual branches of every block (the fused residual
 form of ops.dropout_), drawn from the device generator of rng.py, which --seed seeds; 0, the default, adds no launch.
 
@@ -43,7 +50,7 @@ import tinynn_autograd_amd as tn                                                
 from tinynn_autograd_amd import ostep, rng                                                  # noqa: E402
 from tinynn_autograd_amd.rope import Rotary                                                 # noqa: E402
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
-from tinynn_autograd_amd.generation import generate                                         # noqa: E402
+from tinynn_autograd_amd.generation import KVCache, generate                                # noqa: E402
 from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
 from tinynn_autograd_amd.core.losses import CrossEntropyLoss                                # noqa: E402
 from tinynn_autograd_amd.core.model import Model                                            # noqa: E402
@@ -130,11 +137,15 @@ def main(args):
     if args.generate <= 0:
         return history
     prompt_len = 2 * args.period
-    if prompt_len + args.generate > args.seq:
+    chunk, second = getattr(args, "prefill_chunk", None), getattr(args, "second_turn", 0)
+    total = args.generate + (args.period + second if second > 0 else 0)      # the second turn: `period` motif tokens, M new
+    if prompt_len + total > args.seq:
         raise ValueError("--generate %d: %d prompt + %d new tokens exceed --seq %d (the learned positions, or the rotary tables)"
-                         % (args.generate, prompt_len, args.generate, args.seq))
+                         % (args.generate, prompt_len, total, args.seq))
     rows = test_x[:min(len(test_x), 8)]
     if args.ragged or args.eos is not None or args.capture:
+        if chunk is not None or second > 0:
+            raise ValueError("--prefill-chunk and --second-turn belong to the uniform path: no --ragged, --eos or --capture")
         lens = np.full(len(rows), prompt_len)
         if args.ragged:                                     # prompts of period .. 2 period tokens, the same in every run
             lens = args.period + np.arange(len(rows)) % (args.period + 1)
@@ -150,13 +161,27 @@ def main(args):
               % (args.generate, len(out), lens.min(), lens.max(), share))
         args.generation = (out, share)
         return history
-    out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0)
+    kept = KVCache(args.seq, extend=True) if second > 0 else True       # the first turn's cache, kept for the second
+    out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, cache=kept, prefill_chunk=chunk)
     motif = rows[:, np.arange(prompt_len, prompt_len + args.generate) % args.period]     # what repeating the motif gives
     share = float((out[:, prompt_len:] == motif).mean())
     for row in out:
         print("  %s | %s" % (" ".join("%2d" % t for t in row[:prompt_len]), " ".join("%2d" % t for t in row[prompt_len:])))
     print("generated %d tokens for %d sequences: %.4f of them continue the motif" % (args.generate, len(out), share))
     args.generation = (out, share)
+    args.second = None                  # with --second-turn: (ids [rows, 1 + period + M] of the second call, equal to one call's)
+    if second > 0:
+        # the cache holds every token but the last one generated; the second prompt is that token and the motif's next period
+        at = prompt_len + args.generate
+        turn = np.concatenate([out[:, -1:], rows[:, np.arange(at, at + args.period) % args.period]], axis=1)
+        more = generate(model, turn, second, temperature=0.0, cache=kept)
+        whole = generate(model, np.concatenate([out, turn[:, 1:]], axis=1), second, temperature=0.0)
+        same = bool(np.array_equal(more[:, -second:], whole[:, -second:]))
+        for row in more:
+            print("  ... %s | %s" % (" ".join("%2d" % t for t in row[:-second]), " ".join("%2d" % t for t in row[-second:])))
+        print("second turn: %d prompt + %d new tokens on the kept cache (%d rows now): %s one call on the concatenated prompt"
+              % (turn.shape[1], second, kept.length, "the tokens of" if same else "DIFFERENT from"))
+        args.second = (more, same)
     return history
 
 
@@ -184,6 +209,10 @@ def parse(argv=None):
     parser.add_argument("--ragged", action="store_true", help="--generate: prompts of differing lengths (period .. 2 period tokens)")
     parser.add_argument("--eos", default=None, type=int, metavar="ID", help="--generate: a sequence ends at token ID")
     parser.add_argument("--capture", action="store_true", help="--generate: record the token step into a graph and replay it")
+    parser.add_argument("--prefill-chunk", dest="prefill_chunk", default=None, type=int, metavar="C",
+                        help="--generate: run the prompt in pieces of C tokens (the pieces after the first extend the cache)")
+    parser.add_argument("--second-turn", dest="second_turn", default=0, type=int, metavar="M",
+                        help="--generate: keep the cache and continue it by M more tokens in a second call")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
     parser.add_argument("--adamw", action="store_true", help="AdamW on the device instead of Adam")
     parser.add_argument("--weight_decay", default=0.01, type=float, help="--adamw: decoupled weight decay")

@@ -26,7 +26,14 @@ Rotary position embeddings need none either: a layer built with rope= (a rope.Ro
 prefill, at cache.length in a uniform step and at cache.lens — read on the device, at a fixed address — in a ragged step, so
 the captured step stays a replay.  generate refuses P + N (ragged: Pmax + N) beyond a layer's rope.max_len before any launch.
 
-Out of scope: chunked prefill (it needs a bottom-right causal rule), top-p, bf16, and skipping the work
+Chunked prefill and continuation (include/tnn_extend.h).  A cache made with extend=True also takes T > 1 new tokens when
+it is filled: the layer rotates them at offset cache.length and runs ops.attention_extend_, which attends over the cached
+rows and the new ones (the bottom-right causal rule) and appends them in ONE launch.  generate(prefill_chunk=C) runs the
+prompt as ceil(P / C) pieces — the first through the ordinary prefill, the rest through the extension — and
+generate(cache=a KVCache(extend=True)) continues the sequence an earlier call left in that cache.  The default cache
+refuses T > 1 on a filled cache as before.
+
+Out of scope: ragged chunks (lengths read on the device with T > 1), top-p, bf16, and skipping the work
 of sequences that have ended (they go on emitting the pad token; `stop_every` ends the loop once ALL have ended).
 """
 
@@ -45,21 +52,27 @@ class LayerCache(object):
     """The keys and values of ONE attention layer: k [B, max_len, H, D], v [B, max_len, H, D] (layout "bthd": what a
     [B T, H D] projection reshapes to), allocated from the first batch, and the number of live rows."""
 
-    def __init__(self, max_len, lens=None):
+    def __init__(self, max_len, lens=None, extend=False):
         self.max_len, self.length, self.k, self.v = int(max_len), 0, None, None
+        self.extend = bool(extend)     # a filled cache also takes T > 1 new rows (ops.attention_extend_); False: ONE per step
         self.lens = lens     # a ragged.Lengths: every sequence's own live rows, read on the device; `length` is then the
                              # host's upper bound (what check() uses)
 
     def check(self, b, t, h, d):
         """What MultiHeadAttention.forward asks BEFORE any launch."""
+        if self.extend and self.lens is not None:
+            raise ValueError("KVCache: extend=True with per-sequence lengths (ragged extension is out of scope)")
         if self.length == 0:
             if t > self.max_len:
                 raise ValueError("KVCache: a prompt of %d tokens exceeds the cache's %d rows" % (t, self.max_len))
             return
-        if t != 1:
+        if self.extend:
+            if t < 1 or self.length + t > self.max_len:
+                raise ValueError("KVCache: %d cached + %d new tokens overflow the cache's %d rows" % (self.length, t, self.max_len))
+        elif t != 1:
             raise ValueError("KVCache: the cache holds %d tokens — a step takes ONE new token per sequence, got T = %d "
                              "(chunked prefill is out of scope)" % (self.length, t))
-        if self.length >= self.max_len:
+        elif self.length >= self.max_len:
             raise ValueError("KVCache: the cache is full (%d of %d rows)" % (self.length, self.max_len))
         if tuple(self.k.shape) != (b, self.max_len, h, d):
             raise ValueError("KVCache: the cache was allocated for [B, H, D] = %s, got %s"
@@ -78,15 +91,15 @@ class LayerCache(object):
 class KVCache(object):
     """One LayerCache per layer that takes `cache`, made on demand: `cache.layer(i)` is layer i's."""
 
-    def __init__(self, max_len, lens=None):
+    def __init__(self, max_len, lens=None, extend=False):
         max_len = int(max_len)
         if max_len < 1:
             raise ValueError("KVCache: max_len must be >= 1, got %d" % max_len)
-        self.max_len, self.layers, self.lens = max_len, {}, lens
+        self.max_len, self.layers, self.lens, self.extend = max_len, {}, lens, bool(extend)
 
     def layer(self, index):
         if index not in self.layers:
-            self.layers[index] = LayerCache(self.max_len, self.lens)
+            self.layers[index] = LayerCache(self.max_len, self.lens, self.extend)
         return self.layers[index]
 
     def set_lens(self, lens):
@@ -142,7 +155,8 @@ def _forward(layers, ids, offset, cache, positions=None):
 
 
 def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=None, u=None, seed=None, cache=True,
-             generator=None, prompt_lens=None, eos_id=None, pad_id=0, capture=False, stop_every=None, return_lengths=False):
+             generator=None, prompt_lens=None, eos_id=None, pad_id=0, capture=False, stop_every=None, return_lengths=False,
+             prefill_chunk=None):
     """Continue `prompt_ids` [B, P] (integers) by `max_new_tokens` tokens -> numpy int64 [B, P + N].
 
     prompt_lens, eos_id, pad_id, capture, stop_every, return_lengths: the RAGGED path (_generate_ragged states them); with
@@ -154,6 +168,13 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
     call of the generator (stream element n B + b is u[n, b]); it excludes `u` and `seed`, and temperature 0 draws nothing.
     cache=True: a KVCache — the prompt runs once, every new token costs one row per layer.  cache=False: the whole growing
     prefix runs through the net every step — the independent route, and what the CPU test twin compares with.
+    cache=a KVCache(extend=True): the caller's cache is used and kept.  Empty, it behaves as cache=True; holding L > 0 rows
+    from an earlier call, prompt_ids are the NEW tokens at positions L .. L + P - 1 — they run through the extension
+    (ops.attention_extend_) — the result is still [B, P + N], and nothing new is allocated for the cache.  Either way it is
+    left at L + P + N - 1 rows, and L + P + N must fit its max_len, the embedding's and the rotary tables'.
+    prefill_chunk=C (an integer >= 1; this path only, with a cache): the prompt runs as ceil(P / C) pieces — the first through
+    the ordinary prefill (the extension when L > 0), the rest through the extension at the offset of the rows already cached;
+    the pieces before the last stop behind the last layer that takes the cache, so only the last piece reaches the head.
     The net runs in phase TEST; the previous phase is restored.  P + N beyond an Embedding's max_len raises before any launch."""
     net = getattr(model_or_net, "net", model_or_net)
     layers = net.layers
@@ -164,14 +185,34 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
     N = int(max_new_tokens)
     if N < 0:
         raise ValueError("generate: max_new_tokens must be >= 0, got %d" % N)
+    ragged = prompt_lens is not None or eos_id is not None or capture or stop_every is not None or return_lengths
+    kept = cache if isinstance(cache, KVCache) else None       # the caller's cache: continued, and left to the caller
+    if kept is not None:
+        if ragged:
+            raise ValueError("generate: a kept KVCache continues the uniform path — it excludes prompt_lens, eos_id, capture, "
+                             "stop_every and return_lengths")
+        if not kept.extend or kept.lens is not None:
+            raise ValueError("generate: cache= takes True, False or a KVCache(extend=True) without per-sequence lengths")
+        if any(c.k is not None and int(c.k.shape[0]) != B for c in kept.layers.values()):
+            raise ValueError("generate: the kept KVCache was filled by a batch of another size than B = %d" % B)
+    L = kept.length if kept is not None else 0                 # the rows an earlier call left in the cache
+    if prefill_chunk is not None:
+        if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, (int, np.integer)) or prefill_chunk < 1:
+            raise ValueError("generate: prefill_chunk must be an integer >= 1, got %r" % (prefill_chunk,))
+        if ragged or not cache:
+            raise ValueError("generate: prefill_chunk cuts the prompt of the uniform cached path — it excludes cache=False, "
+                             "prompt_lens, eos_id, capture, stop_every and return_lengths")
+    past = "" if L == 0 else "%d cached + " % L
     for layer in layers:
         limit = getattr(layer, "max_len", None)
-        if limit is not None and _takes(layer, "offset") and P + N > int(limit):
-            raise ValueError("generate: %d prompt + %d new tokens exceed the embedding's max_len %d" % (P, N, int(limit)))
+        if limit is not None and _takes(layer, "offset") and L + P + N > int(limit):
+            raise ValueError("generate: %s%d prompt + %d new tokens exceed the embedding's max_len %d" % (past, P, N, int(limit)))
         rotary = getattr(layer, "rope", None)                  # (a MultiHeadAttention's or a TransformerBlock's Rotary)
-        if rotary is not None and P + N > int(rotary.max_len):
-            raise ValueError("generate: %d prompt + %d new tokens exceed the rotary tables' max_len %d"
-                             % (P, N, int(rotary.max_len)))
+        if rotary is not None and L + P + N > int(rotary.max_len):
+            raise ValueError("generate: %s%d prompt + %d new tokens exceed the rotary tables' max_len %d"
+                             % (past, P, N, int(rotary.max_len)))
+    if kept is not None and L + P + N > kept.max_len:
+        raise ValueError("generate: %s%d prompt + %d new tokens exceed the cache's max_len %d" % (past, P, N, kept.max_len))
     temperature = float(temperature)
     if generator is not None and (u is not None or seed is not None):
         raise ValueError("generate: `generator` draws u on the device — it excludes `u` and `seed`")
@@ -182,7 +223,7 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
         if u.shape != (N, B) or (u.size and not (u.min() >= 0.0 and u.max() < 1.0)):
             raise ValueError("generate: u must be [N, B] = %s numbers in [0, 1), got shape %s" % ((N, B), u.shape))
     host = np.ascontiguousarray(host, dtype=np.int64)
-    if prompt_lens is not None or eos_id is not None or capture or stop_every is not None or return_lengths:
+    if ragged:
         return _generate_ragged(model_or_net, layers, host, N, temperature, top_k, u, cache, generator, prompt_lens, eos_id,
                                 pad_id, capture, stop_every, return_lengths)
     if N == 0 or B == 0:
@@ -194,12 +235,19 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
         out = da.zeros((B, P + N), np.int64)                   # every id of the run, on the device
         out[:, :P] = da.asarray(host)
         u_dev = None                                           # uploaded ONCE, in the dtype of the logits
-        kv = KVCache(P + N) if cache else None
+        kv = kept if kept is not None else KVCache(P + N, extend=prefill_chunk is not None) if cache else None
         for n in range(N):
             if cache and n > 0:
-                ids, offset = out[:, P + n - 1:P + n], P + n - 1
+                ids, offset = out[:, P + n - 1:P + n], L + P + n - 1
             else:
-                ids, offset = out[:, :P + n], 0
+                ids, offset = out[:, :P + n], L
+            if cache and n == 0 and prefill_chunk is not None and prefill_chunk < P:
+                # the pieces before the last fill the cache and stop behind the last layer that takes it
+                body = 1 + max([i for i, layer in enumerate(layers) if _takes(layer, "cache")] or [-1])
+                first = (P - 1) // prefill_chunk * prefill_chunk           # where the last piece starts
+                for s0 in range(0, first, prefill_chunk):
+                    _forward(layers[:body], Tensor(out[:, s0:s0 + prefill_chunk]), L + s0, kv)
+                ids, offset = out[:, first:P], L + first
             t = int(ids.shape[1])
             logits = _forward(layers, Tensor(ids), offset, kv)
             vocab = int(logits.shape[-1])

@@ -20,7 +20,8 @@ Routes
               composed decode loops over the sequences on the host and raises inside an open graph capture.
 
 No routing rule between the two is drawn from measurements yet (profiles/gqa_vs_expanded.txt is written by
-tools/probes/gqa_ab.py).  Out of scope: groups above MAX_GROUP on the native route, bf16, chunked prefill.
+tools/probes/gqa_ab.py).  Out of scope: groups above MAX_GROUP on the native route, bf16 (chunked
+prefill over grouped caches is extend.py's).
 """
 
 from . import attention as _at
