@@ -4,6 +4,7 @@
 // own launches.  The kernels live in the tnn_gemm_*.h fragments below, one kernel family each; this stays ONE translation unit.
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -140,6 +141,30 @@ void fill_small_fast(GemmArgs& g, bool akc, bool bkc) {
     f.hc4 = (uint32_t)g.head_c * 4u;
 }
 
+// Which form of its first-request arguments the last launch of the 16 x 16 latency kernel took (tnn_step_args_form):
+// 1 = fourteen leading scalars, preloaded into user SGPRs (gemm_small_pre_f32_kernel), 0 = the argument block alone
+// (the switch below, an order that does not pack, or operands the FAST form does not take), -1 = none launched yet.
+int g_small_args_form = -1;
+int g_bwd0_args_form = -1;           // the same for the last first-layer backward + Adam launch (tnn_dense_bwd_first_adam)
+
+// TNN_STEP_ARGS=struct keeps every launch on the argument-block kernels, TNN_STEP_ARGS=struct:fwd16,bwd0 only the named parts
+// (fwd4 / fwd8 / fwd16: the FAST 16 x 16 kernel by waves per workgroup; bwd0; head: read in tnn_head.hip).  An A/B switch: read per
+// call, not cached.
+bool step_args_struct_forced(const char* part) {
+    const char* e = getenv("TNN_STEP_ARGS");
+    if (e == nullptr || strncmp(e, "struct", 6) != 0) return false;
+    return e[6] == 0 || (e[6] == ':' && strstr(e + 7, part) != nullptr);
+}
+
+// The FAST forward kernel is preloaded only in launches whose workgroups are all placed at once.  Measured on this kernel
+// alone: there every workgroup's way from entry to its first request is on the launch's critical path and the scalar-memory
+// round trip for the argument segment is a fifth of it; with several rounds of workgroups per CU the wait hides under the
+// workgroups already running, while sixteen user SGPRs per wave instead of six are more for the dispatcher to write — the
+// 1024-row step was 0.25 us SLOWER with every FAST launch preloaded (profiles/step_arg_sgprs_ab.txt).  The rule is this
+// kernel's, not a law: the first-layer backward + Adam (392 + 34 workgroups, 1.5 per CU, all resident together) is preloaded
+// without it and gains 0.5 us, because the preload takes TWO dependent round trips out of every tile workgroup's prologue.
+bool placed_at_once(int64_t workgroups) { return workgroups <= tnn::num_cus(); }
+
 template <int WAVES>
 int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
     small_geometry(g);
@@ -148,6 +173,20 @@ int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
     const bool fast = small_fast_ok(g, transA, transB);
     pick_xcd_cut(g);
     if (fast) fill_small_fast(g, !transA, transB != 0);
+    tnn::PackedTileOrder po;
+    const char* part = WAVES == 4 ? "fwd4" : WAVES == 8 ? "fwd8" : "fwd16";
+    if (fast && placed_at_once(grid.x) && !step_args_struct_forced(part) && tnn::pack_tile_order(g.ord, po)) {
+        const SmallFast& f = g.f;
+        po.w[2] |= (f.h_bytes != 0u ? FAST_FLAG_HEAD : 0u) << tnn::kPackedOrderFlagShift;
+        with_layout(transA, transB, [&](auto akc, auto bkc) {
+            hipLaunchKernelGGL((gemm_small_pre_f32_kernel<decltype(akc)::value, decltype(bkc)::value, WAVES>), grid, WAVES * 64, 0, s,
+                               f.A, f.B, f.a_bytes, f.b_bytes, f.lda4, f.ldb4, f.M, f.N, f.K, po.w[0], po.w[1], po.w[2], g, colsum);
+        });
+        g_small_args_form = 1;
+        TNN_LAUNCH_OK();
+        return 0;
+    }
+    g_small_args_form = 0;
     with_layout(transA, transB, [&](auto akc, auto bkc) {
         tnn::with_flag(fast, [&](auto f) {
             hipLaunchKernelGGL((gemm_small_f32_kernel<decltype(akc)::value, decltype(bkc)::value, WAVES, decltype(f)::value>), grid,
@@ -506,6 +545,15 @@ static bool dw0_wide_ok(const GemmArgs& g) {
     return !off && g.N % 32 == 0 && ((g.M + 15) / 16) * (g.N / 32) >= 256 && g.epi == EPI_AXPBY && g.beta == 0.f;
 }
 
+// M | (N / 32) << 16 | (K - 1) << 24 for dw_first_sgprs (tnn_gemm_small.h); false where a field cannot hold its value or a
+// leading dimension is not the extent it stands for there (lda == M, ldb == ldc == N)
+static bool pack_dw_dims(const GemmArgs& g, uint32_t& dims) {
+    if (g.M < 1 || g.M > 0xffff || g.N < 32 || g.N % 32 != 0 || g.N / 32 > 0xff || g.K < 1 || g.K > 256) return false;
+    if (g.lda != g.M || g.ldb != g.N || g.ldc != g.N) return false;
+    dims = (uint32_t)g.M | (uint32_t)(g.N / 32) << 16 | (uint32_t)(g.K - 1) << 24;
+    return true;
+}
+
 int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const void* x, const void* dz, void* dw, void* db,
                              void* p_w, void* m_w, void* v_w, void* p_b, void* m_b, void* v_b, void* flat_p,
                              const void* flat_g, void* flat_m, void* flat_v, int64_t flat_n, double lr, double b1,
@@ -513,6 +561,7 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
     TNN_NEED_INIT();
     TNN_REQUIRE(rows > 0 && n_in > 0 && n_out > 0, "tnn_dense_bwd_first_adam: empty layer");
     TNN_REQUIRE(pows_f64 && p_w && m_w && v_w && p_b && m_b && v_b, "tnn_dense_bwd_first_adam: optimizer state is required");
+    g_bwd0_args_form = 0;
     if (dtype == TNN_F32) {
         GemmArgs gw = gemm_args(x, n_in, dz, n_out, dw, n_out, n_in, n_out, rows, EPI_AXPBY);
         if (use_small_path(gw) && tn_extents_ok(gw)) {
@@ -546,6 +595,18 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
                 pick_xcd_cut(gw);
                 const int n_wide = gw.tiles_m * gw.tiles_n;
                 const int extra = adam_flat_blocks(ad.fp, ad.fg, ad.fm, ad.fv, ad.fn, 256);
+                // the tiles' first-request values as leading scalars (user SGPRs) where they pack: the order and n_wide in
+                // three dwords, M / N / K in one, a gradient whose leading dimensions are its extents
+                tnn::PackedTileOrder po;
+                uint32_t dims;
+                if (!step_args_struct_forced("bwd0") && tnn::pack_tile_order(gw.ord, po) && n_wide <= 0xffff && pack_dw_dims(gw, dims)) {
+                    po.w[2] |= (uint32_t)n_wide << tnn::kPackedOrderFlagShift;
+                    hipLaunchKernelGGL((dense_bwd0_adam_pre_kernel<4>), n_wide + extra, 256, 0, s, ad.pw, ad.mw, ad.vw, gw.A, gw.B, po.w[0],
+                                       po.w[1], po.w[2], dims, gw, (float*)db, ad, ad);
+                    g_bwd0_args_form = 1;
+                    TNN_LAUNCH_OK();
+                    return 0;
+                }
                 hipLaunchKernelGGL((dense_bwd0_adam_kernel<4, true>), n_wide + extra, 256, 0, s, gw, (float*)db, ad, n_wide);
                 TNN_LAUNCH_OK();
                 return 0;
@@ -576,6 +637,10 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
         return tnn_adam_ex(flat_p, flat_g, flat_m, flat_v, flat_n, lr, b1, b2, eps, pows, nullptr, dtype, 0, nullptr, nullptr);
     return 0;
 }
+
+// How the last launch of the 16 x 16 latency kernel (which = 0) / of the first-layer backward + Adam (which = 1) got its
+// first-request arguments: 1 preloaded user SGPRs, 0 the argument block, -1 none yet.  For tests/test_gpu_step_arg_sgprs.py; not part of include/tnn_hip.h.
+__attribute__((visibility("default"))) int tnn_step_args_form(int which) { return which == 1 ? g_bwd0_args_form : g_small_args_form; }
 
 #ifdef TNN_STEP_TRACE
 // rows [kernel id][workgroup][4] of g_step_trace; `which` = 2 is served by tnn_head.hip's own buffer (tnn_debug_step_trace_head)
@@ -697,8 +762,8 @@ int tnn_dense_fwd_head_partials(int64_t M, int64_t N, int64_t K, const void* A, 
     }
     if (int rc = gemm_f32(g, 0, 0)) return rc;
     const int64_t total = ((N + 15) / 16) * M * head_c;
-    hipLaunchKernelGGL(head_partials_kernel, tnn::stream_grid(total, 256), 256, 0, tnn::stream(), (const float*)C, M, N, ldc,
-                       (const float*)head_w, (int)head_c, (float*)head_z);
+    hipLaunchKernelGGL(head_partials_kernel, tnn::stream_grid(total, 256), 256, 0, tnn::stream(),
+                       HeadPartialsArgs{(const float*)C, M, N, ldc, (const float*)head_w, (int)head_c, (float*)head_z});
     TNN_LAUNCH_OK();
     return 0;
 }

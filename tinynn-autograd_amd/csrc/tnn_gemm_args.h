@@ -31,6 +31,10 @@ struct GemmArgs {
     int64_t M, N, K, lda, ldb, ldc;
     float alpha, beta;
     int epi;
+    // The hole in front of `bias`, named: alpha, beta, epi and this are one 16-byte scalar load, and a load with a DEAD dword
+    // hands that register out again while the load is in flight — a wait for the whole argument group wherever the register
+    // is written next (small_tile_fast: in front of the first fragment request).  small_tile_fast keeps it alive; always 0.
+    int epi_hole;
     const float* bias;
     int act, relu_sign;
     const float* Y;
@@ -69,6 +73,31 @@ struct GemmArgs {
     unsigned long long* trace;   // debug build only: [grid][8] timeline words (nullptr = off)
 #endif
 };
+
+// What a wave of small_tile_fast needs to form the addresses of its FIRST round of requests (the fragments of its chunks) and to
+// pick its straight-line body: the operands' resources and strides, the extents, the tile order and whether wave 0 requests a
+// head_w fragment.  Two makers, one tile body: fast_first(g) reads the values from the argument block (GemmArgs::f / ::ord, the
+// argument segment: a scalar-memory round trip in front of the first request), fast_first_sgprs(...) from fourteen leading
+// scalar kernel parameters, which gfx950 delivers in user SGPRs at wave launch (gemm_small_pre_f32_kernel, tnn_gemm_small.h).
+struct FastFirst {
+    const float *A, *B;
+    uint32_t a_bytes, b_bytes, lda4, ldb4, M, N, K;
+    int nchunks;
+    tnn::TileOrder ord;
+    bool head_on;
+};
+constexpr uint32_t FAST_FLAG_HEAD = 1u << 15;                 // bit 31 of the packed order's third dword
+
+__device__ __forceinline__ FastFirst fast_first(const GemmArgs& g) {
+    const SmallFast& f = g.f;
+    return FastFirst{f.A, f.B, f.a_bytes, f.b_bytes, f.lda4, f.ldb4, f.M, f.N, f.K, f.nchunks, g.ord, f.h_bytes != 0u};
+}
+__device__ __forceinline__ FastFirst fast_first_sgprs(const float* A, const float* B, uint32_t a_bytes, uint32_t b_bytes, uint32_t lda4,
+                                                      uint32_t ldb4, uint32_t M, uint32_t N, uint32_t K, uint32_t o0, uint32_t o1,
+                                                      uint32_t o2) {
+    return FastFirst{A, B, a_bytes, b_bytes, lda4, ldb4, M, N, K, (int)((K + 15u) >> 4), tnn::unpack_tile_order(o0, o1, o2),
+                     (o2 >> tnn::kPackedOrderFlagShift & FAST_FLAG_HEAD) != 0u};
+}
 
 __device__ __forceinline__ float apply_epilogue(const GemmArgs& g, float acc, int64_t row,
                                                 int64_t col) {

@@ -39,7 +39,8 @@ struct TnFrag {
 // straight-line body that issues exactly that many chunk groups and then that many MFMA groups: no branch stands between a
 // load and the MFMAs behind it, so the compiler's wait in front of chunk u's MFMAs leaves chunks u + 1 .. live - 1 in flight.
 // (With `if (u < live)` around each group the wait at every join had to assume the path with the fewest later loads, and
-// the matrix pipe started when the LAST chunk was home.)  mma_mark(u, live) runs in front of slot u's MFMAs (trace stamps).
+// the matrix pipe started when the LAST chunk was home.)  mma_mark(u, live) runs in front of slot u's MFMAs (trace stamps;
+// dw_tile_wide's late requests).
 // Four chunks of a 16 x 32 tile are 48 fragment registers.  SINGLE: nchunks <= WAVES * TN_MAXC is the caller's contract.
 template <int V> struct IntC { static constexpr int value = V; };       // a compile-time count handed to a generic lambda
 constexpr int TN_MAXC = 4;
@@ -65,8 +66,11 @@ template <int WAVES, bool SINGLE, class L, class K, class M>
 __device__ __forceinline__ void tn_batches(const int wid, const int nchunks, L&& load, K&& mma_mark, M&& mma) {
     for (int c0 = wid; c0 < nchunks; c0 += WAVES * TN_MAXC) {
         const int live = (nchunks - c0 + WAVES - 1) / WAVES;
-        // (trace build only: a scalar branch between the loads and the MFMAs, but one that contains no load or store — the
-        // waits behind it count the same on both of its paths; in the product build mma_mark is empty and the branch is gone)
+        // mma_mark runs for the first batch only.  With SINGLE the loop body runs once, c0 == wid holds by construction and the
+        // compiler folds the test: the hook is straight-line code, which dw_tile_wide relies on — it issues its late requests
+        // (bias state, pows) from the hook, in the product build too, and a branch around loads between the fragment requests
+        // and the MFMAs would make the waits behind it pessimistic.  Without SINGLE (small_tile<ADAM>) the hook holds trace
+        // stamps only: a scalar branch in the trace build that contains no load or store, gone in the product build.
         auto mark = [&](const int u, const int n) { if (c0 == wid) mma_mark(u, n); };
         switch (live < TN_MAXC ? live : TN_MAXC) {
             case 1: tn_batch_body<1, WAVES>(c0, load, mark, mma); break;
@@ -229,42 +233,82 @@ __device__ __forceinline__ void small_tile(const GemmArgs& g, float* __restrict_
 //   lane (i16, grp): a[j] = A[16 c + 4 grp + j][m0 + i16], b0 / b1[j] = B[.][n0 + i16] / B[.][n0 + 16 + i16]
 //   acc0 / acc1[r] = C[m0 + 4 grp + r][n0 + i16] / [.. + 16]   (16x16x4 C/D layout)
 // ADAM / TO_LDS as in small_tile; out_lds: [16][32] row-major, then the 32 column sums.
+// What a wave of dw_tile_wide needs for its FIRST round of requests — the Adam state of its outputs and the fragments of its
+// chunks: the operands, the weight block's state, the extents and the tile order.  As FastFirst (tnn_gemm_args.h): dw_first(g, ad)
+// reads them from the argument blocks, dw_first_sgprs(...) from fourteen leading scalar parameters of dense_bwd0_adam_pre_kernel
+// (tnn_gemm_step.h), which arrive in user SGPRs.  The packed form holds a first-layer gradient as tnn_dense_bwd_first_adam
+// builds it: lda == M, ldb == ldc == N.
+struct DwFirst {
+    const float *A, *B;
+    float *pw, *mw, *vw;           // ADAM only
+    int64_t M, N, K, lda, ldb, ldc;
+    tnn::TileOrder ord;
+};
+__device__ __forceinline__ DwFirst dw_first(const GemmArgs& g, const AdamEpi* ad) {
+    return DwFirst{g.A, g.B, ad ? ad->pw : nullptr, ad ? ad->mw : nullptr, ad ? ad->vw : nullptr, g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.ord};
+}
+// dims = M | (N / 32) << 16 | (K - 1) << 24 (pack_dw_dims in tnn_gemm.hip refuses what the fields cannot hold); the upper half of
+// o2 is the number of tile workgroups, read by the kernel itself
+__device__ __forceinline__ DwFirst dw_first_sgprs(float* pw, float* mw, float* vw, const float* A, const float* B, uint32_t o0, uint32_t o1,
+                                                  uint32_t o2, uint32_t dims) {
+    const int64_t M = dims & 0xffffu, N = (dims >> 16 & 0xffu) * 32u, K = (dims >> 24) + 1u;
+    return DwFirst{A, B, pw, mw, vw, M, N, K, M, N, N, tnn::unpack_tile_order(o0, o1, o2)};
+}
+
+// q: the first-request values (above); g and ad give the rest — the bias block's state, pows, alpha, C — which is requested
+// BEHIND the fragments, so that a kernel whose q arrives in SGPRs waits for its argument segment with every load of the weight
+// state and the fragments already out.
 template <int WAVES, bool ADAM, bool TO_LDS>
-__device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restrict__ colsum, const int block, float (*red)[8][64],
-                                             float (*bsum)[2][64], const AdamEpi* ad = nullptr, float* out_lds = nullptr) {
+__device__ __forceinline__ void dw_tile_wide(const DwFirst& q, const GemmArgs& g, float* __restrict__ colsum, const int block,
+                                             float (*red)[8][64], float (*bsum)[2][64], const AdamEpi* ad = nullptr,
+                                             float* out_lds = nullptr) {
     if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 0);      // entry: in front of the Adam state's requests
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     int tm, tn;
-    small_tile_coords(g, block, tm, tn);                     // g.tiles_n counts 32-column tiles here
+    tnn::tile_coords(q.ord, block, tm, tn);                  // the grid's columns are 32-column tiles here
     const int64_t m0 = (int64_t)tm * 16, n0 = (int64_t)tn * 32;
     const int64_t am = m0 + i16, bn = n0 + i16;
-    const bool a_ok = am < g.M;
-    const int nchunks = (int)((g.K + 15) / 16);
+    const bool a_ok = am < q.M;
+    const int nchunks = (int)((q.K + 15) / 16);
     // this thread's two outputs of the epilogue (threads < 256): rows m0 + 4 (ln >> 4) + r, columns n0 + (ln & 15) and + 16
     const int e_r = tid >> 6, e_ln = tid & 63;
     const int64_t e_row = m0 + (e_ln >> 4) * 4 + e_r, e_col = n0 + (e_ln & 15);
-    const bool e_live = tid < 256 && e_row < g.M;
-    float a_p[2] = {0.f, 0.f}, a_m[2] = {0.f, 0.f}, a_v[2] = {0.f, 0.f}, ab_p = 0.f, ab_m = 0.f, ab_v = 0.f, ic1 = 0.f, ic2 = 0.f;
+    const bool e_live = tid < 256 && e_row < q.M;
+    float a_p[2] = {0.f, 0.f}, a_m[2] = {0.f, 0.f}, a_v[2] = {0.f, 0.f}, ab_p = 0.f, ab_m = 0.f, ab_v = 0.f;
+    double pow1 = 0.0, pow2 = 0.0;
     if constexpr (ADAM) {
-        ic1 = (float)(1.0 / (1.0 - ad->pows[0]));
-        ic2 = (float)(1.0 / (1.0 - ad->pows[1]));
         if (e_live) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-                const int64_t i = e_row * g.ldc + e_col + 16 * u;
-                a_p[u] = ad->pw[i]; a_m[u] = ad->mw[i]; a_v[u] = ad->vw[i];
+                const int64_t i = e_row * q.ldc + e_col + 16 * u;
+                a_p[u] = q.pw[i]; a_m[u] = q.mw[i]; a_v[u] = q.vw[i];
             }
         }
-        if (tm == 0 && tid < 32) { ab_p = ad->pb[n0 + tid]; ab_m = ad->mb[n0 + tid]; ab_v = ad->vb[n0 + tid]; }
     }
+    // The bias block's state (the 32 column-sum threads of tile row 0) and pows, requested behind the first batch's fragments
+    // (tn_batches' mma_mark hook; a wave without a chunk requests them on its own below).  Buffer loads with the offset
+    // 0xffffffff for every other thread: an exec-mask branch between the fragment requests and the MFMAs would make the wait in
+    // front of the first MFMA count for the path with the fewest later loads.
+    [[maybe_unused]] auto request_late = [&]() {
+        if constexpr (ADAM) {
+            const uint32_t bytes = (uint32_t)q.N * 4u;
+            uint32_t off = (tm == 0 && tid < 32) ? ((uint32_t)n0 + (uint32_t)tid) * 4u : 0xffffffffu;
+            asm("" : "+v"(off));                              // opaque (TnFrag::load): a select, not a branch
+            ab_p = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(__builtin_amdgcn_make_buffer_rsrc(ad->pb, 0, bytes, 0x00020000), off, 0, 0));
+            ab_m = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(__builtin_amdgcn_make_buffer_rsrc(ad->mb, 0, bytes, 0x00020000), off, 0, 0));
+            ab_v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(__builtin_amdgcn_make_buffer_rsrc(ad->vb, 0, bytes, 0x00020000), off, 0, 0));
+            pow1 = ad->pows[0];
+            pow2 = ad->pows[1];
+        }
+    };
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     float bs0 = 0.f, bs1 = 0.f;
     // K loop: a wave requests the fragments of ALL its chunks (batches of up to TN_MAXC) before its first MFMA — one load round
     // trip per batch instead of one per chunk.  Buffer loads: a row k >= K (or a row of A past M) gets the offset 0xffffffff
     // and reads 0, no exec-mask branch; chunks that do not exist cost neither loads nor MFMAs (tn_batches).  Chunk order, the
     // two accumulator chains and the column-sum adds are those of the chunk-per-trip loop this replaces: the same bits.
-    const TnFrag fa(g.A, g.K, g.lda, g.M, grp, am, a_ok), fb(g.B, g.K, g.ldb, g.N, grp, bn, true);
+    const TnFrag fa(q.A, q.K, q.lda, q.M, grp, am, a_ok), fb(q.B, q.K, q.ldb, q.N, grp, bn, true);
     const int swid = __builtin_amdgcn_readfirstlane(wid);
     float a[TN_MAXC][4], b0[TN_MAXC][4], b1[TN_MAXC][4];
     [[maybe_unused]] unsigned long long t_first = 0, t_last = 0;
@@ -279,9 +323,13 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
                 b1[u][j] = fb.load(row, 64u);
             }
         },
-        [&](const int u, const int n) {                       // (trace build: the wave's first / last chunk home)
-            if constexpr (ADAM) {
-                if (u == 0) TNN_STEP_CLOCK_HOME(t_first, a[0][3], b1[0][3]);
+        [&](const int u, const int n) {                       // in front of slot u's MFMAs: the late requests (product build too),
+            if constexpr (ADAM) {                             // then, trace build only, the wave's first / last chunk home
+                if (u == 0) {
+                    request_late();
+                    __builtin_amdgcn_sched_barrier(0);        // ... and stays in front of the first MFMA's wait
+                    TNN_STEP_CLOCK_HOME(t_first, a[0][3], b1[0][3]);
+                }
                 if (u == n - 1) TNN_STEP_CLOCK_HOME(t_last, a[u][3], b1[u][3]);
             }
         },
@@ -296,10 +344,18 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
             bs0 += (b0[u][0] + b0[u][1]) + (b0[u][2] + b0[u][3]);
             bs1 += (b1[u][0] + b1[u][1]) + (b1[u][2] + b1[u][3]);
         });
+    if constexpr (ADAM) {
+        if (swid >= nchunks) request_late();                  // wave-uniform: a wave without a chunk (K < 16 WAVES)
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) { red[wid][r][lane] = acc0[r]; red[wid][4 + r][lane] = acc1[r]; }
     bsum[wid][0][lane] = bs0;
     bsum[wid][1][lane] = bs1;
+    float ic1 = 0.f, ic2 = 0.f;
+    if constexpr (ADAM) {
+        ic1 = (float)(1.0 / (1.0 - pow1));
+        ic2 = (float)(1.0 / (1.0 - pow2));
+    }
     __syncthreads();
     if constexpr (ADAM) TNN_STEP_STAMP(g_step_trace, 3, 2);
     if constexpr (ADAM) {
@@ -313,13 +369,13 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
 #pragma unroll
             for (int w = 0; w < WAVES; ++w) sres += red[w][4 * u + e_r][e_ln];
             const float gval = g.alpha * sres;
-            const int64_t i = e_row * g.ldc + e_col + 16 * u;
+            const int64_t i = e_row * q.ldc + e_col + 16 * u;
             if constexpr (TO_LDS) out_lds[(int)(e_row - m0) * 32 + (int)(e_col - n0) + 16 * u] = gval;
             else if (!ADAM || g.C != nullptr) g.C[i] = gval;      // ADAM: the gradient itself only on request
             if constexpr (ADAM) {
-                ad->pw[i] = adam_apply(*ad, ic1, ic2, gval, a_m[u], a_v[u], a_p[u]);
-                ad->mw[i] = a_m[u];
-                ad->vw[i] = a_v[u];
+                q.pw[i] = adam_apply(*ad, ic1, ic2, gval, a_m[u], a_v[u], a_p[u]);
+                q.mw[i] = a_m[u];
+                q.vw[i] = a_v[u];
             }
         }
     }
@@ -351,8 +407,10 @@ __device__ __forceinline__ void dw_tile_wide(const GemmArgs& g, float* __restric
 // SYS_HEADZ: the partial logits leave through write-through (system-scope) stores, because a workgroup of THIS launch
 // on another XCD reads them back (dense_fwd_head_kernel)
 // HEAD = false: a caller that never has a head (no head_lds) gets no bodies for that role
+// q: what the first round of requests needs (FastFirst, tnn_gemm_args.h), from the argument block or from preloaded SGPRs;
+// everything else (the epilogue's operand, head_w, C, head_z) is read from g, behind the fragment requests
 template <bool AKC, bool BKC, int WAVES, bool SYS_HEADZ = false, bool HEAD = true>
-__device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __restrict__ colsum, int block,
+__device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmArgs& g, float* __restrict__ colsum, int block,
                                                 float (*red)[4][64], float (*bsum)[64], float* head_lds = nullptr) {
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     constexpr uint32_t OOB = 0xffffffffu;
@@ -364,14 +422,14 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
     // operand) and the tile comes from g.ord without a division: one group of argument loads, then the lanes' own offsets.
     const SmallFast& f = g.f;
     int tm, tn;
-    small_tile_coords(g, block, tm, tn);
+    tnn::tile_coords(q.ord, block, tm, tn);
     const uint32_t m0 = (uint32_t)tm * 16u, n0 = (uint32_t)tn * 16u;
     const uint32_t am = m0 + (uint32_t)i16, bn = n0 + (uint32_t)i16;
-    const bool a_ok = am < f.M, b_ok = bn < f.N;
-    const int nchunks = f.nchunks;
-    const uint32_t K = f.K, lda4 = f.lda4, ldb4 = f.ldb4;
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.A), 0, f.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.B), 0, f.b_bytes, 0x00020000);
+    const bool a_ok = am < q.M, b_ok = bn < q.N;
+    const int nchunks = q.nchunks;
+    const uint32_t K = q.K, lda4 = q.lda4, ldb4 = q.ldb4;
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.A), 0, q.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.B), 0, q.b_bytes, 0x00020000);
     // byte offset of this lane's first element of chunk 0 (k = grp * 4), without the chunk term
     const uint32_t a_lane = AKC ? am * lda4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * lda4 + am * 4u;
     const uint32_t b_lane = BKC ? bn * ldb4 + (uint32_t)grp * 16u : (uint32_t)grp * 4u * ldb4 + bn * 4u;
@@ -380,16 +438,18 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
 
     const int e_r = tid >> 6, e_ln = tid & 63;
     const uint32_t e_row = m0 + (uint32_t)((e_ln >> 4) * 4 + e_r), e_col = n0 + (uint32_t)(e_ln & 15);   // 16x16x4 C/D layout
-    const bool e_live = tid < 256 && e_row < f.M && e_col < f.N;
+    const bool e_live = tid < 256 && e_row < q.M && e_col < q.N;
     // The epilogue's operand and wave 0's head_w fragment travel like the K loop's fragments: a buffer resource (a NULL bias /
     // no operand: 0 bytes long, every offset reads 0), a 32-bit byte offset, and 0xffffffff for a thread, row or unit that does
     // not exist.  Left to pointers, each of these loads sat under its own exec-mask branch behind a 64-bit multiply-add whose
     // register pair overlapped the load in front of it, and wave 0 of every workgroup took three dependent round trips before
     // it requested its first fragment.  32-bit extents of C / Y: small_fast_ok.
-    const uint32_t e_off = e_row * f.e_ld4 + e_col * 4u;
-    const __amdgpu_buffer_rsrc_t e_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.e_ptr), 0, f.e_bytes, 0x00020000);
-    const bool head_on = f.h_bytes != 0u;                     // kernel-uniform
-    const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f.head_w), 0, f.h_bytes, 0x00020000);
+    // Their descriptions are read from the argument block HERE, one group of scalar loads in front of everything, but nothing
+    // uses them before request_epilogue: offsets and resources are formed there, behind the fragment requests, so the wait for
+    // the argument segment stands behind those requests too (a kernel whose FastFirst arrives in SGPRs issues them unwaited).
+    const uint32_t e_ld4 = f.e_ld4, e_bytes = f.e_bytes, h_bytes = f.h_bytes, h_hc4 = f.hc4;
+    const float *const e_ptr = f.e_ptr, *const h_ptr = f.head_w;
+    const bool head_on = q.head_on;                           // kernel-uniform
     const int swid = __builtin_amdgcn_readfirstlane(wid);     // the branches below are scalar: no exec mask around a load
     float e_pre = 0.f;
     float head_pre[4] = {0.f, 0.f, 0.f, 0.f};                 // wave 0: head_w[n0 + 4 grp + j][i16], the B fragment of the partial-logit product
@@ -398,7 +458,10 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
     auto request_epilogue = [&](auto role_c) {
         constexpr int ROLE = decltype(role_c)::value;
         if constexpr (ROLE >= 1) {
-            uint32_t off = e_live ? e_off : OOB;
+            const __amdgpu_buffer_rsrc_t e_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e_ptr), 0, e_bytes, 0x00020000);
+            uint32_t row_b = e_row * e_ld4;
+            asm("" : "+v"(row_b));                            // opaque, as unit_b below: no v_mad_u64_u32 on a pair with a load in flight
+            uint32_t off = e_live ? row_b + e_col * 4u : OOB;
             asm("" : "+v"(off));                              // opaque (TnFrag::load): the select stays a select
             e_pre = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(e_rsrc, off, 0, 0));
         }
@@ -406,14 +469,15 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
             // one vector multiply for the lane's first unit (opaque, so that it is not fused with the add: a 32-bit multiply-add
             // comes out as v_mad_u64_u32 on a register pair whose upper half is the load in flight in front of it — a full
             // wait for nothing), the unit step added as a scalar
-            const uint32_t unit0 = n0 + 4u * (uint32_t)grp, hc4 = f.hc4;
+            const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(h_ptr), 0, h_bytes, 0x00020000);
+            const uint32_t unit0 = n0 + 4u * (uint32_t)grp, hc4 = h_hc4;
             uint32_t unit_b = unit0 * hc4;
             asm("" : "+v"(unit_b));
             const uint32_t off0 = unit_b + (uint32_t)i16 * 4u;
             const bool cls_ok = (uint32_t)i16 * 4u < hc4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const bool ok = cls_ok & (unit0 + (uint32_t)j < f.N);
+                const bool ok = cls_ok & (unit0 + (uint32_t)j < q.N);
                 uint32_t off = ok ? off0 + (uint32_t)j * hc4 : OOB;
                 asm("" : "+v"(off));
                 head_pre[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(h_rsrc, off, 0, 0));
@@ -521,6 +585,7 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
     for (int r = 0; r < 4; ++r) red[wid][r][lane] = acc[r];
     bsum[wid][lane] = bs;
     __syncthreads();
+    asm volatile("" ::"s"(g.epi_hole));                     // (GemmArgs::epi_hole: no dead dword in the epilogue's argument load)
     TNN_STEP_STAMP(g_step_trace, KID, 2);
     TNN_STEP_STAMP_VALUE(g_step_trace_first, KID, 1, 0, t_first);
     TNN_STEP_STAMP_VALUE(g_step_trace, KID, 4, 1, t_last);
@@ -534,7 +599,7 @@ __device__ __forceinline__ void small_tile_fast(const GemmArgs& g, float* __rest
             g.C[(int64_t)e_row * g.ldc + e_col] = e_val;
         }
     }
-    if (colsum != nullptr && tm == 0 && tid < 16 && n0 + (uint32_t)tid < f.N) {
+    if (colsum != nullptr && tm == 0 && tid < 16 && n0 + (uint32_t)tid < q.N) {
         float s = 0.f;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) s += (bsum[w][tid] + bsum[w][16 + tid]) + (bsum[w][32 + tid] + bsum[w][48 + tid]);
@@ -576,11 +641,29 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_small_f32_kernel(GemmArgs g, 
     __shared__ float bsum[WAVES][64];
     if constexpr (FAST) {
         __shared__ __attribute__((aligned(16))) float head_lds[16 * 20];   // tnn_dense_fwd_head_partials: the finished tile
-        small_tile_fast<AKC, BKC, WAVES>(g, colsum, (int)blockIdx.x, red, bsum, head_lds);
+        small_tile_fast<AKC, BKC, WAVES>(fast_first(g), g, colsum, (int)blockIdx.x, red, bsum, head_lds);
         // single writer; read by the NEXT launch only, so it stands behind the tile: in front it was an argument fetch, a wait
         // and an exec-mask branch on every wave's way to its first request
         if (g.bump != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *g.bump += 1u;
     } else {
         small_tile<AKC, BKC, WAVES>(g, colsum, (int)blockIdx.x, red, bsum);
     }
+}
+
+// The FAST form with its first-request values as fourteen leading scalar parameters (two pointers and ten dwords: FastFirst with
+// the tile order packed, tnn_tile_order.h).  Built with -amdgpu-kernarg-preload-count=16 (csrc/Makefile) they arrive in user SGPRs
+// at wave launch — a by-value struct would not — so a wave forms its fragment addresses and issues its first batch without
+// waiting for the argument segment; what the epilogue needs comes from g in one group of scalar loads whose wait stands
+// behind those requests.  Same tile body; the host picks this kernel where the order packs (launch_small).
+template <bool AKC, bool BKC, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void gemm_small_pre_f32_kernel(const float* A, const float* B, uint32_t a_bytes, uint32_t b_bytes,
+                                                                        uint32_t lda4, uint32_t ldb4, uint32_t M, uint32_t N, uint32_t K,
+                                                                        uint32_t o0, uint32_t o1, uint32_t o2, GemmArgs g,
+                                                                        float* __restrict__ colsum) {
+    __shared__ float red[WAVES][4][64];
+    __shared__ float bsum[WAVES][64];
+    __shared__ __attribute__((aligned(16))) float head_lds[16 * 20];
+    small_tile_fast<AKC, BKC, WAVES>(fast_first_sgprs(A, B, a_bytes, b_bytes, lda4, ldb4, M, N, K, o0, o1, o2), g, colsum,
+                                     (int)blockIdx.x, red, bsum, head_lds);
+    if (g.bump != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *g.bump += 1u;
 }

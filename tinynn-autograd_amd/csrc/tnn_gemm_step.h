@@ -23,7 +23,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_fwd_head_kernel(GemmArgs g, 
     __shared__ double dred[8][4];
     __shared__ int is_last;
     TNN_AR_STAMP(g_fh_trace, blockIdx.x, 8, 128, 0);
-    small_tile_fast<true, false, WAVES, true>(g, nullptr, (int)blockIdx.x, red, bsum, head_lds);
+    small_tile_fast<true, false, WAVES, true>(fast_first(g), g, nullptr, (int)blockIdx.x, red, bsum, head_lds);
     TNN_AR_STAMP(g_fh_trace, blockIdx.x, 8, 128, 1);
     // Shards of more than 128 rows: every 128-row block has its own arrival counter (ticket[1 + rb], the block's 8 tile rows x
     // all tile columns), so the blocks' statistics are reduced in parallel, each by the workgroup that finishes the block; the
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_fwd_head_generic_kernel(Gemm
     __shared__ __attribute__((aligned(16))) float head_lds[16 * 20];
     __shared__ float wred[WAVES][2];
     __shared__ int is_last;
-    small_tile_fast<true, false, WAVES, true>(g, nullptr, (int)blockIdx.x, red, bsum, head_lds);
+    small_tile_fast<true, false, WAVES, true>(fast_first(g), g, nullptr, (int)blockIdx.x, red, bsum, head_lds);
     using namespace tnn::p2p;
     if (threadIdx.x < 64) {                                    // wave 0 wrote this tile's partial logits
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -341,9 +341,9 @@ __global__ __launch_bounds__(WAVES * 64) void dense_bwd_small_kernel(GemmArgs gw
     __shared__ float bsum[WAVES][64];
     if constexpr (FAST) {
         if ((int)blockIdx.x < n_dw)
-            small_tile_fast<false, false, WAVES, false, false>(gw, db, (int)blockIdx.x, red, bsum);
+            small_tile_fast<false, false, WAVES, false, false>(fast_first(gw), gw, db, (int)blockIdx.x, red, bsum);
         else
-            small_tile_fast<true, true, WAVES, false, false>(gx, nullptr, (int)blockIdx.x - n_dw, red, bsum);
+            small_tile_fast<true, true, WAVES, false, false>(fast_first(gx), gx, nullptr, (int)blockIdx.x - n_dw, red, bsum);
     } else {
         if ((int)blockIdx.x < n_dw)
             small_tile<false, false, WAVES>(gw, db, (int)blockIdx.x, red, bsum);
@@ -362,8 +362,29 @@ __global__ __launch_bounds__(WAVES * 64) void dense_bwd0_adam_kernel(GemmArgs gw
     __shared__ float red[WAVES][WIDE ? 8 : 4][64];
     __shared__ float bsum[WAVES][WIDE ? 2 : 1][64];
     if ((int)blockIdx.x < n_dw) {
-        if constexpr (WIDE) dw_tile_wide<WAVES, true, false>(gw, db, (int)blockIdx.x, red, bsum, &ad);
+        if constexpr (WIDE) dw_tile_wide<WAVES, true, false>(dw_first(gw, &ad), gw, db, (int)blockIdx.x, red, bsum, &ad);
         else small_tile<false, false, WAVES, true>(gw, db, (int)blockIdx.x, red, reinterpret_cast<float(*)[64]>(bsum), &ad);
+        return;
+    }
+    adam_flat_range<WAVES * 64, true>(ad, (int)blockIdx.x - n_dw, (int)gridDim.x - n_dw);
+}
+
+// The 16 x 32 form of the same launch with the tiles' first-request values as fourteen leading scalar parameters (five pointers
+// and four dwords: DwFirst with the order, the number of tile workgroups and the extents packed), preloaded into user SGPRs at
+// wave launch (-amdgpu-kernarg-preload-count=16, csrc/Makefile).  The role is decided and a tile workgroup's Adam state and
+// fragments are requested without waiting for the argument segment: dense_bwd0_adam_kernel waits for it twice in a row, once
+// for n_dw and once more inside the role.  Same tile body, same flat-range walk.  The Adam block is passed twice, adt for the
+// tiles and ad for the flat range: fields both roles read from ONE copy are fetched in front of the role branch, in a group
+// whose other registers the tile role does not need and hands out again while the fetch is in flight — a wait at its top.
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void dense_bwd0_adam_pre_kernel(float* pw, float* mw, float* vw, const float* A, const float* B,
+                                                                         uint32_t o0, uint32_t o1, uint32_t o2, uint32_t dims, GemmArgs gw,
+                                                                         float* __restrict__ db, AdamEpi adt, AdamEpi ad) {
+    __shared__ float red[WAVES][8][64];
+    __shared__ float bsum[WAVES][2][64];
+    const int n_dw = (int)(o2 >> tnn::kPackedOrderFlagShift);
+    if ((int)blockIdx.x < n_dw) {
+        dw_tile_wide<WAVES, true, false>(dw_first_sgprs(pw, mw, vw, A, B, o0, o1, o2, dims), gw, db, (int)blockIdx.x, red, bsum, &adt);
         return;
     }
     adam_flat_range<WAVES * 64, true>(ad, (int)blockIdx.x - n_dw, (int)gridDim.x - n_dw);
@@ -410,7 +431,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_bwd0_allreduce_adam_kernel(G
         // (requested in front of the product: behind it, this agent-scope load was a round trip on the way to the sends — 0.9 us
         // between "product done" and "sends issued" in profiles/r06_dp_step_stamps.txt; the word is sticky, an earlier look is as good)
         const int dead_at_entry = __hip_atomic_load(ctx.dead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (WIDE) dw_tile_wide<WAVES, false, true>(gw, nullptr, (int)blockIdx.x, red, bsum, nullptr, tile);
+        if constexpr (WIDE) dw_tile_wide<WAVES, false, true>(dw_first(gw, nullptr), gw, nullptr, (int)blockIdx.x, red, bsum, nullptr, tile);
         else small_tile<false, false, WAVES, false, true>(gw, nullptr, (int)blockIdx.x, red, reinterpret_cast<float(*)[64]>(bsum), nullptr, tile);
         __syncthreads();
         TNN_AR_STAMP(g_ar_trace, blockIdx.x, 4, 1024, 1);
@@ -527,8 +548,21 @@ __global__ __launch_bounds__(512) void dense_bwd0_mid_allreduce_adam_kernel(Gemm
 
 // fallback of tnn_dense_fwd_head_partials for shapes the latency kernel does not take: the same partial sums from the
 // finished output, one thread per (tile, row, class)
-__global__ __launch_bounds__(256) void head_partials_kernel(const float* __restrict__ out, int64_t M, int64_t N, int64_t ldc,
-                                                            const float* __restrict__ hw, int hc, float* __restrict__ hz) {
+// (Its arguments are ONE by-value struct: the unit is built with kernel-argument preload, which reaches every kernel whose leading
+// parameters are scalars — and this one runs with many workgroups, where the preload only adds work for the dispatcher.)
+struct HeadPartialsArgs {
+    const float* out;
+    int64_t M, N, ldc;
+    const float* hw;
+    int hc;
+    float* hz;
+};
+__global__ __launch_bounds__(256) void head_partials_kernel(HeadPartialsArgs a) {
+    const float* __restrict__ out = a.out;
+    const float* __restrict__ hw = a.hw;
+    float* __restrict__ hz = a.hz;
+    const int64_t M = a.M, N = a.N, ldc = a.ldc;
+    const int hc = a.hc;
     const int64_t tiles_n = (N + 15) / 16, total = tiles_n * M * hc;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % hc);

@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "tnn_internal.h"
 #include "tnn_tile_order.h"
@@ -69,8 +70,17 @@ template <int C, int NP>
 struct HeadStage {
     f32x4 v[NP], yv;
 };
+// What the staging requests and the bias need, and nothing else: the FIRST round of requests of a workgroup of the merged head
+// launch.  head_first(p) reads it from the argument block; mlp_head_bwd_pre_kernel takes it as eight leading scalar dwords, which
+// gfx950 delivers in user SGPRs at wave launch (kernel-argument preload, csrc/Makefile), so its nine staging requests and the
+// bias go out without waiting for the argument segment.
+struct HeadFirst {
+    const float *zpart, *y, *b;
+    int m, vec;
+};
+__device__ __forceinline__ HeadFirst head_first(const HeadMArgs& p);
 template <int C, int NP>
-__device__ __forceinline__ void head_stage_request(const HeadMArgs& p, const int t, HeadStage<C, NP>& h) {
+__device__ __forceinline__ void head_stage_request(const HeadFirst& p, const int t, HeadStage<C, NP>& h) {
     const int n = p.m * C;
     if (p.vec && t < (n >> 2)) {
 #pragma unroll
@@ -78,11 +88,15 @@ __device__ __forceinline__ void head_stage_request(const HeadMArgs& p, const int
         h.yv = *reinterpret_cast<const f32x4*>(p.y + 4 * t);
     }
 }
+template <int C, int NP>
+__device__ __forceinline__ void head_stage_request(const HeadMArgs& p, const int t, HeadStage<C, NP>& h) {
+    head_stage_request<C, NP>(head_first(p), t, h);
+}
 // BI: the bias of this thread's four staged elements, requested WITH the partial logits (no exec-mask branch: every index is
 // below C) — asked for inside ST it was a second dependent round trip behind the wait for everything else.  The same for
 // every row block of the row-blocked kernel (a block starts at a multiple of C floats).  The element-wise path reads its own.
 template <int C, int NP>
-__device__ __forceinline__ f32x4 head_stage_bias(const HeadMArgs& p, const int t) {
+__device__ __forceinline__ f32x4 head_stage_bias(const HeadFirst& p, const int t) {
     f32x4 b = {0.f, 0.f, 0.f, 0.f};
     if (p.vec) {
 #pragma unroll
@@ -91,7 +105,11 @@ __device__ __forceinline__ f32x4 head_stage_bias(const HeadMArgs& p, const int t
     return b;
 }
 template <int C, int NP>
-__device__ __forceinline__ void head_stage_store(const HeadMArgs& p, const int t, const HeadStage<C, NP>& h, float* zs, float* ys,
+__device__ __forceinline__ f32x4 head_stage_bias(const HeadMArgs& p, const int t) {
+    return head_stage_bias<C, NP>(head_first(p), t);
+}
+template <int C, int NP, class P>
+__device__ __forceinline__ void head_stage_store(const P& p, const int t, const HeadStage<C, NP>& h, float* zs, float* ys,
                                                  const f32x4 bias4) {
     static_assert(NP == 8, "the partial-sum tree is written for 8 tiles");
     const int n = p.m * C;
@@ -112,6 +130,8 @@ __device__ __forceinline__ void head_stage_store(const HeadMArgs& p, const int t
         }
     }
 }
+
+__device__ __forceinline__ HeadFirst head_first(const HeadMArgs& p) { return HeadFirst{p.zpart, p.y, p.b, p.m, p.vec}; }
 
 // PART: the logits arrive as H / 16 partial sums per element (tnn_dense_fwd_head_partials: the previous layer's 16-column
 // tiles each contributed their share) and are only ADDED here; otherwise every workgroup computes them itself on
@@ -365,13 +385,18 @@ struct HeadBwdArgs {
                                      // (1024 rows: 656 instead of 1168 workgroups, profiles/r06_head_rb_stamps.txt)
 };
 
+// which form the last single-GPU launch of mlp_head_bwd_kernel took (tnn_step_args_form_head): 1 = the first-request block in
+// preloaded SGPRs (mlp_head_bwd_pre_kernel), 0 = the argument block alone, -1 = none yet
+int g_head_args_form = -1;
+
 // CUT (ablation builds of round 2, template parameter only): tile roles stop after 1 = the logits, 2 = the statistics, 3 = dz, 4 = the dz1 panel.
 #ifdef TNN_STEP_TRACE
 __device__ unsigned long long g_step_trace_head[1024 * 4];       // tnn_internal.h: TNN_STEP_STAMP (kernel id 2 of the step)
 #endif
 
-template <int H, int C, int CUT = 0, int SH = 0>
-__global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdArgs q) {
+// One body under two kernels: f is the first-request block (HeadFirst), from the argument block or from preloaded SGPRs.
+template <int H, int C, int CUT, int SH>
+__device__ __forceinline__ void mlp_head_bwd_body(const HeadFirst& f, const HeadMArgs& p, const HeadBwdArgs& q) {
     constexpr int ROWS = 128, WS = 12, NP = H / 16, G = H / 8, TH = H / 16, PS = H + 4;
     static_assert(H == 128 && NP == 8, "one 16-deep K chunk per wave, 8 waves");
     TNN_STEP_STAMP(g_step_trace_head, 0, 0);
@@ -389,7 +414,13 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
     const int srow = t >> 2, sub = t & 3;
-    const int m = p.m;
+    const int m = f.m;
+    // The staging requests and the bias FIRST: they need only f, so a kernel whose f arrives in SGPRs issues them before
+    // anything waits for the argument segment; the role, its tile and its own loads (q: n_dw, the orders, x, w1; p: w, a) follow.
+    HeadStage<C, NP> stg;
+    head_stage_request<C, NP>(f, t, stg);
+    const f32x4 bias4 = head_stage_bias<C, NP>(f, t);
+    __builtin_amdgcn_sched_barrier(0);
     const bool slive = srow < m;
     const int sr = min(srow, m - 1);
     const int n_dw = q.n_dw;
@@ -407,9 +438,6 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     // dW tile: wave w takes rows 16 w .. 16 w + 15 x units n0 .. n0 + 15; dx tile: rows m0 .. m0 + 15 x units 16 w .. 16 w + 15.
     // Lane (i16, grp) supplies B[k = grp][n = i16] = W2[unit i16][class 4 s + grp] and receives P[row 4 grp + r][unit i16],
     // r = 0..3 — for the dW tile that IS the B fragment of the tile product (b[j] = dz1[16 w + 4 grp + j][n0 + i16]).
-    HeadStage<C, NP> stg;
-    head_stage_request<C, NP>(p, t, stg);
-    const f32x4 bias4 = head_stage_bias<C, NP>(p, t);
     const int urow = (is_dw ? n0 : 16 * wid) + i16;                  // this lane's hidden unit
     const int prow0 = (is_dw ? 16 * wid : m0) + 4 * grp;             // first of this lane's 4 panel rows
     float w2f[3], a1m[4];
@@ -442,7 +470,7 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
     static_assert(C == 10, "the zero columns of the K = 12 product are written for 10 classes");
 
     TNN_STEP_STAMP_ACKED(g_step_trace_head, 0, 1);
-    head_stage_store<C, NP>(p, t, stg, zs, ys, bias4);
+    head_stage_store<C, NP>(f, t, stg, zs, ys, bias4);
     __syncthreads();
     float zc[3], yc[3];
 #pragma unroll
@@ -554,6 +582,18 @@ __global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdA
         q.db1[n0 + t] = s;
     }
     TNN_STEP_STAMP_ACKED(g_step_trace_head, 0, 3);
+}
+
+template <int H, int C, int CUT = 0, int SH = 0>
+__global__ __launch_bounds__(512) void mlp_head_bwd_kernel(HeadMArgs p, HeadBwdArgs q) {
+    mlp_head_bwd_body<H, C, CUT, SH>(head_first(p), p, q);
+}
+// The single-GPU form with its first-request block as eight leading scalar dwords (three pointers, m, vec): preloaded into user
+// SGPRs, the rest of p and q in one group of scalar loads whose wait stands behind the staging requests.
+template <int H, int C>
+__global__ __launch_bounds__(512) void mlp_head_bwd_pre_kernel(const float* zpart, const float* y, const float* b, int m, int vec,
+                                                               HeadMArgs p, HeadBwdArgs q) {
+    mlp_head_bwd_body<H, C, 0, 0>(HeadFirst{zpart, y, b, m, vec}, p, q);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1554,7 +1594,13 @@ int head_bwd_launch(const char* fn, const float* ext_pairs, int ext_n, bool whol
         TNN_LAUNCH_OK();
         return 0;
     }
-    hipLaunchKernelGGL((mlp_head_bwd_kernel<128, 10>), grid, 512, 0, tnn::stream(), p, q);
+    // the first-request block as leading scalars (user SGPRs) unless TNN_STEP_ARGS=struct[:..head..] asks for the argument block
+    // (read per call, as in tnn_gemm.hip); every launch of this form fits the block
+    const char* sw = getenv("TNN_STEP_ARGS");
+    const bool forced = sw != nullptr && strncmp(sw, "struct", 6) == 0 && (sw[6] == 0 || (sw[6] == ':' && strstr(sw + 7, "head") != nullptr));
+    g_head_args_form = forced ? 0 : 1;
+    if (forced) hipLaunchKernelGGL((mlp_head_bwd_kernel<128, 10>), grid, 512, 0, tnn::stream(), p, q);
+    else hipLaunchKernelGGL((mlp_head_bwd_pre_kernel<128, 10>), grid, 512, 0, tnn::stream(), p.zpart, p.y, p.b, p.m, p.vec, p, q);
     TNN_LAUNCH_OK();
     return 0;
 }
@@ -1563,6 +1609,9 @@ int head_bwd_launch(const char* fn, const float* ext_pairs, int ext_n, bool whol
 }  // namespace
 
 extern "C" {
+
+// for tests/test_gpu_step_arg_sgprs.py (as tnn_step_args_form in tnn_gemm.hip); not part of include/tnn_hip.h
+__attribute__((visibility("default"))) int tnn_step_args_form_head(void) { return g_head_args_form; }
 
 #ifdef TNN_STEP_TRACE
 __attribute__((visibility("default"))) int tnn_debug_step_trace_head(unsigned long long* out, int n) {

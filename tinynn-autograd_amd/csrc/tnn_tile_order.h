@@ -76,4 +76,39 @@ TNN_TILE_ORDER_HD void tile_coords(const TileOrder& o, const int block, int& tm,
     tn = (int)((xcd >> o.xm_shift) * o.pn + q);
 }
 
+// The same order in three dwords, for a kernel that takes it as scalar parameters (a by-value struct is not preloaded into
+// user SGPRs, three leading scalars are): a second READER of the values above, not a second order.
+//   w[0] = pm | pn << 16          both <= 65,535
+//   w[1] = the low 32 bits of magic; only pm == 1 has a 33rd bit (magic = 2^32 + 1), and the reader puts it back from pm
+//   w[2] = xcd_mask | xcd_shift << 3 | xm_mask << 5 | xm_shift << 8; bits 16 .. 31 are the caller's own flags
+struct PackedTileOrder {
+    uint32_t w[3];
+};
+constexpr uint32_t kPackedOrderFlagShift = 16;
+
+// false (and `p` untouched) for an order the three dwords cannot hold: a rectangle side above 65,535, a mask or shift outside
+// its field, or a magic that is not the reciprocal of pm — the caller keeps the unpacked form then
+inline bool pack_tile_order(const TileOrder& o, PackedTileOrder& p) {
+    if (o.pm == 0 || o.pm > 65535u || o.pn > 65535u) return false;
+    if (o.magic != (uint64_t(1) << 32) / o.pm + 1) return false;
+    if (o.xcd_mask > 7u || o.xcd_shift > 3u || o.xm_mask > 7u || o.xm_shift > 3u) return false;
+    p.w[0] = o.pm | o.pn << 16;
+    p.w[1] = (uint32_t)o.magic;
+    p.w[2] = o.xcd_mask | o.xcd_shift << 3 | o.xm_mask << 5 | o.xm_shift << 8;
+    return true;
+}
+
+// the fields back out (on the device: scalar bit-field extracts and one scalar select for pm == 1); tile_coords reads the result
+TNN_TILE_ORDER_HD TileOrder unpack_tile_order(const uint32_t w0, const uint32_t w1, const uint32_t w2) {
+    TileOrder o;
+    o.pm = w0 & 0xffffu;
+    o.pn = w0 >> 16;
+    o.magic = (o.pm == 1u ? uint64_t(1) << 32 : uint64_t(0)) | w1;
+    o.xcd_mask = w2 & 7u;
+    o.xcd_shift = (w2 >> 3) & 3u;
+    o.xm_mask = (w2 >> 5) & 7u;
+    o.xm_shift = (w2 >> 8) & 3u;
+    return o;
+}
+
 }  // namespace tnn
