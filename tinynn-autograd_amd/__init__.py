@@ -65,6 +65,7 @@ from . import ostep
 from . import rng
 from . import gated
 from . import extend
+from . import varlen
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

@@ -87,6 +87,10 @@ from ._extend_signatures import _EXTEND_SIGNATURES            # noqa: E402  (inc
 
 EXTEND_SYMBOLS = sorted(_EXTEND_SIGNATURES)
 
+from ._varlen_signatures import _VARLEN_SIGNATURES            # noqa: E402  (include/tnn_varlen.h: libtnn_hip.so only)
+
+VARLEN_SYMBOLS = sorted(_VARLEN_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -162,6 +166,8 @@ class _Lib(object):
         # products and sums on slices (gated.py; the exact-GELU gate has no composed form and raises there)
         # and cache-extending attention (include/tnn_extend.h): under the twin device_array slice-assigns the new rows and
         # runs the composed attention over the live prefix with the offset mask (extend.py)
+        # and training attention with per-sequence lengths (include/tnn_varlen.h): under the twin device_array runs the
+        # composed attention with a key mask and a row mask built from the lengths on the host (varlen.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -175,7 +181,8 @@ class _Lib(object):
                                     (_GQA_SIGNATURES, "tnn_gqa.h", "grouped-query attention"),
                                     (_ROPE_SIGNATURES, "tnn_rope.h", "rotary position embedding"),
                                     (_GATED_SIGNATURES, "tnn_gated.h", "gated activation"),
-                                    (_EXTEND_SIGNATURES, "tnn_extend.h", "cache-extending attention")):
+                                    (_EXTEND_SIGNATURES, "tnn_extend.h", "cache-extending attention"),
+                                    (_VARLEN_SIGNATURES, "tnn_varlen.h", "attention with per-sequence lengths")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -199,6 +206,7 @@ class _Lib(object):
         self.has_rope = hasattr(self.cdll, "tnn_rope_apply")
         self.has_gated = hasattr(self.cdll, "tnn_gated_fwd")
         self.has_extend = hasattr(self.cdll, "tnn_extend_attn")
+        self.has_varlen = hasattr(self.cdll, "tnn_varlen_fwd")
 
     @staticmethod
     def _absent(name, what):

@@ -258,8 +258,12 @@ class MultiHeadAttention(Layer):
             self.params[name] = tensor
         self.is_init = True
 
-    def forward(self, inputs, cache=None):
-        """cache: a generation.LayerCache (inference).  Empty: the PREFILL — the ordinary causal path runs and its k and v
+    def forward(self, inputs, cache=None, lens=None):
+        """lens (training over a right-padded batch): a ragged.Lengths or a dense int64 device array [B] — sequence b has
+        lens[b] live tokens; the attention op gets it (ops.attention_: live rows attend over live keys only, dead rows come
+        out as +0 before the output projection, padding is never read on the native route).  Not with a cache.  None: today's
+        path, launch for launch.
+        cache: a generation.LayerCache (inference).  Empty: the PREFILL — the ordinary causal path runs and its k and v
         [B, T, H, E / H] are slice-assigned into the cache; afterwards T must be 1: three projections of the one row,
         ops.attention_decode_ with the append, the output projection.  A cache with `lens` set (a ragged batch) takes
         ops.attention_decode_ragged_, which reads every sequence's length on the device; cache.length stays the host's upper
@@ -269,6 +273,9 @@ class MultiHeadAttention(Layer):
         the new ones and appends them; T == 1 keeps taking the decode ops."""
         if len(inputs.shape) != 3:
             raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
+        if lens is not None and cache is not None:
+            raise ValueError("MultiHeadAttention: lens= (training over a padded batch) and cache= (generation) do not go "
+                             "together; a ragged generation batch keeps its lengths in the cache")
         b, t, e = (int(s) for s in inputs.shape)
         if not self.is_init:
             self._init_parameters(e)
@@ -315,9 +322,9 @@ class MultiHeadAttention(Layer):
             if self.rope is not None:
                 q, k = ops.rope_(q, k, rotary=self.rope, route=route)
             if grouped:
-                att = ops.attention_gqa_(q, k, v, causal=self.causal, route=route)
+                att = ops.attention_gqa_(q, k, v, causal=self.causal, route=route, lens=lens)
             else:
-                att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route)
+                att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route, lens=lens)
             if cache is not None:
                 cache.fill(k.values, v.values)
         out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
@@ -518,10 +525,13 @@ class TransformerBlock(Layer):
             self.params[key] = parts[part].params[name]
         self.is_init = True
 
-    def forward(self, inputs, cache=None):
-        """cache: handed to the attention part (MultiHeadAttention.forward); None: today's path."""
+    def forward(self, inputs, cache=None, lens=None):
+        """cache, lens: handed to the attention part (MultiHeadAttention.forward); None: today's path.  lens together with a
+        cache raises before any launch."""
         if len(inputs.shape) != 3:
             raise ValueError("TransformerBlock: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
+        if lens is not None and cache is not None:
+            raise ValueError("TransformerBlock: lens= (training over a padded batch) and cache= (generation) do not go together")
         b, t, e = (int(s) for s in inputs.shape)
         if not self.is_init:
             self._init_parameters(e)
@@ -535,7 +545,7 @@ class TransformerBlock(Layer):
         if self.rope is not None:
             parts["attn"]._check_rope(t, cache)          # positions beyond the rotary tables raise before ANY launch
         normed = parts["ln1"].forward(inputs)
-        h = self.drop.forward(parts["attn"].forward(normed, cache=cache), residual=inputs)     # (inactive: inputs + attn)
+        h = self.drop.forward(parts["attn"].forward(normed, cache=cache, lens=lens), residual=inputs)   # (inactive: inputs + attn)
         z = parts["fc1"].forward(ops.reshape(parts["ln2"].forward(h), (b * t, e)))
         act = MLP_FORMS[self.mlp]
         if act is None:

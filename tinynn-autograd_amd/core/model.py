@@ -53,8 +53,9 @@ class Model(object):
         self._pending_first = None   # (x, dz, w, rows, n_in, n_out): the first Dense layer's backward, deferred to step()
         self._clip_rec = self._clip_ws = None    # clip_grad_norm's device record and workspace (include/tnn_ostep.h)
 
-    def forward(self, inputs):
-        return self.net.forward(inputs)
+    def forward(self, inputs, lens=None):
+        """lens: per-sequence lengths of a right-padded batch, handed to the layers that take them (Net.forward)."""
+        return self.net.forward(inputs) if lens is None else self.net.forward(inputs, lens=lens)
 
     def get_phase(self):
         return self._phase

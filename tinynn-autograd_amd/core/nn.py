@@ -2,7 +2,22 @@
 iteration over parameter tensors in the optimizer's flattening order, parameter counting and the Dense/ReLU
 structure query the whole-step trainer uses."""
 
+import inspect
+
 from .layers import Conv2D, Dense, ReLU
+
+_TAKES_LENS = {}      # layer type -> its forward declares `lens`
+
+
+def _takes_lens(layer):
+    known = _TAKES_LENS.get(type(layer))
+    if known is None:
+        try:
+            known = "lens" in inspect.signature(type(layer).forward).parameters
+        except (TypeError, ValueError):
+            known = False
+        _TAKES_LENS[type(layer)] = known
+    return known
 
 
 class Net(object):
@@ -14,8 +29,10 @@ class Net(object):
         self._phase = "TRAIN"
 
     # ------------------------------------------------------------------ reference API
-    def forward(self, inputs):
-        """Thread the input through the layers (core/nn.py:10-13).  A fused `Dense` directly followed by a `ReLU` runs
+    def forward(self, inputs, lens=None):
+        """lens (per-sequence lengths of a right-padded batch: MultiHeadAttention.forward) is handed to the layers whose
+        `forward` declares it, as generation does for `cache`; None: nothing changes.
+        Thread the input through the layers (core/nn.py:10-13).  A fused `Dense` directly followed by a `ReLU` runs
         as ONE node (GEMM + bias + clip(., 0) epilogue, ops.dense_(relu=True); likewise a fused `Conv2D`, ops.conv2d_); the
         ReLU layer object is then skipped —
         its `inputs` attribute (cached but never read by the reference, core/layers.py:67) holds the fused output."""
@@ -39,6 +56,9 @@ class Net(object):
                 activations = layer.forward(activations, relu=True)       # clip(., 0) in the convolution's epilogue
                 nxt.inputs = activations
                 i += 2
+            elif lens is not None and _takes_lens(layer):
+                activations = layer.forward(activations, lens=lens)
+                i += 1
             else:
                 activations = layer.forward(activations, lazy=True) if (head and i == n - 1) else layer.forward(activations)
                 i += 1

@@ -611,6 +611,11 @@ class _AttnVjp(object):
         return [res[name] for name in edges]
 
 
+def _lens_opt(lens):
+    """lens= as an option of the node (saved for the vjps; never differentiated); None: the options are today's."""
+    return {} if lens is None else {"lens": _raw_values(lens)}
+
+
 def _attn_node(q, k, v, fwd, bwd_q, bwd_kv, **opts):
     """The node of attention_ / attention_gqa_: `fwd` with the options, and an _AttnVjp that hands them to the backward."""
     out, lse = fwd(q.values, k.values, v.values, **opts)
@@ -621,14 +626,21 @@ def _attn_node(q, k, v, fwd, bwd_q, bwd_kv, **opts):
     return node
 
 
-def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **unknown):
+def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, lens=None, **unknown):
     """Scaled-dot-product attention node: softmax(scale q k^T) v, softmax over the key axis, scale = 1 / sqrt(D) by default.
 
     layout "bhtd": q [..., Tq, D], k [..., Tk, D], v [..., Tk, Dv] -> [..., Tq, Dv] (identical leading dimensions, no
     broadcasting); layout "bthd": q [B, Tq, H, D], k [B, Tk, H, D], v [B, Tk, H, Dv] -> [B, Tq, H, Dv], what a [B T, H D]
     projection reshapes to for free.  causal=True keeps key j for query i iff j <= i (top-left aligned for any Tq, Tk).
-    float32 and float64; other dtypes are promoted the way matmul promotes them.  Out of scope: arbitrary or padding masks,
-    dropout, bf16 — unknown keyword arguments raise.
+    float32 and float64; other dtypes are promoted the way matmul promotes them.  Out of scope: arbitrary masks, dropout,
+    bf16 — unknown keyword arguments raise.
+
+    lens (a ragged.Lengths or a dense int64 device array [B], not differentiable; Tq == Tk, layout "bthd" or three-axis
+    "bhtd"): sequence b of a right-padded batch has lens[b] live tokens.  Live rows attend over live keys only; dead rows get
+    o = +0 and dq = +0, dead keys dk = dv = +0; lens[b] == 0 is an all-zero sequence.  Forward and both backward launches are
+    then tnn_varlen_* (include/tnn_varlen.h): the lengths are read on the device, whole 64-row blocks of padding are skipped
+    and padding is never read.  A host sequence raises TypeError; a Lengths with a value outside [0, T] raises before any
+    launch.  The composed route masks on the host (varlen.py).
 
     Forward is ONE tnn_attn_fwd launch (online softmax on MFMA; the [Tq, Tk] scores never reach memory) that also keeps the
     per-row log-sum-exp.  Backward recomputes the probabilities from it: dq from one launch (not computed when q does not
@@ -637,10 +649,10 @@ def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, **u
     if unknown:
         raise TypeError("attention_: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
     return _attn_node(q, k, v, da.attention, da.attention_bwd_q, da.attention_bwd_kv, causal=causal, scale=scale, layout=layout,
-                      route=route)
+                      route=route, **_lens_opt(lens))
 
 
-def attention_gqa_(q, k, v, causal=False, scale=None, route=None, **unknown):
+def attention_gqa_(q, k, v, causal=False, scale=None, route=None, lens=None, **unknown):
     """Grouped-query attention node, layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] -> [B, Tq, H, Dv]
     with H a multiple of Hkv; query head h attends over key / value head h // (H / Hkv).  Hkv == 1 is multi-query attention,
     Hkv == H gives attention_'s result bit for bit.  The causal rule, the scale and the dtypes are attention_'s.
@@ -649,13 +661,14 @@ def attention_gqa_(q, k, v, causal=False, scale=None, route=None, **unknown):
     which a workgroup owns a key block of ONE key / value head and adds its group's query heads in a fixed order (no atomics,
     dk and dv are written once, in the shapes of k and v), into lent arena views when there are any.  Under the CPU test
     twin, with route="composed" (or device_array.GQA_ROUTE), beyond head dimension 128 and for groups above 8, k and v are
-    repeated over the group, the composed attention runs and dk / dv are summed over the group axis.  Out of scope: masks,
+    repeated over the group, the composed attention runs and dk / dv are summed over the group axis.  lens: per-sequence
+    lengths of a right-padded batch, as attention_ (the same tnn_varlen_* launches, with the group).  Out of scope: masks,
     dropout, bf16, other layouts — unknown keyword arguments raise."""
     if unknown:
         raise TypeError("attention_gqa_: unsupported arguments %s (masks, dropout, bf16 and other layouts than \"bthd\" are out "
                         "of scope)" % sorted(unknown))
     return _attn_node(q, k, v, da.gqa_attention, da.gqa_attention_bwd_q, da.gqa_attention_bwd_kv, causal=causal, scale=scale,
-                      route=route)
+                      route=route, **_lens_opt(lens))
 
 
 def rope_(q, k=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, route=None, **unknown):
@@ -1314,11 +1327,11 @@ def max_pool2d(obj, kernel, stride=None, padding=0):
     return max_pool2d_(as_tensor(obj), kernel, stride=stride, padding=padding)
 
 
-def attention(obj, k, v, causal=False, scale=None, layout="bhtd", **unknown):
+def attention(obj, k, v, causal=False, scale=None, layout="bhtd", lens=None, **unknown):
     """not in the reference: see attention_ (masks, dropout and bf16 are out of scope: unknown keyword arguments raise)"""
     if unknown:
         raise TypeError("attention: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
-    return attention_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, layout=layout)
+    return attention_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, layout=layout, lens=lens)
 
 
 def _opt_tensor(obj):
@@ -1381,11 +1394,11 @@ def cross_entropy(obj, targets, ignore_index=None, reduction="mean", **unknown):
     return cross_entropy_(as_tensor(obj), targets, ignore_index=ignore_index, reduction=reduction)
 
 
-def attention_gqa(obj, k, v, causal=False, scale=None, **unknown):
+def attention_gqa(obj, k, v, causal=False, scale=None, lens=None, **unknown):
     """not in the reference: see attention_gqa_ (grouped-query heads, layout "bthd"; unknown keyword arguments raise)"""
     if unknown:
         raise TypeError("attention_gqa: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
-    return attention_gqa_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale)
+    return attention_gqa_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, lens=lens)
 
 
 def rope(obj, k=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, **unknown):

@@ -5,6 +5,13 @@
 // (b, key / value head, key block), walks the group's query heads in ascending order and inside each its query blocks, with
 // k, v, dk and dv in registers throughout, and writes once.  Internal: not installed under include/.
 //
+// A second parameter, LENS (csrc/tnn_varlen.hip, include/tnn_varlen.h: a right-padded self-attention batch).  LENS = false is
+// the kernel as it was, instruction for instruction (profiles/varlen_resource_usage.txt).  LENS = true: sequence b has
+// n_b = clamp(lens[b], 0, T) live rows, read from a device array, and n_b takes the place of Tq and Tk wherever the body bounds
+// rows — loop ends, the row limits of stage_tile and load_rows, the masks — while T stays the stride of lse and delta and the
+// extent of the grid.  Rows at and beyond n_b are never read and get +0 (lse, delta: 0); a workgroup (float64: a wave) wholly
+// beyond it writes its zeros and returns before its first barrier.
+//
 //     o = softmax(scale q k^T) v        forward: online softmax over key blocks, the scores never reach memory
 //     dq, dk, dv                        two recompute kernels: p is rebuilt from the saved log-sum-exp
 //
@@ -52,6 +59,7 @@ struct AttnArgs {
     double scale;
     int causal;
     int group;              // query heads per key / value head (read by the GROUPED kernels alone; H is the QUERY head count)
+    const int64_t* lens;    // live rows of every batch entry, dense [B] (read by the LENS kernels alone; last: no offset above moves)
 };
 
 // the key / value head of query head h
@@ -59,6 +67,31 @@ template <bool GROUPED>
 __device__ __forceinline__ int64_t kv_head(const AttnArgs& a, int64_t h) {
     if constexpr (GROUPED) return h / a.group;
     else return h;
+}
+
+// the live rows of batch entry b out of T: T itself unless LENS, then lens[b] clamped to [0, T] — uniform over the workgroup
+// (f64: over the wave), so every test against it is a scalar branch
+template <bool LENS>
+__device__ __forceinline__ int64_t live_rows(const AttnArgs& a, int64_t b, int64_t T) {
+    if constexpr (LENS) {
+        const int64_t n = a.lens[b];
+        return n < 0 ? 0 : n > T ? T : n;
+    } else {
+        return T;
+    }
+}
+
+// the same for a kernel whose !LENS instantiation must keep reading the field AT the use site (attn_bwd_kv_f32: with the
+// extent in a local, hipcc orders the dk and dv accumulators of its NT = 1 form the other way round)
+template <bool LENS>
+__device__ __forceinline__ int64_t rows_q(const AttnArgs& a, int64_t n_b) {
+    if constexpr (LENS) return n_b;
+    else return a.Tq;
+}
+template <bool LENS>
+__device__ __forceinline__ int64_t rows_k(const AttnArgs& a, int64_t n_b) {
+    if constexpr (LENS) return n_b;
+    else return a.Tk;
 }
 
 template <typename T>
@@ -175,6 +208,14 @@ __device__ __forceinline__ void store_rows(float* __restrict__ P, int64_t rs, in
         store4(P + row * rs, 16 * c + 4 * g, W, vec, acc[c][0] * mul, acc[c][1] * mul, acc[c][2] * mul, acc[c][3] * mul);
 }
 
+// +0 into the wave's result rows (the LENS kernels: rows at and beyond the sequence's length)
+template <int NT>
+__device__ __forceinline__ void zero_rows(float* __restrict__ P, int64_t rs, int64_t row, bool ok, int64_t W, bool vec, int g) {
+    if (!ok) return;
+#pragma unroll
+    for (int c = 0; c < NT; ++c) store4(P + row * rs, 16 * c + 4 * g, W, vec, 0.f, 0.f, 0.f, 0.f);
+}
+
 __device__ __forceinline__ float group_sum(float v) {        // over the four lanes that share lane & 15
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
@@ -187,7 +228,7 @@ __device__ __forceinline__ float group_max(float v) {
 }
 
 // ---------------------------------------------------------------------------------------------- float32 forward
-template <int NT, bool GROUPED>
+template <int NT, bool GROUPED, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_fwd_f32(AttnArgs a) {
     constexpr int LD = 16 * NT + 4;
     __shared__ __attribute__((aligned(16))) float Ks[BKV * LD];
@@ -200,9 +241,18 @@ __global__ __launch_bounds__(256) void attn_fwd_f32(AttnArgs a) {
     const float* __restrict__ K = at<float>(a.k, a.sk, b, kv_head<GROUPED>(a, h));
     const float* __restrict__ V = at<float>(a.v, a.sv, b, kv_head<GROUPED>(a, h));
     const int64_t qrow = q0 + WR * wid + i;
-    const bool q_ok = qrow < a.Tq;
+    const int64_t Tq = live_rows<LENS>(a, b, a.Tq), Tk = live_rows<LENS>(a, b, a.Tk);      // (LENS: Tq == Tk, one value)
+    const bool q_ok = qrow < Tq;
     const float scale = (float)a.scale;
     const bool causal = a.causal != 0;
+    if constexpr (LENS) {
+        // rows at and beyond the length: o = +0, lse = 0, nothing of theirs is read; a block wholly beyond it ends here
+        // (uniform over the workgroup, before the first barrier)
+        const bool dead = !q_ok && qrow < a.Tq;
+        zero_rows<NT>(at<float>(a.out, a.so, b, h), a.so.sr, qrow, dead, a.Dv, a.so.vec != 0, g);
+        if (dead && g == 0) static_cast<float*>(a.lse_out)[bh * a.Tq + qrow] = 0.f;
+        if (q0 >= Tq) return;
+    }
 
     float4 qr[NT];
     load_rows<NT>(qr, Q, a.sq.sr, qrow, q_ok, a.D, a.sq.vec != 0, g);
@@ -213,12 +263,12 @@ __global__ __launch_bounds__(256) void attn_fwd_f32(AttnArgs a) {
 
     // causal: the block's last query sees keys < q0 + 64, so every processed key block starts at k0 <= q0 <= qrow and
     // keeps at least key k0 for every row — no row of a processed block is empty, m stays finite
-    int64_t kend = a.Tk;
+    int64_t kend = Tk;
     if (causal && q0 + BQ < kend) kend = q0 + BQ;
     for (int64_t k0 = 0; k0 < kend; k0 += BKV) {
         __syncthreads();                          // the previous block's reads are done
-        stage_tile<NT>(Ks, K, a.sk.sr, k0, a.Tk, a.D, a.sk.vec != 0, tid);
-        stage_tile<NT>(Vs, V, a.sv.sr, k0, a.Tk, a.Dv, a.sv.vec != 0, tid);
+        stage_tile<NT>(Ks, K, a.sk.sr, k0, Tk, a.D, a.sk.vec != 0, tid);
+        stage_tile<NT>(Vs, V, a.sv.sr, k0, Tk, a.Dv, a.sv.vec != 0, tid);
         __syncthreads();
         f32x4 s[4];
         rows_times_regs<NT>(s, Ks, qr, i, g);
@@ -229,7 +279,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32(AttnArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int64_t key = k0 + 16 * t + 4 * g + r;
                 float x = s[t][r] * scale;
-                if (key >= a.Tk || (causal && key > qrow)) x = -INFINITY;
+                if (key >= Tk || (causal && key > qrow)) x = -INFINITY;
                 s[t][r] = x;
                 mx = fmaxf(mx, x);
             }
@@ -260,7 +310,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- float32 dq (+ delta)
-template <int NT, bool GROUPED>
+template <int NT, bool GROUPED, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_bwd_q_f32(AttnArgs a) {
     constexpr int LD = 16 * NT + 4;
     __shared__ __attribute__((aligned(16))) float Ks[BKV * LD];
@@ -270,9 +320,17 @@ __global__ __launch_bounds__(256) void attn_bwd_q_f32(AttnArgs a) {
     const int64_t bh = blockIdx.x / nqb, q0 = (blockIdx.x % nqb) * BQ;
     const int64_t b = bh / a.H, h = bh % a.H;
     const int64_t qrow = q0 + WR * wid + i;
-    const bool q_ok = qrow < a.Tq;
+    const int64_t Tq = live_rows<LENS>(a, b, a.Tq), Tk = live_rows<LENS>(a, b, a.Tk);
+    const bool q_ok = qrow < Tq;
     const float scale = (float)a.scale;
     const bool causal = a.causal != 0;
+    if constexpr (LENS) {
+        // rows at and beyond the length: delta = 0, dq = +0, nothing of theirs is read; a block wholly beyond it ends here
+        const bool dead = !q_ok && qrow < a.Tq;
+        if (dead && g == 0) static_cast<float*>(a.delta_out)[bh * a.Tq + qrow] = 0.f;
+        if (a.dq != nullptr) zero_rows<NT>(at<float>(a.dq, a.sdq, b, h), a.sdq.sr, qrow, dead, a.D, a.sdq.vec != 0, g);
+        if (q0 >= Tq) return;
+    }
 
     float4 dor[NT];
     load_rows<NT>(dor, at<float>(a.d_o, a.sdo, b, h), a.sdo.sr, qrow, q_ok, a.Dv, a.sdo.vec != 0, g);
@@ -298,12 +356,12 @@ __global__ __launch_bounds__(256) void attn_bwd_q_f32(AttnArgs a) {
 #pragma unroll
     for (int c = 0; c < NT; ++c) dq[c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    int64_t kend = a.Tk;
+    int64_t kend = Tk;
     if (causal && q0 + BQ < kend) kend = q0 + BQ;
     for (int64_t k0 = 0; k0 < kend; k0 += BKV) {
         __syncthreads();
-        stage_tile<NT>(Ks, K, a.sk.sr, k0, a.Tk, a.D, a.sk.vec != 0, tid);
-        stage_tile<NT>(Vs, V, a.sv.sr, k0, a.Tk, a.Dv, a.sv.vec != 0, tid);
+        stage_tile<NT>(Ks, K, a.sk.sr, k0, Tk, a.D, a.sk.vec != 0, tid);
+        stage_tile<NT>(Vs, V, a.sv.sr, k0, Tk, a.Dv, a.sv.vec != 0, tid);
         __syncthreads();
         f32x4 s[4], dp[4];
         rows_times_regs<NT>(s, Ks, qr, i, g);
@@ -313,7 +371,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_f32(AttnArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t key = k0 + 16 * t + 4 * g + r;
-                const bool masked = key >= a.Tk || (causal && key > qrow);
+                const bool masked = key >= Tk || (causal && key > qrow);
                 const float p = masked ? 0.f : expf(s[t][r] * scale - lse);
                 s[t][r] = p * (dp[t][r] - delta);
             }
@@ -324,7 +382,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_f32(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- float32 dk, dv
-template <int NT, bool GROUPED>
+template <int NT, bool GROUPED, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_f32(AttnArgs a) {
     constexpr int LD = 16 * NT + 4;
     __shared__ __attribute__((aligned(16))) float Qs[BQ * LD];
@@ -337,10 +395,18 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_f32(AttnArgs a) {
     const int64_t group = GROUPED ? a.group : 1, HK = GROUPED ? a.H / group : a.H;     // bh runs over the key / value heads
     const int64_t b = bh / HK, h = bh % HK;
     const int64_t krow = k0 + WR * wid + i;
-    const bool k_ok = krow < a.Tk;
+    const int64_t n_b = live_rows<LENS>(a, b, a.Tk);         // (used through rows_q / rows_k: see there)
+    const bool k_ok = krow < rows_k<LENS>(a, n_b);
     const float scale = (float)a.scale;
     const bool causal = a.causal != 0;
     const bool want_dk = a.dk != nullptr, want_dv = a.dv != nullptr;
+    if constexpr (LENS) {
+        // keys at and beyond the length: dk = dv = +0, nothing of theirs is read; a block wholly beyond it ends here
+        const bool dead = !k_ok && krow < a.Tk;
+        if (want_dk) zero_rows<NT>(at<float>(a.dk, a.sdk, b, h), a.sdk.sr, krow, dead, a.D, a.sdk.vec != 0, g);
+        if (want_dv) zero_rows<NT>(at<float>(a.dv, a.sdv, b, h), a.sdv.sr, krow, dead, a.Dv, a.sdv.vec != 0, g);
+        if (k0 >= n_b) return;
+    }
 
     // the first query head of this key / value head (the only one unless GROUPED); lse and delta are dense over the QUERY heads
     const int64_t row0 = GROUPED ? b * a.H + h * group : bh;
@@ -366,12 +432,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_f32(AttnArgs a) {
         const float* __restrict__ LSE = LSE0 + x * a.Tq;
         const float* __restrict__ DEL = DEL0 + x * a.Tq;
         // causal: the first query that sees this key block is query k0 (a multiple of the block): start at its block
-        for (int64_t q0 = causal ? k0 : 0; q0 < a.Tq; q0 += BQ) {
+        for (int64_t q0 = causal ? k0 : 0; q0 < rows_q<LENS>(a, n_b); q0 += BQ) {
             __syncthreads();
-            stage_tile<NT>(Qs, Q, a.sq.sr, q0, a.Tq, a.D, a.sq.vec != 0, tid);
-            stage_tile<NT>(Gs, G, a.sdo.sr, q0, a.Tq, a.Dv, a.sdo.vec != 0, tid);
+            stage_tile<NT>(Qs, Q, a.sq.sr, q0, rows_q<LENS>(a, n_b), a.D, a.sq.vec != 0, tid);
+            stage_tile<NT>(Gs, G, a.sdo.sr, q0, rows_q<LENS>(a, n_b), a.Dv, a.sdo.vec != 0, tid);
             if (tid < BQ) {
-                const bool ok = q0 + tid < a.Tq;
+                const bool ok = q0 + tid < rows_q<LENS>(a, n_b);
                 lse_s[tid] = ok ? LSE[q0 + tid] : 0.f;
                 delta_s[tid] = ok ? DEL[q0 + tid] : 0.f;
             }
@@ -385,7 +451,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_f32(AttnArgs a) {
                 for (int r = 0; r < 4; ++r) {
                     const int ql = 16 * t + 4 * g + r;
                     const int64_t qq = q0 + ql;
-                    const bool masked = qq >= a.Tq || !k_ok || (causal && krow > qq);
+                    const bool masked = qq >= rows_q<LENS>(a, n_b) || !k_ok || (causal && krow > qq);
                     const float p = masked ? 0.f : expf(s[t][r] * scale - lse_s[ql]);
                     s[t][r] = p;
                     dp[t][r] = p * (dp[t][r] - delta_s[ql]);
@@ -406,16 +472,26 @@ __device__ __forceinline__ double dot64(const double* __restrict__ x, const doub
     return s;
 }
 
-template <bool GROUPED>
+template <bool GROUPED, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_fwd_f64(AttnArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= a.B * a.H * a.Tq) return;            // (whole waves leave; no barrier below)
     const int64_t bh = w / a.Tq, qi = w % a.Tq, b = bh / a.H, h = bh % a.H;
+    const int64_t Tk = live_rows<LENS>(a, b, a.Tk);
+    if constexpr (LENS) {
+        if (qi >= Tk) {                           // a row at or beyond the length: o = +0, lse = 0, nothing is read
+            double* __restrict__ o = at<double>(a.out, a.so, b, h) + qi * a.so.sr;
+            if (lane < a.Dv) o[lane] = 0.0;
+            if (lane + 64 < a.Dv) o[lane + 64] = 0.0;
+            if (lane == 0) static_cast<double*>(a.lse_out)[w] = 0.0;
+            return;
+        }
+    }
     const double* __restrict__ q = at<double>(a.q, a.sq, b, h) + qi * a.sq.sr;
     const double* __restrict__ K = at<double>(a.k, a.sk, b, kv_head<GROUPED>(a, h));
     const double* __restrict__ V = at<double>(a.v, a.sv, b, kv_head<GROUPED>(a, h));
-    const int64_t kend = (a.causal && qi + 1 < a.Tk) ? qi + 1 : a.Tk;
+    const int64_t kend = (a.causal && qi + 1 < Tk) ? qi + 1 : Tk;
     double m = -INFINITY, l = 0.0, o0 = 0.0, o1 = 0.0;      // this lane's output columns: lane and lane + 64
     for (int64_t j0 = 0; j0 < kend; j0 += 64) {
         const int64_t j = j0 + lane;
@@ -442,12 +518,24 @@ __global__ __launch_bounds__(256) void attn_fwd_f64(AttnArgs a) {
     if (lane == 0) static_cast<double*>(a.lse_out)[w] = m + log(l);
 }
 
-template <bool GROUPED>
+template <bool GROUPED, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_bwd_q_f64(AttnArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= a.B * a.H * a.Tq) return;
     const int64_t bh = w / a.Tq, qi = w % a.Tq, b = bh / a.H, h = bh % a.H;
+    const int64_t Tk = live_rows<LENS>(a, b, a.Tk);
+    if constexpr (LENS) {
+        if (qi >= Tk) {                           // a row at or beyond the length: delta = 0, dq = +0, nothing is read
+            if (lane == 0) static_cast<double*>(a.delta_out)[w] = 0.0;
+            if (a.dq != nullptr) {
+                double* __restrict__ dq = at<double>(a.dq, a.sdq, b, h) + qi * a.sdq.sr;
+                if (lane < a.D) dq[lane] = 0.0;
+                if (lane + 64 < a.D) dq[lane + 64] = 0.0;
+            }
+            return;
+        }
+    }
     const double* __restrict__ g = at<double>(a.d_o, a.sdo, b, h) + qi * a.sdo.sr;
     const double* __restrict__ o = at<double>(a.o, a.so, b, h) + qi * a.so.sr;
     double part = 0.0;
@@ -460,7 +548,7 @@ __global__ __launch_bounds__(256) void attn_bwd_q_f64(AttnArgs a) {
     const double* __restrict__ K = at<double>(a.k, a.sk, b, kv_head<GROUPED>(a, h));
     const double* __restrict__ V = at<double>(a.v, a.sv, b, kv_head<GROUPED>(a, h));
     const double lse = static_cast<const double*>(a.lse)[w];
-    const int64_t kend = (a.causal && qi + 1 < a.Tk) ? qi + 1 : a.Tk;
+    const int64_t kend = (a.causal && qi + 1 < Tk) ? qi + 1 : Tk;
     double d0 = 0.0, d1 = 0.0;
     for (int64_t j0 = 0; j0 < kend; j0 += 64) {
         const int64_t j = j0 + lane;
@@ -482,13 +570,29 @@ __global__ __launch_bounds__(256) void attn_bwd_q_f64(AttnArgs a) {
     if (lane + 64 < a.D) dq[lane + 64] = a.scale * d1;
 }
 
-template <bool GROUPED>
+template <bool GROUPED, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_bwd_kv_f64(AttnArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t group = GROUPED ? a.group : 1, HK = GROUPED ? a.H / group : a.H;     // one wave per (b, key / value head, key)
     if (w >= a.B * HK * a.Tk) return;
     const int64_t bh = w / a.Tk, kj = w % a.Tk, b = bh / HK, h = bh % HK;
+    const int64_t Tq = live_rows<LENS>(a, b, a.Tq);
+    if constexpr (LENS) {
+        if (kj >= Tq) {                           // a key at or beyond the length: dk = dv = +0, nothing is read
+            if (a.dk != nullptr) {
+                double* __restrict__ dk = at<double>(a.dk, a.sdk, b, h) + kj * a.sdk.sr;
+                if (lane < a.D) dk[lane] = 0.0;
+                if (lane + 64 < a.D) dk[lane + 64] = 0.0;
+            }
+            if (a.dv != nullptr) {
+                double* __restrict__ dv = at<double>(a.dv, a.sdv, b, h) + kj * a.sdv.sr;
+                if (lane < a.Dv) dv[lane] = 0.0;
+                if (lane + 64 < a.Dv) dv[lane + 64] = 0.0;
+            }
+            return;
+        }
+    }
     const double* __restrict__ k = at<double>(a.k, a.sk, b, h) + kj * a.sk.sr;
     const double* __restrict__ v = at<double>(a.v, a.sv, b, h) + kj * a.sv.sr;
     const int64_t row0 = GROUPED ? b * a.H + h * group : bh;        // the first query head of this key / value head
@@ -503,14 +607,14 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_f64(AttnArgs a) {
         const double* __restrict__ G = G0 + x * a.sdo.sh;
         const double* __restrict__ LSE = LSE0 + x * a.Tq;
         const double* __restrict__ DEL = DEL0 + x * a.Tq;
-        for (int64_t i0 = a.causal ? (kj / 64) * 64 : 0; i0 < a.Tq; i0 += 64) {
+        for (int64_t i0 = a.causal ? (kj / 64) * 64 : 0; i0 < Tq; i0 += 64) {
             const int64_t qi = i0 + lane;
             double p = 0.0, ds = 0.0;
-            if (qi < a.Tq && !(a.causal && kj > qi)) {
+            if (qi < Tq && !(a.causal && kj > qi)) {
                 p = exp(a.scale * dot64(Q + qi * a.sq.sr, k, a.D) - LSE[qi]);
                 ds = p * (dot64(G + qi * a.sdo.sr, v, a.Dv) - DEL[qi]);
             }
-            const int cnt = (int)((a.Tq - i0) < 64 ? (a.Tq - i0) : 64);
+            const int cnt = (int)((Tq - i0) < 64 ? (Tq - i0) : 64);
             for (int ii = 0; ii < cnt; ++ii) {
                 const double pi = __shfl(p, ii, 64), di = __shfl(ds, ii, 64);
                 const double* __restrict__ grow = G + (i0 + ii) * a.sdo.sr;
@@ -535,8 +639,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_f64(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// One validation and one launch path per entry point for both ABIs.  GROUPED = false: `who` is a tnn_attn_* name, group is 1
-// and the launch is the one that existed before.  GROUPED = true (tnn_gqa_*): H query heads over H / group key / value heads.
+// One validation and one launch path per entry point for the three ABIs.  GROUPED = false: `who` is a tnn_attn_* name, group
+// is 1 and the launch is the one that existed before.  GROUPED = true (tnn_gqa_*): H query heads over H / group key / value
+// heads.  LENS = true (tnn_varlen_*, csrc/tnn_varlen.hip): `lens` is the device array of the per-sequence lengths.
 inline Opnd operand(const void* base, const int64_t* s, int dtype) {
     Opnd o;
     o.sb = s[0]; o.sh = s[1]; o.sr = s[2];
@@ -566,17 +671,17 @@ inline int head_tiles(int64_t D, int64_t Dv) {
 #define ATTN_LAUNCH(KERNEL, grid)                                                                            \
     do {                                                                                                     \
         switch (head_tiles(D, Dv)) {                                                                         \
-            case 1: hipLaunchKernelGGL((KERNEL<1, GROUPED>), dim3(grid), dim3(256), 0, s, g); break;         \
-            case 2: hipLaunchKernelGGL((KERNEL<2, GROUPED>), dim3(grid), dim3(256), 0, s, g); break;         \
-            case 4: hipLaunchKernelGGL((KERNEL<4, GROUPED>), dim3(grid), dim3(256), 0, s, g); break;         \
-            default: hipLaunchKernelGGL((KERNEL<8, GROUPED>), dim3(grid), dim3(256), 0, s, g); break;        \
+            case 1: hipLaunchKernelGGL((KERNEL<1, GROUPED, LENS>), dim3(grid), dim3(256), 0, s, g); break;   \
+            case 2: hipLaunchKernelGGL((KERNEL<2, GROUPED, LENS>), dim3(grid), dim3(256), 0, s, g); break;   \
+            case 4: hipLaunchKernelGGL((KERNEL<4, GROUPED, LENS>), dim3(grid), dim3(256), 0, s, g); break;   \
+            default: hipLaunchKernelGGL((KERNEL<8, GROUPED, LENS>), dim3(grid), dim3(256), 0, s, g); break;  \
         }                                                                                                    \
     } while (0)
 
-template <bool GROUPED>
+template <bool GROUPED, bool LENS = false>
 int launch_fwd(const char* who, const void* q, const void* k, const void* v, void* o, void* lse, int64_t B, int64_t H,
                int64_t group, int64_t Tq, int64_t Tk, int64_t D, int64_t Dv, const int64_t* strides, double scale, int causal,
-               int dtype) {
+               int dtype, const void* lens = nullptr) {
     if (int rc = check_geometry(who, B, H, Tq, Tk, D, Dv, strides, 12, dtype)) return rc;
     if (B == 0 || H == 0 || Tq == 0) return 0;
     TNN_REQUIRE(q && k && v && o && lse, "%s: null operand", who);
@@ -585,10 +690,10 @@ int launch_fwd(const char* who, const void* q, const void* k, const void* v, voi
     g.B = B; g.H = H; g.Tq = Tq; g.Tk = Tk; g.D = D; g.Dv = Dv;
     g.sq = operand(q, strides, dtype); g.sk = operand(k, strides + 3, dtype);
     g.sv = operand(v, strides + 6, dtype); g.so = operand(o, strides + 9, dtype);
-    g.scale = scale; g.causal = causal; g.group = (int)group;
+    g.scale = scale; g.causal = causal; g.group = (int)group; g.lens = static_cast<const int64_t*>(lens);
     hipStream_t s = tnn::stream();
     if (dtype == TNN_F64) {
-        hipLaunchKernelGGL(attn_fwd_f64<GROUPED>, dim3((unsigned)((B * H * Tq + 3) / 4)), dim3(256), 0, s, g);
+        hipLaunchKernelGGL((attn_fwd_f64<GROUPED, LENS>), dim3((unsigned)((B * H * Tq + 3) / 4)), dim3(256), 0, s, g);
     } else {
         const int64_t grid = B * H * ((Tq + BQ - 1) / BQ);
         ATTN_LAUNCH(attn_fwd_f32, (unsigned)grid);
@@ -597,10 +702,10 @@ int launch_fwd(const char* who, const void* q, const void* k, const void* v, voi
     return 0;
 }
 
-template <bool GROUPED>
+template <bool GROUPED, bool LENS = false>
 int launch_bwd_q(const char* who, const void* q, const void* k, const void* v, const void* o, const void* d_o, const void* lse,
                  void* dq, void* delta, int64_t B, int64_t H, int64_t group, int64_t Tq, int64_t Tk, int64_t D, int64_t Dv,
-                 const int64_t* strides, double scale, int causal, int dtype) {
+                 const int64_t* strides, double scale, int causal, int dtype, const void* lens = nullptr) {
     if (int rc = check_geometry(who, B, H, Tq, Tk, D, Dv, strides, dq ? 18 : 15, dtype)) return rc;
     if (B == 0 || H == 0 || Tq == 0) return 0;
     TNN_REQUIRE(q && k && v && o && d_o && lse && delta, "%s: null operand", who);
@@ -611,10 +716,10 @@ int launch_bwd_q(const char* who, const void* q, const void* k, const void* v, c
     g.sv = operand(v, strides + 6, dtype); g.so = operand(o, strides + 9, dtype);
     g.sdo = operand(d_o, strides + 12, dtype);
     if (dq) g.sdq = operand(dq, strides + 15, dtype);
-    g.scale = scale; g.causal = causal; g.group = (int)group;
+    g.scale = scale; g.causal = causal; g.group = (int)group; g.lens = static_cast<const int64_t*>(lens);
     hipStream_t s = tnn::stream();
     if (dtype == TNN_F64) {
-        hipLaunchKernelGGL(attn_bwd_q_f64<GROUPED>, dim3((unsigned)((B * H * Tq + 3) / 4)), dim3(256), 0, s, g);
+        hipLaunchKernelGGL((attn_bwd_q_f64<GROUPED, LENS>), dim3((unsigned)((B * H * Tq + 3) / 4)), dim3(256), 0, s, g);
     } else {
         const int64_t grid = B * H * ((Tq + BQ - 1) / BQ);
         ATTN_LAUNCH(attn_bwd_q_f32, (unsigned)grid);
@@ -624,10 +729,10 @@ int launch_bwd_q(const char* who, const void* q, const void* k, const void* v, c
 }
 
 // (the grid runs over the H / group key / value heads: one workgroup owns one (b, key / value head, key block))
-template <bool GROUPED>
+template <bool GROUPED, bool LENS = false>
 int launch_bwd_kv(const char* who, const void* q, const void* k, const void* v, const void* d_o, const void* lse,
                   const void* delta, void* dk, void* dv, int64_t B, int64_t H, int64_t group, int64_t Tq, int64_t Tk, int64_t D,
-                  int64_t Dv, const int64_t* strides, double scale, int causal, int dtype) {
+                  int64_t Dv, const int64_t* strides, double scale, int causal, int dtype, const void* lens = nullptr) {
     if (int rc = check_geometry(who, B, H, Tq, Tk, D, Dv, strides, 18, dtype)) return rc;
     if (B == 0 || H == 0 || (dk == nullptr && dv == nullptr)) return 0;
     TNN_REQUIRE(k && v, "%s: null operand", who);
@@ -638,11 +743,11 @@ int launch_bwd_kv(const char* who, const void* q, const void* k, const void* v, 
     g.sq = operand(q, strides, dtype); g.sk = operand(k, strides + 3, dtype);
     g.sv = operand(v, strides + 6, dtype); g.sdo = operand(d_o, strides + 9, dtype);
     g.sdk = operand(dk, strides + 12, dtype); g.sdv = operand(dv, strides + 15, dtype);
-    g.scale = scale; g.causal = causal; g.group = (int)group;
+    g.scale = scale; g.causal = causal; g.group = (int)group; g.lens = static_cast<const int64_t*>(lens);
     const int64_t HK = H / group;
     hipStream_t s = tnn::stream();
     if (dtype == TNN_F64) {
-        hipLaunchKernelGGL(attn_bwd_kv_f64<GROUPED>, dim3((unsigned)((B * HK * Tk + 3) / 4)), dim3(256), 0, s, g);
+        hipLaunchKernelGGL((attn_bwd_kv_f64<GROUPED, LENS>), dim3((unsigned)((B * HK * Tk + 3) / 4)), dim3(256), 0, s, g);
     } else {
         const int64_t grid = B * HK * ((Tk + BKV - 1) / BKV);
         ATTN_LAUNCH(attn_bwd_kv_f32, (unsigned)grid);

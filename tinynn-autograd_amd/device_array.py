@@ -40,6 +40,7 @@ from . import norm as _nm
 from . import ragged as _rg
 from . import rope as _rp
 from . import tokens as _tk
+from . import varlen as _vl
 from ._lib import F32, F64, I64, U8
 
 _CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int64): I64,
@@ -1449,34 +1450,92 @@ def _attn_scores(q, k, plan):
 _AttnForm = collections.namedtuple("_AttnForm", "plan fwd bwd_q bwd_kv what fold")
 _PLAIN = _AttnForm(_attn_plan, "attn_fwd", "attn_bwd_q", "attn_bwd_kv", "attention", False)
 
+VARLEN_ROUTE = None   # tests / probes: "native" or "composed" overrides the planner's choice when lens= is given (varlen.py)
 
-def _attn_fwd(form, q, k, v, causal, scale, layout, route):
-    """attention / gqa_attention.  Native: ONE call of the form's forward entry point.  Composed: k and v repeated over the
-    plan's group (1 for the plain form: nothing is repeated), two batched products, max-subtract, exp, sum, divide."""
+
+class _Varlen(object):
+    """What lens= adds to one call of _attn_fwd / _attn_bwd_q / _attn_bwd_kv: the plan of varlen.py, the device array of the
+    lengths, and on the composed route the two masks built from their host values."""
+    __slots__ = ("plan", "dev", "lens")
+
+    def __init__(self, form, q, k, v, lens, causal, scale, layout, route):
+        what = form.what
+        if not isinstance(lens, (_rg.Lengths, DeviceArray)):
+            raise TypeError("%s: lens must be a ragged.Lengths or a dense int64 device array [B], got %s (a host sequence is "
+                            "refused: upload it once with device_array.lengths)" % (what, type(lens).__name__))
+        self.lens = lens
+        self.dev = _ragged_state(lens, what, "lens")
+        self.plan = _vl.plan_varlen(q.shape, k.shape, v.shape, self.dev.shape, causal, scale, layout, grouped=form.fold,
+                                    native=_lib.get().has_varlen, route=route or VARLEN_ROUTE)
+        if isinstance(lens, _rg.Lengths):
+            _vl.check_lens(lens.host, self.plan.T, what)
+
+    def native(self, entry, *args):
+        """ONE call of a tnn_varlen_* entry point: the arguments of its tnn_attn_* counterpart, then lens and the group."""
+        getattr(_lib.get(), entry)(*(args + (self.dev._ptr, self.plan.group)))
+
+    def masks(self, dt):
+        """(key mask [B H, T, T], row mask [B H, T, 1]) of the composed route, from the host values of the lengths."""
+        what = self.plan.grouped and "gqa_attention" or "attention"
+        if _lib.capturing:
+            raise RuntimeError("%s (composed route): the masks of lens= are built on the host and uploaded, which a graph "
+                               "capture cannot do; the native route reads the lengths on the device" % what)
+        host = _vl.check_lens(_ragged_mirror(self.lens, what), self.plan.T, what)
+        plan = self.plan
+        return (asarray(_vl.key_mask(host, plan.T, plan.H, dt), dtype=dt), asarray(_vl.row_mask(host, plan.T, plan.H, dt), dtype=dt))
+
+
+def _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens):
+    """(plan, varlen state or None) of one call."""
+    if lens is None:
+        return form.plan(q, k, v, causal, scale, layout, route), None
+    vl = _Varlen(form, q, k, v, lens, causal, scale, layout, route)
+    return vl.plan, vl
+
+
+def _zeroed(x3, rows):
+    """x3 with its dead rows set to +0 (x * 0 may be -0; -0 + 0 is +0)."""
+    return x3 * rows + 0.0
+
+
+def _attn_fwd(form, q, k, v, causal, scale, layout, route, lens=None):
+    """attention / gqa_attention.  Native: ONE call of the form's forward entry point (with lens=: of tnn_varlen_fwd).
+    Composed: k and v repeated over the plan's group (1 for the plain form: nothing is repeated), two batched products,
+    max-subtract, exp, sum, divide; with lens= the key mask joins the scores and the row mask zeroes the dead rows."""
     dt, (q, k, v) = _operands(q, k, v)
-    plan = form.plan(q, k, v, causal, scale, layout, route)
+    plan, vl = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens)
     if plan.empty():
         return zeros(plan.out_shape, dt), zeros(plan.lse_shape, dt)
     if plan.route == "native":
         out = DeviceArray._new(plan.out_shape, dt)
         lse = DeviceArray._new(plan.lse_shape, dt)
-        getattr(_lib.get(), form.fwd)(q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr, *plan.geometry(),
-                                      _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
+        args = (q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr) + tuple(plan.geometry()) + (
+            _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
+        if vl is None:
+            getattr(_lib.get(), form.fwd)(*args)
+        else:
+            vl.native("varlen_fwd", *args)
         return out, lse
     k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     s = _attn_scores(q, k, plan)
+    if vl is not None:
+        keys, rows = vl.masks(s.dtype)
+        s = s + keys
     m = s.max(axis=-1, keepdims=True)
     e = exp(s - m)
     l = e.sum(axis=-1, keepdims=True)
     o3 = matmul(e / l, _attn3(v, plan, plan.Tk, plan.Dv))
-    return _attn_from3(o3, plan, plan.Tq, plan.Dv), (m + log(l)).reshape(plan.lse_shape)
+    lse = m + log(l)
+    if vl is not None:
+        o3, lse = _zeroed(o3, rows), _zeroed(lse, rows)
+    return _attn_from3(o3, plan, plan.Tq, plan.Dv), lse.reshape(plan.lse_shape)
 
 
-def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out):
+def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out, lens=None):
     """attention_bwd_q / gqa_attention_bwd_q.  Native: ONE call of the form's backward-q entry point; dq_out is used when it
     has exactly q's shape.  Composed: as _attn_fwd, on the repeated k and v."""
     dt, (q, k, v, o, do, lse) = _operands(q, k, v, o, do, lse)
-    plan = form.plan(q, k, v, causal, scale, layout, route)
+    plan, vl = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens)
     if tuple(o.shape) != plan.out_shape or tuple(lse.shape) != plan.lse_shape:
         raise ValueError("%s_bwd_q: do / o %s and lse %s do not match the output %s and row statistics %s of this attention"
                          % (form.what, tuple(o.shape), tuple(lse.shape), plan.out_shape, plan.lse_shape))
@@ -1487,27 +1546,39 @@ def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq
     if plan.route == "native":
         dq = _dest(need_dq, dq_out, q.shape, dt, exact=True)
         delta = DeviceArray._new(plan.lse_shape, dt)
-        getattr(_lib.get(), form.bwd_q)(q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, _ptr_of(dq), delta._ptr,
-                                        *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale,
-                                        int(plan.causal), delta._code())
+        args = (q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, _ptr_of(dq), delta._ptr) + tuple(plan.geometry()) + (
+            _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale, int(plan.causal), delta._code())
+        if vl is None:
+            getattr(_lib.get(), form.bwd_q)(*args)
+        else:
+            vl.native("varlen_bwd_q", *args)
         return dq, delta
     k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     do3 = _attn3(do, plan, plan.Tq, plan.Dv)
     delta3 = (do3 * _attn3(o, plan, plan.Tq, plan.Dv)).sum(axis=-1, keepdims=True)
+    if vl is not None:
+        keys, rows = vl.masks(delta3.dtype)
+        delta3 = _zeroed(delta3, rows)
     dq = None
     if need_dq:
-        p = exp(_attn_scores(q, k, plan) - lse.reshape(plan.B * plan.H, plan.Tq, 1))
+        s = _attn_scores(q, k, plan)
+        if vl is not None:
+            s = s + keys
+        p = exp(s - lse.reshape(plan.B * plan.H, plan.Tq, 1))
         ds = p * (matmul(do3, _attn3(v, plan, plan.Tk, plan.Dv), swap_b=True) - delta3)
-        dq = _attn_from3(matmul(ds, _attn3(k, plan, plan.Tk, plan.D)) * plan.scale, plan, plan.Tq, plan.D)
+        dq3 = matmul(ds, _attn3(k, plan, plan.Tk, plan.D)) * plan.scale
+        if vl is not None:
+            dq3 = _zeroed(dq3, rows)
+        dq = _attn_from3(dq3, plan, plan.Tq, plan.D)
     return dq, delta3.reshape(plan.lse_shape)
 
 
-def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out):
+def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out, lens=None):
     """attention_bwd_kv / gqa_attention_bwd_kv.  Native: ONE call of the form's backward-kv entry point; dk_out / dv_out are
     used when they have exactly k's / v's shape.  Composed: as _attn_fwd, on the repeated k and v; the grouped form then sums
     dk and dv over the group axis (also for a group of one)."""
     dt, (q, k, v, do, lse, delta) = _operands(q, k, v, do, lse, delta)
-    plan = form.plan(q, k, v, causal, scale, layout, route)
+    plan, vl = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens)
     if tuple(lse.shape) != plan.lse_shape or tuple(delta.shape) != plan.lse_shape:
         raise ValueError("%s_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
                          % (form.what, tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
@@ -1519,46 +1590,63 @@ def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, ne
         return (zeros(k.shape, dt) if need_dk else None), (zeros(v.shape, dt) if need_dv else None)
     if plan.route == "native":
         dk, dv = _dest(need_dk, dk_out, k.shape, dt, exact=True), _dest(need_dv, dv_out, v.shape, dt, exact=True)
-        getattr(_lib.get(), form.bwd_kv)(q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, _ptr_of(dk), _ptr_of(dv),
-                                         *plan.geometry(), _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale,
-                                         int(plan.causal), lse._code())
+        args = (q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, _ptr_of(dk), _ptr_of(dv)) + tuple(plan.geometry()) + (
+            _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale, int(plan.causal), lse._code())
+        if vl is None:
+            getattr(_lib.get(), form.bwd_kv)(*args)
+        else:
+            vl.native("varlen_bwd_kv", *args)
         return dk, dv
     k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     rows = plan.B * plan.H
     do3 = _attn3(do, plan, plan.Tq, plan.Dv)
-    p = exp(_attn_scores(q, k, plan) - lse.reshape(rows, plan.Tq, 1))
+    s = _attn_scores(q, k, plan)
+    if vl is not None:
+        keys, live = vl.masks(s.dtype)
+        s = s + keys
+    p = exp(s - lse.reshape(rows, plan.Tq, 1))
+    if vl is not None:
+        p = p * live                        # dead rows contribute to no key; dead keys of live rows have p = exp(-inf) = 0
     dk = dv = None
     if need_dv:
-        dv = _attn_from3(matmul(p, do3, swap_a=True), plan, plan.Tk, plan.Dv)
+        dv3 = matmul(p, do3, swap_a=True)
+        dv = _attn_from3(dv3 if vl is None else _zeroed(dv3, live), plan, plan.Tk, plan.Dv)
     if need_dk:
         ds = p * (matmul(do3, _attn3(v, plan, plan.Tk, plan.Dv), swap_b=True) - delta.reshape(rows, plan.Tq, 1))
-        dk = _attn_from3(matmul(ds, _attn3(q, plan, plan.Tq, plan.D), swap_a=True) * plan.scale, plan, plan.Tk, plan.D)
+        dk3 = matmul(ds, _attn3(q, plan, plan.Tq, plan.D), swap_a=True) * plan.scale
+        dk = _attn_from3(dk3 if vl is None else _zeroed(dk3, live), plan, plan.Tk, plan.D)
     if form.fold:
         fold = lambda g, w: g.reshape(plan.B, plan.Tk, plan.Hkv, plan.group, w).sum(axis=3)
         dk, dv = (None if dk is None else fold(dk, plan.D)), (None if dv is None else fold(dv, plan.Dv))
     return dk, dv
 
 
-def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None):
+def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None, lens=None):
     """(o, lse): o = softmax(scale q k^T) v over the key axis and the per-row log-sum-exp of the scaled scores (what the
     backward recomputes the probabilities from).  Layouts, the causal rule and the routes: attention.py.  Native: ONE
-    tnn_attn_fwd launch, the scores never reach memory; composed: two batched products, max-subtract, exp, sum, divide."""
-    return _attn_fwd(_PLAIN, q, k, v, causal, scale, layout, route)
+    tnn_attn_fwd launch, the scores never reach memory; composed: two batched products, max-subtract, exp, sum, divide.
+    lens= (a ragged.Lengths or a dense int64 device array [B]; Tq == Tk, layout "bthd" or three-axis "bhtd"): sequence b of a
+    right-padded batch has lens[b] live tokens — live rows attend over live keys only, dead rows get o = +0 and lse = 0
+    (varlen.py: the rule, the routes).  Native: ONE tnn_varlen_fwd launch that reads the lengths on the device."""
+    return _attn_fwd(_PLAIN, q, k, v, causal, scale, layout, route, lens)
 
 
-def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd", route=None, need_dq=True, dq_out=None):
+def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd", route=None, need_dq=True, dq_out=None,
+                    lens=None):
     """(dq, delta) for the gradient `do` of attention's output: delta[i] = sum_c do[i, c] o[i, c] (what attention_bwd_kv
     reads) and dq = scale dS k with dS = p (dP - delta), dP = do v^T, p recomputed from lse.  need_dq=False: dq is None and
-    only delta is produced (native: the key loop is skipped).  dq_out: a dense array the result is written into."""
-    return _attn_bwd_q(_PLAIN, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out)
+    only delta is produced (native: the key loop is skipped).  dq_out: a dense array the result is written into.  lens=: as
+    attention; dead rows get delta = 0 and dq = +0."""
+    return _attn_bwd_q(_PLAIN, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out, lens)
 
 
 def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="bhtd", route=None, need_dk=True,
-                     need_dv=True, dk_out=None, dv_out=None):
+                     need_dv=True, dk_out=None, dv_out=None, lens=None):
     """(dk, dv): dv = p^T do and dk = scale dS^T q from ONE launch, with the delta attention_bwd_q produced (on the native
     route the launch must follow that call).  need_dk / need_dv = False: that product is skipped and None returned.  A key
-    that no query sees (causal, Tk > Tq) gets exact zeros.  dk_out / dv_out: dense arrays the results are written into."""
-    return _attn_bwd_kv(_PLAIN, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out)
+    that no query sees (causal, Tk > Tq) gets exact zeros.  dk_out / dv_out: dense arrays the results are written into.
+    lens=: as attention; dead keys get dk = dv = +0."""
+    return _attn_bwd_kv(_PLAIN, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out, lens)
 
 
 # ---------------------------------------------------------------------- kernels: layer norm, RMS norm, GELU (csrc/tnn_norm.hip)
@@ -2254,27 +2342,27 @@ _GROUPED = _AttnForm(lambda q, k, v, causal, scale, layout, route: _gqa_plan(q, 
                      "gqa_fwd", "gqa_bwd_q", "gqa_bwd_kv", "gqa_attention", True)
 
 
-def gqa_attention(q, k, v, causal=False, scale=None, route=None):
+def gqa_attention(q, k, v, causal=False, scale=None, route=None, lens=None):
     """(o, lse) of grouped-query attention in layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] ->
     o [B, Tq, H, Dv], lse [B, H, Tq]; query head h reads key / value head h // (H / Hkv) (gqa.py: the checks, the routes).
     Native: ONE tnn_gqa_fwd launch, k and v are never expanded; composed: k and v repeated over the group, then attention()
-    on its composed route."""
-    return _attn_fwd(_GROUPED, q, k, v, causal, scale, "bthd", route)
+    on its composed route.  lens=: per-sequence lengths of a right-padded batch, as attention (ONE tnn_varlen_fwd launch)."""
+    return _attn_fwd(_GROUPED, q, k, v, causal, scale, "bthd", route, lens)
 
 
-def gqa_attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, route=None, need_dq=True, dq_out=None):
+def gqa_attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, route=None, need_dq=True, dq_out=None, lens=None):
     """(dq, delta) of gqa_attention, as attention_bwd_q: delta [B, H, Tq] is what gqa_attention_bwd_kv reads; need_dq=False:
-    only delta.  Native: ONE tnn_gqa_bwd_q launch."""
-    return _attn_bwd_q(_GROUPED, q, k, v, o, do, lse, causal, scale, "bthd", route, need_dq, dq_out)
+    only delta.  Native: ONE tnn_gqa_bwd_q launch (lens=: tnn_varlen_bwd_q)."""
+    return _attn_bwd_q(_GROUPED, q, k, v, o, do, lse, causal, scale, "bthd", route, need_dq, dq_out, lens)
 
 
 def gqa_attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, route=None, need_dk=True, need_dv=True,
-                         dk_out=None, dv_out=None):
+                         dk_out=None, dv_out=None, lens=None):
     """(dk, dv) of gqa_attention with the shapes of k and v: the sums over every key / value head's group of query heads.
     Native: ONE tnn_gqa_bwd_kv launch (it must follow gqa_attention_bwd_q on the stream: it reads that call's delta) — one
     workgroup per (b, key / value head, key block) adds the group's heads in ascending order and writes once.  Composed:
-    attention_bwd_kv on k and v repeated over the group, then a sum over the group axis."""
-    return _attn_bwd_kv(_GROUPED, q, k, v, do, lse, delta, causal, scale, "bthd", route, need_dk, need_dv, dk_out, dv_out)
+    attention_bwd_kv on k and v repeated over the group, then a sum over the group axis.  lens=: tnn_varlen_bwd_kv."""
+    return _attn_bwd_kv(_GROUPED, q, k, v, do, lse, delta, causal, scale, "bthd", route, need_dk, need_dv, dk_out, dv_out, lens)
 
 
 def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=None, scale=None, layout="bthd", route=None,

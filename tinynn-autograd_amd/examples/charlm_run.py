@@ -30,6 +30,12 @@ Embedding is built without max_len, so there is no "pos" table.  It composes wit
 geglu are the gated forms act(x Wg) * (x Wu) projected by W2, with Wg and Wu held as one fc1 [E, 2 hidden] and the product done
 by ONE ops.gated_ launch (csrc/tnn_gated.hip); hidden is then 8 E / 3 rounded up to a multiple of 8.
 
+--ragged-train: right-padded batches, the way real text arrives — every sequence of a batch is cut to a random length in
+[seq / 4, seq], the targets at and beyond it are set to the loss's ignore_index, and the lengths are uploaded once per batch
+and handed to the model (model.forward(x, lens=)): every attention launch reads them on the device (include/tnn_varlen.h),
+skips whole 64-row blocks of padding and never reads a padded row.  --no-lens keeps the lengths from the model: the padded
+baseline, right for this causal model and wasteful.  The live tokens per second of every epoch are printed.  Default off.
+
 --adamw: core/optimizer.AdamW instead of Adam — decoupled weight decay (--weight_decay, biases and norm parameters exempt),
 clipping by the global gradient norm (--clip MAX_NORM, 0 = none) and a linear warm-up over --warmup steps followed by a cosine
 decay to zero at the last step, all resident on the device (include/tnn_ostep.h).  Without --adamw the run and its launch
@@ -47,7 +53,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 
 import tinynn_autograd_amd as tn                                                            # noqa: E402
-from tinynn_autograd_amd import ostep, rng                                                  # noqa: E402
+from tinynn_autograd_amd import device_array as da, ostep, rng                              # noqa: E402
 from tinynn_autograd_amd.rope import Rotary                                                 # noqa: E402
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
 from tinynn_autograd_amd.generation import KVCache, generate                                # noqa: E402
@@ -76,6 +82,17 @@ def make_data(rs, count, seq, vocab, period):
     return np.ascontiguousarray(stream[:, :-1]), np.ascontiguousarray(stream[:, 1:])
 
 
+IGNORE = -1           # --ragged-train: the target of a position at or beyond its sequence's length
+
+
+def ragged_batch(rs, x, y, seq):
+    """--ragged-train: every sequence of the batch cut to a random length in [seq / 4, seq] — the ids stay (right padding: what
+    sits there is never read by the attention), the targets at dead positions become IGNORE.  -> (lens, targets)."""
+    lens = rs.randint(max(seq // 4, 1), seq + 1, len(x))
+    y = np.where(np.arange(seq)[None, :] < lens[:, None], y, IGNORE)
+    return lens, y
+
+
 def build(args):
     fused = not args.composed
     drop = args.dropout
@@ -87,7 +104,8 @@ def build(args):
                TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
                                 rope=rotary, mlp=mlp),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
-    loss_layer = CrossEntropyLoss(fused=fused)
+    # --ragged-train: the targets at dead positions carry this index and count for nothing
+    loss_layer = CrossEntropyLoss(ignore_index=IGNORE if getattr(args, "ragged_train", False) else None, fused=fused)
     return Model(net=net, loss=loss_layer, optimizer=make_optimizer(args)), loss_layer
 
 
@@ -111,17 +129,29 @@ def main(args):
     print("data: synthetic, %d sequences of %d tokens from %d, period %d; backend %s"
           % (len(train_x), args.seq, args.vocab, args.period, tn.backend_name()))
     history = []
+    ragged = getattr(args, "ragged_train", False)
     for epoch in range(args.num_ep):
         t0, losses = time.time(), []
+        live = 0
         for start in range(0, len(train_x) - args.batch_size + 1, args.batch_size):
             x = Tensor(train_x[start:start + args.batch_size])
-            y = train_y[start:start + args.batch_size].reshape(-1)
+            y = train_y[start:start + args.batch_size]
+            lens = None
+            if ragged:
+                host, y = ragged_batch(rs, train_x[start:start + args.batch_size], y, args.seq)
+                live += int(host.sum())
+                if not getattr(args, "no_lens", False):
+                    lens = da.lengths(host)                 # uploaded once per batch; every attention node reads it on the device
             model.zero_grad()
-            loss = loss_layer.loss(model.forward(x), y)
+            loss = loss_layer.loss(model.forward(x, lens=lens), y.reshape(-1))
             loss.backward()
             model.step()
             losses.append(loss)
         mean = float(np.mean([float(l.values) for l in losses]))
+        if ragged:
+            print("         ragged batches: %d live tokens of %d, %.0f live tokens/s%s" % (
+                live, len(losses) * args.batch_size * args.seq, live / (time.time() - t0),
+                " (lengths NOT handed to the model: causal attention over the padding)" if getattr(args, "no_lens", False) else ""))
         model.set_phase("TEST")
         logits = np.asarray(model.forward(Tensor(test_x)).values).reshape(len(test_x), args.seq, args.vocab)
         model.set_phase("TRAIN")
@@ -213,6 +243,11 @@ def parse(argv=None):
                         help="--generate: run the prompt in pieces of C tokens (the pieces after the first extend the cache)")
     parser.add_argument("--second-turn", dest="second_turn", default=0, type=int, metavar="M",
                         help="--generate: keep the cache and continue it by M more tokens in a second call")
+    parser.add_argument("--ragged-train", dest="ragged_train", action="store_true",
+                        help="train on right-padded batches: every sequence cut to a random length in [seq / 4, seq], the targets "
+                             "beyond it ignored by the loss, the lengths handed to the model (model.forward(x, lens=))")
+    parser.add_argument("--no-lens", dest="no_lens", action="store_true",
+                        help="--ragged-train: keep the lengths from the model (the padded baseline; right for a causal model, wasteful)")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
     parser.add_argument("--adamw", action="store_true", help="AdamW on the device instead of Adam")
     parser.add_argument("--weight_decay", default=0.01, type=float, help="--adamw: decoupled weight decay")
