@@ -66,6 +66,7 @@ from . import rng
 from . import gated
 from . import extend
 from . import varlen
+from . import kvq
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

@@ -91,6 +91,10 @@ from ._varlen_signatures import _VARLEN_SIGNATURES            # noqa: E402  (inc
 
 VARLEN_SYMBOLS = sorted(_VARLEN_SIGNATURES)
 
+from ._kvq_signatures import _KVQ_SIGNATURES                  # noqa: E402  (include/tnn_kvq.h: libtnn_hip.so only)
+
+KVQ_SYMBOLS = sorted(_KVQ_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -168,6 +172,8 @@ class _Lib(object):
         # runs the composed attention over the live prefix with the offset mask (extend.py)
         # and training attention with per-sequence lengths (include/tnn_varlen.h): under the twin device_array runs the
         # composed attention with a key mask and a row mask built from the lengths on the host (varlen.py)
+        # and the int8 key / value cache (include/tnn_kvq.h): under the twin device_array quantizes and dequantizes on the host
+        # with kvq.py's numpy statement of the format and runs the composed decode over the dequantized prefix
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -182,7 +188,8 @@ class _Lib(object):
                                     (_ROPE_SIGNATURES, "tnn_rope.h", "rotary position embedding"),
                                     (_GATED_SIGNATURES, "tnn_gated.h", "gated activation"),
                                     (_EXTEND_SIGNATURES, "tnn_extend.h", "cache-extending attention"),
-                                    (_VARLEN_SIGNATURES, "tnn_varlen.h", "attention with per-sequence lengths")):
+                                    (_VARLEN_SIGNATURES, "tnn_varlen.h", "attention with per-sequence lengths"),
+                                    (_KVQ_SIGNATURES, "tnn_kvq.h", "int8 key / value cache")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -207,6 +214,7 @@ class _Lib(object):
         self.has_gated = hasattr(self.cdll, "tnn_gated_fwd")
         self.has_extend = hasattr(self.cdll, "tnn_extend_attn")
         self.has_varlen = hasattr(self.cdll, "tnn_varlen_fwd")
+        self.has_kvq = hasattr(self.cdll, "tnn_kvq_decode_attn")
 
     @staticmethod
     def _absent(name, what):

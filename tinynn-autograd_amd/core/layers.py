@@ -270,7 +270,9 @@ class MultiHeadAttention(Layer):
         bound.  None: today's path, bit for bit.  With kv_heads the cache holds the key / value heads and the grouped ops run
         in the same places.  A cache made with extend=True also takes T > 1 when it is filled (chunked prefill, a continued
         sequence): q and k are rotated at offset cache.length and ONE ops.attention_extend_ attends over the cached rows and
-        the new ones and appends them; T == 1 keeps taking the decode ops."""
+        the new ones and appends them; T == 1 keeps taking the decode ops.  A cache made with quant="int8" holds uint8 codes and
+        float32 row scales: the prefill's k and v (k already rotated) are quantized by ONE launch and every step runs
+        ops.attention_decode_kvq_, for plain and grouped heads, uniform and ragged batches alike."""
         if len(inputs.shape) != 3:
             raise ValueError("MultiHeadAttention: the input must be [B, T, E], got shape %s" % (tuple(inputs.shape),))
         if lens is not None and cache is not None:
@@ -309,7 +311,11 @@ class MultiHeadAttention(Layer):
                 q, k = ops.rope_(ops.reshape(q, (b, 1, h, e // h)), ops.reshape(k, (b, 1, hk, e // h)), rotary=self.rope,
                                  route=route, **where)
                 q, k = ops.reshape(q, (b, h, e // h)), ops.reshape(k, (b, hk, e // h))
-            if getattr(cache, "lens", None) is not None:         # a ragged batch: the lengths are read on the device
+            if getattr(cache, "quant", None) is not None:        # an int8 cache: plain, grouped, uniform and ragged in ONE op
+                where = (dict(lens=cache.lens) if getattr(cache, "lens", None) is not None else dict(length=cache.length))
+                att = ops.attention_decode_kvq_(q, cache.k, cache.v, cache.k_scale, cache.v_scale, k_new=k, v_new=v,
+                                                layout="bthd", route=route, **where)
+            elif getattr(cache, "lens", None) is not None:       # a ragged batch: the lengths are read on the device
                 decode = ops.attention_decode_ragged_gqa_ if grouped else ops.attention_decode_ragged_
                 att = decode(q, cache.k, cache.v, cache.lens, k, v, layout="bthd", route=route)
             else:
@@ -326,7 +332,10 @@ class MultiHeadAttention(Layer):
             else:
                 att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route, lens=lens)
             if cache is not None:
-                cache.fill(k.values, v.values)
+                if getattr(cache, "quant", None) is not None:
+                    cache.fill(k.values, v.values, route=route)
+                else:
+                    cache.fill(k.values, v.values)
         out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
         return ops.reshape(out, (b, t, e))
 

@@ -1013,6 +1013,26 @@ def attention_decode_ragged_gqa_(q, k_cache, v_cache, lens, k_new, v_new, scale=
     return q.__class__(out, False, [])
 
 
+def attention_decode_kvq_(q, k_codes, v_codes, k_scales, v_scales, length=None, k_new=None, v_new=None, lens=None, scale=None,
+                          layout="bthd", route=None, splits=None, **unknown):
+    """One decoding step over an INT8 key / value cache, INFERENCE ONLY (kvq.py states the format): q [B, H, D] float32 over
+    uint8 codes ("bthd": [B, Tmax, Hkv, D | Dv]) with one float32 scale per cache row ([B, Tmax, Hkv]).  k_new [B, Hkv, D] and
+    v_new [B, Hkv, Dv] are quantized and written into cache row `length` (a host integer) or lens[b] (read ON THE DEVICE, as
+    attention_decode_ragged_) in place, and every query attends over the dequantized rows up to and including it; H / Hkv
+    query heads share a key / value head (1: plain multi-head attention).  ONE tnn_kvq_decode_attn call that reads a quarter
+    of the float32 cache's bytes; under the CPU test twin and with route="composed" (or device_array.KVQ_ROUTE) the host
+    quantizes and dequantizes and the composed decode runs.  The result is a LEAF tensor without a grad_fn.  Out of scope:
+    fp8 / int4 codes, float64, T > 1 new rows (chunked prefill) — unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_decode_kvq_: unsupported arguments %s (fp8 / int4 codes and chunked prefill over a quantized "
+                        "cache are out of scope)" % sorted(unknown))
+    out = da.attention_decode_kvq(q.values, _raw_values(k_codes), _raw_values(v_codes), _raw_values(k_scales),
+                                  _raw_values(v_scales), length, None if k_new is None else k_new.values,
+                                  None if v_new is None else v_new.values, None if lens is None else _raw_values(lens),
+                                  scale=scale, layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
 def attention_extend_(q, k_cache, v_cache, length, k_new, v_new, scale=None, layout="bthd", route=None, **unknown):
     """Attention of T NEW rows per sequence over a key / value cache and over themselves, with the append, INFERENCE ONLY —
     chunked prefill, the continuation of a cached sequence, the verification of drafted tokens.  layout "bthd": q [B, T, H, D],

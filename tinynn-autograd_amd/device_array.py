@@ -36,6 +36,7 @@ from . import extend as _ex
 from . import gated as _gt
 from . import gqa as _gq
 from . import indexing as _ix
+from . import kvq as _kq
 from . import norm as _nm
 from . import ragged as _rg
 from . import rope as _rp
@@ -45,7 +46,8 @@ from ._lib import F32, F64, I64, U8
 
 _CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int64): I64,
          np.dtype(np.bool_): U8,
-         np.dtype(np.uint16): _lib.BF16}     # raw bf16 bit patterns: storage only (tinynn_autograd_amd.bf16)
+         np.dtype(np.uint16): _lib.BF16,     # raw bf16 bit patterns: storage only (tinynn_autograd_amd.bf16)
+         np.dtype(np.uint8): U8}             # raw int8 codes of a quantized key / value cache: storage only (kvq.py)
 _default_float = np.dtype(np.float32)
 READONLY_COPY = "readonly-copy"      # DeviceArray._tag of a snapshot that must not be mistaken for a view (fused.MLPTrainer.param_view)
 MAX_NDIM = 6
@@ -2399,6 +2401,121 @@ def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=No
     if ragged:
         return _decode_composed_ragged(what, gqa_decode, plan, dt, lens, q, k_cache, v_cache, k_new, v_new)
     return _decode_composed(plan, q, k_cache, v_cache, k_new, v_new)
+
+
+# ---------------------------------------------------------------------- kernels: the int8 key / value cache (csrc/tnn_kvq.hip)
+KVQ_ROUTE = None      # tests / probes: "native" or "composed" overrides the planner's choice (kvq.py)
+
+
+def _kvq_caches(what, k_codes, v_codes, k_scales, v_scales):
+    """The four cache operands are written IN PLACE: dense device arrays, uint8 codes and float32 scales."""
+    for a, n, dt in ((k_codes, "k_codes", np.uint8), (v_codes, "v_codes", np.uint8), (k_scales, "k_scales", np.float32),
+                     (v_scales, "v_scales", np.float32)):
+        if not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != np.dtype(dt):
+            raise TypeError("%s: %s must be a dense device array of dtype %s (it is written in place)" % (what, n, np.dtype(dt)))
+
+
+def _kvq_aligned(*arrays):
+    return all(a is None or a._ptr % 16 == 0 for a in arrays)
+
+
+def _kvq_eager(what):
+    if _lib.capturing:
+        raise RuntimeError("%s (composed route) quantizes and dequantizes on the host, which a graph capture cannot do" % what)
+
+
+def _kvq_rows(layout, first, stop):
+    """The index of cache rows [first, stop) in either layout, for the code and the scale arrays alike."""
+    return (slice(None),) * _DECODE_AXES[layout][0] + (slice(first, stop),)
+
+
+def _kvq_host_put(layout, codes, scales, first, x):
+    """Composed: x float32 [B, T, Hkv, W] on the host -> codes and scales at cache rows [first, first + T)."""
+    c, s = _kq.quantize_host(x)
+    if layout == "bhtd":
+        c, s = c.transpose(0, 2, 1, 3), s.transpose(0, 2, 1)
+    rows = _kvq_rows(layout, first, first + x.shape[1])
+    codes[rows] = asarray(np.ascontiguousarray(c), dtype=np.uint8)
+    scales[rows] = asarray(np.ascontiguousarray(s), dtype=np.float32)
+
+
+def kvq_quantize_rows(k, v, k_codes, v_codes, k_scales, v_scales, row0=0, layout="bthd", route=None):
+    """The prefill's fill of an int8 cache, IN PLACE: k [B, T, Hkv, D] and v [B, T, Hkv, Dv] (float32) become codes and
+    scales at cache rows [row0, row0 + T) (kvq.py states the format, the layouts and the routes).  Native: ONE
+    tnn_kvq_quantize_rows launch for both tensors.  Composed: k and v are read back, quantized by kvq.quantize_host and
+    slice-assigned, which a graph capture cannot do."""
+    what = "kvq_quantize_rows"
+    _kvq_caches(what, k_codes, v_codes, k_scales, v_scales)
+    k, v = asarray(k)._contig(), asarray(v)._contig()
+    float_ok = k.dtype == v.dtype == np.dtype(np.float32)
+    lib = _lib.get()
+    plan = _kq.plan_kvq_fill(k.shape, v.shape, k_codes.shape, v_codes.shape, k_scales.shape, v_scales.shape, row0, layout,
+                             native=lib.has_kvq, float_ok=float_ok, aligned=_kvq_aligned(k, v, k_codes, v_codes),
+                             route=route or KVQ_ROUTE)
+    if plan.empty():
+        return
+    if plan.route == "native":
+        lib.kvq_quantize_rows(k._ptr, v._ptr, k_codes._ptr, v_codes._ptr, k_scales._ptr, v_scales._ptr, *plan.geometry(),
+                              _i64arr(plan.strides()), _CODE[k.dtype])
+        return
+    _kvq_eager(what)
+    _kvq_host_put(layout, k_codes, k_scales, plan.row0, np.asarray(k, dtype=np.float32))
+    _kvq_host_put(layout, v_codes, v_scales, plan.row0, np.asarray(v, dtype=np.float32))
+
+
+def attention_decode_kvq(q, k_codes, v_codes, k_scales, v_scales, length=None, k_new=None, v_new=None, lens=None, scale=None,
+                         layout="bthd", route=None, splits=None):
+    """o [B, H, Dv] float32: one decoding step over an INT8 cache (kvq.py).  q [B, H, D]; k_new [B, Hkv, D] and v_new
+    [B, Hkv, Dv] are quantized, written into cache row `length` (a host integer) or lens[b] (a ragged.Lengths or a dense
+    int64 device array, read on the device) IN PLACE, and the queries of head h attend over the DEQUANTIZED rows of key /
+    value head h // (H / Hkv) up to and including that row.  Native: ONE tnn_kvq_decode_attn call (a second small launch
+    inside it when the keys are split); with lens= its arguments are fixed by the shapes, so it can be captured, and a length
+    outside [0, Tmax) gives zeros and leaves the caches untouched.  Composed: the row is quantized on the host, the live
+    prefix dequantized there, and gqa_decode's composed route runs over it — host reads that a graph capture cannot do."""
+    what = "attention_decode_kvq"
+    _kvq_caches(what, k_codes, v_codes, k_scales, v_scales)
+    if k_new is None or v_new is None:
+        raise ValueError("%s: k_new and v_new are required (the step quantizes and appends its row)" % what)
+    if (length is None) == (lens is None):
+        raise ValueError("%s: give length= (a host integer shared by the batch) or lens= (one per sequence), not both" % what)
+    q, k_new, v_new = (asarray(a)._contig() for a in (q, k_new, v_new))
+    float_ok = all(a.dtype == np.dtype(np.float32) for a in (q, k_new, v_new))
+    if not float_ok and any(a.dtype.kind != "f" for a in (q, k_new, v_new)):
+        raise TypeError("%s: q, k_new and v_new must be floating-point" % what)
+    ld = None if lens is None else _ragged_state(lens, what, "lens")
+    lib = _lib.get()
+    plan = _kq.plan_kvq_decode(q.shape, k_codes.shape, v_codes.shape, k_scales.shape, v_scales.shape, length, k_new.shape,
+                               v_new.shape, scale, layout, splits, None if ld is None else ld.shape, native=lib.has_kvq,
+                               float_ok=float_ok, aligned=_kvq_aligned(q, k_new, v_new, k_codes, v_codes),
+                               route=route or KVQ_ROUTE)
+    dt = np.dtype(np.float32)
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        nbytes = plan.workspace_bytes()
+        ws = DeviceArray._new((nbytes // 4,), dt) if nbytes else None
+        lib.kvq_decode_attn(q._ptr, k_new._ptr, v_new._ptr, k_codes._ptr, v_codes._ptr, k_scales._ptr, v_scales._ptr, out._ptr,
+                            _ptr_of(ws), nbytes, _ptr_of(ld), *plan.geometry(), _i64arr(plan.strides()), plan.scale, plan.splits,
+                            _CODE[dt])
+        return out
+    _kvq_eager(what)
+    if plan.ragged:                                            # a loop over the sequences with the host lengths
+        host = _ragged_mirror(lens, what)
+        out = zeros(plan.out_shape, dt)
+        for b in range(plan.B):
+            if 0 <= int(host[b]) < plan.Tmax:                  # (else zeros, the caches untouched)
+                one = slice(b, b + 1)
+                out[one] = attention_decode_kvq(q[one], k_codes[one], v_codes[one], k_scales[one], v_scales[one], int(host[b]),
+                                                k_new[one], v_new[one], scale=plan.scale, layout=layout, route="composed")
+        return out
+    n = plan.length + 1
+    for codes, scales, new in ((k_codes, k_scales, k_new), (v_codes, v_scales, v_new)):
+        _kvq_host_put(layout, codes, scales, plan.length, np.asarray(new, dtype=np.float32)[:, None])
+    live = _kvq_rows(layout, 0, n)
+    kf, vf = (asarray(_kq.dequantize_host(np.asarray(c[live]), np.asarray(s[live]), np.float32), dtype=dt)
+              for c, s in ((k_codes, k_scales), (v_codes, v_scales)))
+    return gqa_decode(q.astype(dt), kf, vf, n, scale=plan.scale, layout=layout, route="composed")
 
 
 # ---------------------------------------------------------------------- kernels: cache-extending attention (csrc/tnn_extend.hip)

@@ -173,6 +173,9 @@ def main(args):
         raise ValueError("--generate %d: %d prompt + %d new tokens exceed --seq %d (the learned positions, or the rotary tables)"
                          % (args.generate, prompt_len, total, args.seq))
     rows = test_x[:min(len(test_x), 8)]
+    quant = getattr(args, "kv_quant", None)                 # --kv-quant int8: uint8 codes and float32 row scales (kvq.py)
+    if quant is not None and (chunk is not None or second > 0):
+        raise ValueError("--kv-quant excludes --prefill-chunk and --second-turn (chunked prefill over a quantized cache is out of scope)")
     if args.ragged or args.eos is not None or args.capture:
         if chunk is not None or second > 0:
             raise ValueError("--prefill-chunk and --second-turn belong to the uniform path: no --ragged, --eos or --capture")
@@ -180,7 +183,8 @@ def main(args):
         if args.ragged:                                     # prompts of period .. 2 period tokens, the same in every run
             lens = args.period + np.arange(len(rows)) % (args.period + 1)
         out, ends = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, prompt_lens=lens, eos_id=args.eos,
-                             capture=args.capture, return_lengths=True)
+                             capture=args.capture, return_lengths=True,
+                             cache=KVCache(args.seq, quant=quant) if quant is not None else True)
         new = np.stack([out[b, p:p + args.generate] for b, p in enumerate(lens)])
         motif = np.stack([rows[b, np.arange(p, p + args.generate) % args.period] for b, p in enumerate(lens)])
         live = np.arange(args.generate)[None, :] < (ends - lens)[:, None]          # up to and including an end of sequence
@@ -192,6 +196,8 @@ def main(args):
         args.generation = (out, share)
         return history
     kept = KVCache(args.seq, extend=True) if second > 0 else True       # the first turn's cache, kept for the second
+    if quant is not None:
+        kept = KVCache(args.seq, quant=quant)
     out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, cache=kept, prefill_chunk=chunk)
     motif = rows[:, np.arange(prompt_len, prompt_len + args.generate) % args.period]     # what repeating the motif gives
     share = float((out[:, prompt_len:] == motif).mean())
@@ -239,6 +245,8 @@ def parse(argv=None):
     parser.add_argument("--ragged", action="store_true", help="--generate: prompts of differing lengths (period .. 2 period tokens)")
     parser.add_argument("--eos", default=None, type=int, metavar="ID", help="--generate: a sequence ends at token ID")
     parser.add_argument("--capture", action="store_true", help="--generate: record the token step into a graph and replay it")
+    parser.add_argument("--kv-quant", dest="kv_quant", default=None, choices=("int8",),
+                        help="--generate: keep the key / value cache as int8 codes with one float32 scale per row")
     parser.add_argument("--prefill-chunk", dest="prefill_chunk", default=None, type=int, metavar="C",
                         help="--generate: run the prompt in pieces of C tokens (the pieces after the first extend the cache)")
     parser.add_argument("--second-turn", dest="second_turn", default=0, type=int, metavar="M",

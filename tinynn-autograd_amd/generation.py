@@ -33,6 +33,12 @@ prompt as ceil(P / C) pieces — the first through the ordinary prefill, the res
 generate(cache=a KVCache(extend=True)) continues the sequence an earlier call left in that cache.  The default cache
 refuses T > 1 on a filled cache as before.
 
+An int8 cache (include/tnn_kvq.h).  KVCache(max_len, quant="int8") keeps uint8 codes and one float32 scale per cache row
+instead of float32 rows — 3.88x fewer bytes at head dimension 128.  fill() quantizes the prefill's k and v with ONE launch,
+every step runs ops.attention_decode_kvq_, which quantizes and appends the step's own row; it serves plain and grouped
+heads, uniform and ragged batches, rope, and the captured step.  generate(cache=KVCache(P + N, quant="int8")) uses it for
+ONE call (it must be empty); extend=True together with quant raises.  quant=None is the float path, bit for bit.
+
 Out of scope: ragged chunks (lengths read on the device with T > 1), top-p, bf16, and skipping the work
 of sequences that have ended (they go on emitting the pad token; `stop_every` ends the loop once ALL have ended).
 """
@@ -43,6 +49,7 @@ import numpy as np
 
 from . import _lib
 from . import device_array as da
+from . import kvq
 from . import ragged as rg
 from .core import ops
 from .core.tensor import Tensor
@@ -52,8 +59,10 @@ class LayerCache(object):
     """The keys and values of ONE attention layer: k [B, max_len, H, D], v [B, max_len, H, D] (layout "bthd": what a
     [B T, H D] projection reshapes to), allocated from the first batch, and the number of live rows."""
 
-    def __init__(self, max_len, lens=None, extend=False):
+    def __init__(self, max_len, lens=None, extend=False, quant=None):
         self.max_len, self.length, self.k, self.v = int(max_len), 0, None, None
+        self.quant = _check_quant(quant, extend)     # "int8": k and v hold uint8 codes, k_scale / v_scale [B, max_len, H] the
+        self.k_scale = self.v_scale = None           # float32 scale of every row (kvq.py); None: float rows
         self.extend = bool(extend)     # a filled cache also takes T > 1 new rows (ops.attention_extend_); False: ONE per step
         self.lens = lens     # a ragged.Lengths: every sequence's own live rows, read on the device; `length` is then the
                              # host's upper bound (what check() uses)
@@ -78,9 +87,16 @@ class LayerCache(object):
             raise ValueError("KVCache: the cache was allocated for [B, H, D] = %s, got %s"
                              % ((self.k.shape[0],) + tuple(self.k.shape[2:]), (b, h, d)))
 
-    def fill(self, k, v):
-        """The prefill's k and v [B, T, H, D] (device arrays) become rows [0, T)."""
+    def fill(self, k, v, route=None):
+        """The prefill's k and v [B, T, H, D] (device arrays) become rows [0, T) — quantized by ONE launch when the cache is
+        an int8 one (`route`: that launch's, None picks)."""
         b, t, h, d = (int(s) for s in k.shape)
+        if self.quant is not None:
+            self.k, self.v = da.zeros((b, self.max_len, h, d), np.uint8), da.zeros((b, self.max_len, h, int(v.shape[3])), np.uint8)
+            self.k_scale, self.v_scale = (da.zeros((b, self.max_len, h), np.float32) for _ in range(2))
+            da.kvq_quantize_rows(k, v, self.k, self.v, self.k_scale, self.v_scale, 0, "bthd", route=route)
+            self.length = t
+            return
         self.k = da.zeros((b, self.max_len, h, d), k.dtype)
         self.v = da.zeros((b, self.max_len, h, int(v.shape[3])), v.dtype)
         self.k[:, :t] = k
@@ -88,18 +104,28 @@ class LayerCache(object):
         self.length = t
 
 
-class KVCache(object):
-    """One LayerCache per layer that takes `cache`, made on demand: `cache.layer(i)` is layer i's."""
+def _check_quant(quant, extend):
+    if quant is not None and quant not in kvq.QUANTS:
+        raise ValueError("KVCache: quant must be None or one of %s, got %r" % (kvq.QUANTS, quant))
+    if quant is not None and extend:
+        raise ValueError("KVCache: extend=True with quant=%r (chunked prefill over a quantized cache is out of scope)" % quant)
+    return quant
 
-    def __init__(self, max_len, lens=None, extend=False):
+
+class KVCache(object):
+    """One LayerCache per layer that takes `cache`, made on demand: `cache.layer(i)` is layer i's.  quant="int8": every layer
+    keeps uint8 codes and float32 row scales (the module's head)."""
+
+    def __init__(self, max_len, lens=None, extend=False, quant=None):
         max_len = int(max_len)
         if max_len < 1:
             raise ValueError("KVCache: max_len must be >= 1, got %d" % max_len)
         self.max_len, self.layers, self.lens, self.extend = max_len, {}, lens, bool(extend)
+        self.quant = _check_quant(quant, extend)
 
     def layer(self, index):
         if index not in self.layers:
-            self.layers[index] = LayerCache(self.max_len, self.lens, self.extend)
+            self.layers[index] = LayerCache(self.max_len, self.lens, self.extend, self.quant)
         return self.layers[index]
 
     def set_lens(self, lens):
@@ -186,7 +212,15 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
     if N < 0:
         raise ValueError("generate: max_new_tokens must be >= 0, got %d" % N)
     ragged = prompt_lens is not None or eos_id is not None or capture or stop_every is not None or return_lengths
-    kept = cache if isinstance(cache, KVCache) else None       # the caller's cache: continued, and left to the caller
+    quant = cache if isinstance(cache, KVCache) and cache.quant is not None else None      # an int8 cache: used for ONE call
+    if quant is not None:
+        if quant.length or quant.lens is not None or quant.max_len < P + N:
+            raise ValueError("generate: a quantized KVCache must be empty, without lengths of its own, and hold the %d prompt + "
+                             "%d new tokens (max_len %d)" % (P, N, quant.max_len))
+        if prefill_chunk is not None:
+            raise ValueError("generate: prefill_chunk with a quantized KVCache (chunked prefill over a quantized cache is out "
+                             "of scope)")
+    kept = cache if isinstance(cache, KVCache) and quant is None else None       # the caller's cache: continued, and left to the caller
     if kept is not None:
         if ragged:
             raise ValueError("generate: a kept KVCache continues the uniform path — it excludes prompt_lens, eos_id, capture, "
@@ -235,7 +269,8 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
         out = da.zeros((B, P + N), np.int64)                   # every id of the run, on the device
         out[:, :P] = da.asarray(host)
         u_dev = None                                           # uploaded ONCE, in the dtype of the logits
-        kv = kept if kept is not None else KVCache(P + N, extend=prefill_chunk is not None) if cache else None
+        kv = kept if kept is not None else quant if quant is not None else \
+            KVCache(P + N, extend=prefill_chunk is not None) if cache else None
         for n in range(N):
             if cache and n > 0:
                 ids, offset = out[:, P + n - 1:P + n], L + P + n - 1
@@ -313,6 +348,9 @@ def _generate_ragged(model_or_net, layers, host, N, temperature, top_k, u, cache
 
     if N == 0 or B == 0:
         return result(ids)
+    if capture and isinstance(cache, KVCache) and (not _lib.get().has_kvq or da.KVQ_ROUTE == "composed"):
+        raise ValueError("generate: capture=True over a quantized cache needs the native route (libtnn_hip.so): the composed "
+                         "route quantizes on the host, which a graph capture cannot do")
     if capture and (not _lib.get().has_ragged or da.RAGGED_ROUTE == "composed" or da.DECODE_ROUTE == "composed"
                     or any(getattr(layer, "fused", True) is False for layer in layers)):
         raise ValueError("generate: capture=True needs the native route (libtnn_hip.so and fused layers): the composed route "
@@ -324,7 +362,12 @@ def _generate_ragged(model_or_net, layers, host, N, temperature, top_k, u, cache
         out = da.asarray(ids)                                  # every id of the run, on the device
         lens = da.lengths(start - 1)                           # the position of every sequence's LAST token
         start_d, done, cur = da.asarray(start), da.zeros((B,), np.int64), da.zeros((B,), np.int64)
-        kv = KVCache(Tout, lens) if cache else None
+        kv = None
+        if isinstance(cache, KVCache):                         # (generate() has checked it: quantized, empty, large enough)
+            kv = cache
+            kv.set_lens(lens)
+        elif cache:
+            kv = KVCache(Tout, lens)
         arange = np.arange(B, dtype=np.int64)
 
         def last_rows(logits, t):
