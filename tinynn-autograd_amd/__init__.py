@@ -67,6 +67,7 @@ from . import gated
 from . import extend
 from . import varlen
 from . import kvq
+from . import wq
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

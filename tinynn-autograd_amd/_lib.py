@@ -95,6 +95,10 @@ from ._kvq_signatures import _KVQ_SIGNATURES                  # noqa: E402  (inc
 
 KVQ_SYMBOLS = sorted(_KVQ_SIGNATURES)
 
+from ._wq_signatures import _WQ_SIGNATURES                    # noqa: E402  (include/tnn_wq.h: libtnn_hip.so only)
+
+WQ_SYMBOLS = sorted(_WQ_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -174,6 +178,8 @@ class _Lib(object):
         # composed attention with a key mask and a row mask built from the lengths on the host (varlen.py)
         # and the int8 key / value cache (include/tnn_kvq.h): under the twin device_array quantizes and dequantizes on the host
         # with kvq.py's numpy statement of the format and runs the composed decode over the dequantized prefix
+        # and the int8 weight-only linear layer (include/tnn_wq.h): under the twin device_array quantizes and dequantizes on the
+        # host with wq.py's numpy statement of the format and runs the ordinary product over the dequantized weight
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -189,7 +195,8 @@ class _Lib(object):
                                     (_GATED_SIGNATURES, "tnn_gated.h", "gated activation"),
                                     (_EXTEND_SIGNATURES, "tnn_extend.h", "cache-extending attention"),
                                     (_VARLEN_SIGNATURES, "tnn_varlen.h", "attention with per-sequence lengths"),
-                                    (_KVQ_SIGNATURES, "tnn_kvq.h", "int8 key / value cache")):
+                                    (_KVQ_SIGNATURES, "tnn_kvq.h", "int8 key / value cache"),
+                                    (_WQ_SIGNATURES, "tnn_wq.h", "int8 weight-only linear")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -215,6 +222,7 @@ class _Lib(object):
         self.has_extend = hasattr(self.cdll, "tnn_extend_attn")
         self.has_varlen = hasattr(self.cdll, "tnn_varlen_fwd")
         self.has_kvq = hasattr(self.cdll, "tnn_kvq_decode_attn")
+        self.has_wq = hasattr(self.cdll, "tnn_wq_linear")
 
     @staticmethod
     def _absent(name, what):

@@ -76,6 +76,8 @@ class Dense(Layer):
             self._init_parameters(inputs.shape[1])
         self.inputs = inputs                     # kept like the reference does (core/layers.py:48)
         w, b = (self.params[name] for name in PARAM_ORDER)
+        if ops.WQ_ACTIVE is not None and id(w) in ops.WQ_ACTIVE and not relu and not lazy and head_w is None:
+            return ops.linear_(inputs, w, b, None if self.fused else "composed")     # generate(weights=): the int8 codes
         if not self.fused:
             out = inputs @ w + b
             return ops.clip(out, 0.0) if relu else out
@@ -297,14 +299,14 @@ class MultiHeadAttention(Layer):
         rows = ops.reshape(inputs, (b * t, e))
         grouped = self.kv_heads is not None
         if cache is not None and cache.length > 0 and t > 1:     # (cache.check let it pass: a cache made with extend=True)
-            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h if n == "q" else hk, e // h))
+            q, k, v = (ops.reshape(ops.linear_(rows, p["w" + n], p["b" + n], route), (b, t, h if n == "q" else hk, e // h))
                        for n in "qkv")
             if self.rope is not None:                            # the new rows sit at the cache rows they are appended to
                 q, k = ops.rope_(q, k, rotary=self.rope, offset=cache.length, route=route)
             att = ops.attention_extend_(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
             cache.length += t
         elif cache is not None and cache.length > 0:
-            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, h if n == "q" else hk, e // h)) for n in "qkv")
+            q, k, v = (ops.reshape(ops.linear_(rows, p["w" + n], p["b" + n], route), (b, h if n == "q" else hk, e // h)) for n in "qkv")
             if self.rope is not None:                            # the step's row sits at the cache row it is appended to
                 where = (dict(positions=cache.lens) if getattr(cache, "lens", None) is not None
                          else dict(offset=cache.length))
@@ -323,7 +325,7 @@ class MultiHeadAttention(Layer):
                 att = decode(q, cache.k, cache.v, cache.length, k, v, layout="bthd", route=route)
             cache.length += 1
         else:
-            q, k, v = (ops.reshape(ops.dense_(rows, p["w" + n], p["b" + n]), (b, t, h if n == "q" else hk, e // h))
+            q, k, v = (ops.reshape(ops.linear_(rows, p["w" + n], p["b" + n], route), (b, t, h if n == "q" else hk, e // h))
                        for n in "qkv")
             if self.rope is not None:
                 q, k = ops.rope_(q, k, rotary=self.rope, route=route)
@@ -336,7 +338,7 @@ class MultiHeadAttention(Layer):
                     cache.fill(k.values, v.values, route=route)
                 else:
                     cache.fill(k.values, v.values)
-        out = ops.dense_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"])
+        out = ops.linear_(ops.reshape(att, (b * t, e)), p["wo"], p["bo"], route)
         return ops.reshape(out, (b, t, e))
 
     def _check_rope(self, t, cache):

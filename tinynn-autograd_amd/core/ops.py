@@ -487,6 +487,37 @@ def dense_(x, w, b, relu=False, head_w=None, lazy=False, head_b=None):
     return node
 
 
+def dense_wq_(x, qweight, b, route=None, splits=None, **unknown):
+    """x @ (code * scale) + b over an INT8 weight, INFERENCE ONLY (wq.py states the format): x [M, K] float32, qweight a
+    (codes, scales) pair — uint8 codes [K / 4, N, 4], one float32 scale per output column — as device_array.wq_quantize makes
+    it, b [1, N] or None.  Up to wq.MAX_ROWS rows (a decoding step) ONE tnn_wq_linear call reads a quarter of the float32
+    weight's bytes; more rows (a prefill) dequantize into a scratch weight and run the float32 GEMM; under the CPU test twin
+    and with route="composed" (or device_array.WQ_ROUTE) the weight is dequantized and the ordinary product runs.  The
+    result is a LEAF tensor without a grad_fn.  Out of scope: group-wise scales, int4 / fp8 codes, float64, a backward pass —
+    unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("dense_wq_: unsupported arguments %s (group-wise scales, int4 / fp8 codes and a backward pass are out "
+                        "of scope)" % sorted(unknown))
+    codes, scales = qweight
+    out = da.wq_linear(x.values, _raw_values(codes), _raw_values(scales), None if b is None else _raw_values(b), route=route,
+                       splits=splits)
+    return x.__class__(out, False, [])
+
+
+WQ_ACTIVE = None      # generation.generate(weights=): {id(parameter tensor): (codes, scales)} while it runs, else None
+
+
+def linear_(x, w, b, route=None):
+    """What the layers' plain projections call: ops.dense_, or — inside generate(weights=) and for a weight that was
+    quantized — ops.dense_wq_ on its codes (`route`: its route), in which case w's float values are not read.  With nothing
+    active this IS dense_: no launch more, no value changed."""
+    if WQ_ACTIVE is not None:
+        q = WQ_ACTIVE.get(id(w))
+        if q is not None:
+            return dense_wq_(x, q, b, route=route)
+    return dense_(x, w, b)
+
+
 class _ConvVjp(object):
     """The vjps of one ops.conv2d_ node: `fused_vjp` for Tensor.backward (dw and db from ONE launch, written into the
     parameters' arena views when they are lent; dx only when x is an edge), per-edge forms for everybody else."""

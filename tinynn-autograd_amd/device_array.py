@@ -42,6 +42,7 @@ from . import ragged as _rg
 from . import rope as _rp
 from . import tokens as _tk
 from . import varlen as _vl
+from . import wq as _wq
 from ._lib import F32, F64, I64, U8
 
 _CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.int64): I64,
@@ -2516,6 +2517,96 @@ def attention_decode_kvq(q, k_codes, v_codes, k_scales, v_scales, length=None, k
     kf, vf = (asarray(_kq.dequantize_host(np.asarray(c[live]), np.asarray(s[live]), np.float32), dtype=dt)
               for c, s in ((k_codes, k_scales), (v_codes, v_scales)))
     return gqa_decode(q.astype(dt), kf, vf, n, scale=plan.scale, layout=layout, route="composed")
+
+
+# ---------------------------------------------------------------------- kernels: the int8 weight-only linear layer (csrc/tnn_wq.hip)
+WQ_ROUTE = None       # tests / probes: "native" or "composed" overrides the planner's choice (wq.py)
+
+
+def _wq_weight(what, codes, scales):
+    """(K, N) of a quantized weight: dense device arrays, uint8 codes [K / 4, N, 4] and float32 scales [N]."""
+    for a, n, dt in ((codes, "codes", np.uint8), (scales, "scales", np.float32)):
+        if not isinstance(a, DeviceArray) or a._hv is not None or a._t or a.dtype != np.dtype(dt):
+            raise TypeError("%s: %s must be a dense device array of dtype %s" % (what, n, np.dtype(dt)))
+    K, N = _wq.weight_shape(codes.shape)
+    if scales.size != N:
+        raise ValueError("%s: %d scales for the %d columns of the codes" % (what, scales.size, N))
+    return K, N
+
+
+def _wq_on_device(lib, *arrays):
+    return lib.has_wq and all(a is None or a._ptr % 16 == 0 for a in arrays)
+
+
+def wq_quantize(w):
+    """w [K, N] float32 -> (codes uint8 [K / 4, N, 4], scales float32 [N]) (wq.py states the format; K and N multiples of
+    4).  ONE tnn_wq_quantize launch, nothing travels to the host; under the CPU test twin wq.quantize_host."""
+    what = "wq_quantize"
+    w = asarray(w)._contig()
+    if w.ndim != 2 or w.dtype != np.dtype(np.float32):
+        raise TypeError("%s: w must be a float32 matrix [K, N], got shape %s, dtype %s" % (what, tuple(w.shape), w.dtype))
+    K, N = w.shape
+    shape = _wq.codes_shape(K, N)
+    lib = _lib.get()
+    if _wq_on_device(lib, w):
+        codes, scales = DeviceArray._new(shape, np.uint8), DeviceArray._new((N,), np.float32)
+        lib.wq_quantize(w._ptr, N, codes._ptr, scales._ptr, K, N, _CODE[w.dtype])
+        return codes, scales
+    _kvq_eager(what)
+    c, s = _wq.quantize_host(np.asarray(w))
+    return asarray(c, dtype=np.uint8), asarray(s, dtype=np.float32)
+
+
+def wq_dequantize(codes, scales):
+    """codes, scales -> the float32 weight [K, N] they stand for, code * scale.  ONE tnn_wq_dequantize launch; under the CPU
+    test twin wq.dequantize_host."""
+    what = "wq_dequantize"
+    K, N = _wq_weight(what, codes, scales)
+    lib = _lib.get()
+    dt = np.dtype(np.float32)
+    if _wq_on_device(lib, codes, scales):
+        out = DeviceArray._new((K, N), dt)
+        lib.wq_dequantize(codes._ptr, scales._ptr, out._ptr, K, N, _CODE[dt])
+        return out
+    _kvq_eager(what)
+    return asarray(_wq.dequantize_host(np.asarray(codes), np.asarray(scales), np.float32), dtype=dt)
+
+
+def wq_linear(x, codes, scales, b=None, route=None, splits=None):
+    """y [M, N] float32 = x [M, K] (code * scale) + b over an int8 weight (wq.py).  Native, M <= wq.MAX_ROWS: ONE
+    tnn_wq_linear call that reads one byte per weight (a second small launch inside it when K is split over workgroups); its
+    arguments are fixed by the shapes, so it can be captured.  Native with more rows (a prefill): the weight is dequantized
+    into a scratch array and the float32 GEMM with the bias epilogue runs.  Composed: wq_dequantize and the ordinary product
+    and sum."""
+    what = "wq_linear"
+    K, N = _wq_weight(what, codes, scales)
+    x = asarray(x)._contig()
+    if b is not None:
+        b = asarray(b)._contig()
+    float_ok = x.dtype == np.dtype(np.float32) and (b is None or b.dtype == x.dtype)
+    if not float_ok and (x.dtype.kind != "f" or (b is not None and b.dtype.kind != "f")):
+        raise TypeError("%s: x and b must be floating-point" % what)
+    lib = _lib.get()
+    plan = _wq.plan_linear(x.shape, codes.shape, scales.shape, None if b is None else b.shape, splits, native=lib.has_wq,
+                           float_ok=float_ok, aligned=_wq_on_device(lib, x, codes, scales, b), route=route or WQ_ROUTE)
+    dt = np.dtype(np.float32)
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.kernel == "linear":
+        y = DeviceArray._new(plan.out_shape, dt)
+        nbytes = plan.workspace_bytes()
+        ws = DeviceArray._new((nbytes // 4,), dt) if nbytes else None
+        lib.wq_linear(x._ptr, K, codes._ptr, scales._ptr, _ptr_of(b), y._ptr, _ptr_of(ws), nbytes, plan.M, K, N, plan.splits,
+                      _CODE[dt])
+        return y
+    w = wq_dequantize(codes, scales)
+    x = x.astype(dt)
+    if plan.route == "native" and b is not None:
+        y = DeviceArray._new(plan.out_shape, dt)
+        lib.gemm_bias_act(0, 0, plan.M, N, K, x._ptr, K, w._ptr, N, b._ptr, _lib.ACT_NONE, 0, y._ptr, N, _CODE[dt])
+        return y
+    y = matmul(x, w)
+    return y if b is None else y + b.astype(dt).reshape(1, N)
 
 
 # ---------------------------------------------------------------------- kernels: cache-extending attention (csrc/tnn_extend.hip)

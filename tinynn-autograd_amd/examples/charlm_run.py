@@ -183,7 +183,7 @@ def main(args):
         if args.ragged:                                     # prompts of period .. 2 period tokens, the same in every run
             lens = args.period + np.arange(len(rows)) % (args.period + 1)
         out, ends = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, prompt_lens=lens, eos_id=args.eos,
-                             capture=args.capture, return_lengths=True,
+                             capture=args.capture, return_lengths=True, weights=getattr(args, "weight_quant", None),
                              cache=KVCache(args.seq, quant=quant) if quant is not None else True)
         new = np.stack([out[b, p:p + args.generate] for b, p in enumerate(lens)])
         motif = np.stack([rows[b, np.arange(p, p + args.generate) % args.period] for b, p in enumerate(lens)])
@@ -198,7 +198,8 @@ def main(args):
     kept = KVCache(args.seq, extend=True) if second > 0 else True       # the first turn's cache, kept for the second
     if quant is not None:
         kept = KVCache(args.seq, quant=quant)
-    out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, cache=kept, prefill_chunk=chunk)
+    out = generate(model, rows[:, :prompt_len], args.generate, temperature=0.0, cache=kept, prefill_chunk=chunk,
+                   weights=getattr(args, "weight_quant", None))     # --weight-quant int8: the projections run from int8 codes (wq.py)
     motif = rows[:, np.arange(prompt_len, prompt_len + args.generate) % args.period]     # what repeating the motif gives
     share = float((out[:, prompt_len:] == motif).mean())
     for row in out:
@@ -247,6 +248,9 @@ def parse(argv=None):
     parser.add_argument("--capture", action="store_true", help="--generate: record the token step into a graph and replay it")
     parser.add_argument("--kv-quant", dest="kv_quant", default=None, choices=("int8",),
                         help="--generate: keep the key / value cache as int8 codes with one float32 scale per row")
+    parser.add_argument("--weight-quant", dest="weight_quant", default=None, choices=("int8",),
+                        help="--generate: quantize the projection weights to int8 codes with one float32 scale per output column "
+                             "and generate from the codes")
     parser.add_argument("--prefill-chunk", dest="prefill_chunk", default=None, type=int, metavar="C",
                         help="--generate: run the prompt in pieces of C tokens (the pieces after the first extend the cache)")
     parser.add_argument("--second-turn", dest="second_turn", default=0, type=int, metavar="M",

@@ -39,6 +39,13 @@ every step runs ops.attention_decode_kvq_, which quantizes and appends the step'
 heads, uniform and ragged batches, rope, and the captured step.  generate(cache=KVCache(P + N, quant="int8")) uses it for
 ONE call (it must be empty); extend=True together with quant raises.  quant=None is the float path, bit for bit.
 
+Int8 weights (include/tnn_wq.h).  qw = quantize_weights(model, "int8") quantizes, once and on the device, every weight that
+reaches ops.dense_ during generation and fits the format (wq.py): Dense "w", the attention layer's wq / wk / wv / wo, the
+block's fc1 / fc2 — uint8 codes and one float32 scale per output column, a quarter of the bytes a decoding step reads.
+generate(weights=qw), or weights="int8" to quantize for the one call, runs the prefill and every step from the codes alone
+(ops.dense_wq_): the float values of a quantized weight are never read; embeddings, norms and biases stay float.  It holds
+on the uniform, ragged and captured paths and together with an int8 cache.  weights=None is the float path, launch for launch.
+
 Out of scope: ragged chunks (lengths read on the device with T > 1), top-p, bf16, and skipping the work
 of sequences that have ended (they go on emitting the pad token; `stop_every` ends the loop once ALL have ended).
 """
@@ -51,6 +58,7 @@ from . import _lib
 from . import device_array as da
 from . import kvq
 from . import ragged as rg
+from . import wq
 from .core import ops
 from .core.tensor import Tensor
 
@@ -149,6 +157,63 @@ class KVCache(object):
         self.layers = {}
 
 
+# the parameters that reach ops.dense_ as the weight, by layer class name (a TransformerBlock's flat dict names its parts')
+_WQ_WEIGHTS = {"Dense": ("w",), "MultiHeadAttention": ("wq", "wk", "wv", "wo"),
+               "TransformerBlock": ("attn.wq", "attn.wk", "attn.wv", "attn.wo", "fc1.w", "fc2.w")}
+
+
+class QuantizedWeights(object):
+    """The int8 codes of a model's projection weights (wq.py states the format), made by quantize_weights.
+
+        quantized   [(name, (K, N))] of what was quantized, name = "<layer index>.<parameter>"
+        kept        [(name, shape, why)] of the projection weights left in float32 (the format needs K and N in multiples of 4)
+        refresh()   requantize from the parameters as they are NOW (after further training, or Net.set_parameters)
+
+    generate(weights=this) runs every listed weight from its codes; the float values are not read while it is active."""
+
+    def __init__(self, model_or_net, quant="int8"):
+        if quant not in wq.QUANTS:
+            raise ValueError("quantize_weights: quant must be one of %s, got %r" % (wq.QUANTS, quant))
+        self.net, self.quant = getattr(model_or_net, "net", model_or_net), quant
+        self.refresh()
+
+    def refresh(self):
+        self.table, self.quantized, self.kept, self._owners = {}, [], [], []
+        for i, layer in enumerate(self.net.layers):
+            for name in _WQ_WEIGHTS.get(type(layer).__name__, ()):
+                tensor = layer.params.get(name)
+                label = "%d.%s" % (i, name)
+                if tensor is None:
+                    self.kept.append((label, None, "the layer has not seen a batch yet: no parameter"))
+                    continue
+                values = tensor.values
+                shape = tuple(int(s) for s in values.shape)
+                if wq.plan_weight(shape) != "int8" or values.dtype != np.dtype(np.float32):
+                    self.kept.append((label, shape, "the format needs a float32 [K, N] with K and N in multiples of 4"))
+                    continue
+                self.table[id(tensor)] = da.wq_quantize(values)
+                self._owners.append((layer, name, tensor))     # (keeps the tensor alive: its id is the key)
+                self.quantized.append((label, shape))
+        return self
+
+    def nbytes(self):
+        """(bytes of the codes and scales, bytes of the float32 weights they stand for)."""
+        kn = [k * n for _, (k, n) in self.quantized]
+        return sum(kn) + 4 * sum(n for _, (_, n) in self.quantized), 4 * sum(kn)
+
+    def activate(self):
+        """The table ops.linear_ consults, after checking that every quantized parameter still IS the layer's."""
+        for layer, name, tensor in self._owners:
+            if layer.params.get(name) is not tensor:
+                raise ValueError("generate: the model's parameter %r was replaced after quantize_weights — call refresh()" % name)
+        return self.table
+
+
+def quantize_weights(model_or_net, quant="int8"):
+    """Quantize every projection weight of the model once, on the device -> a QuantizedWeights for generate(weights=)."""
+    return QuantizedWeights(model_or_net, quant)
+
+
 _TAKES = {}      # (layer class, argument name) -> bool: inspect.signature costs more than a decoding step's launches
 
 
@@ -182,8 +247,11 @@ def _forward(layers, ids, offset, cache, positions=None):
 
 def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=None, u=None, seed=None, cache=True,
              generator=None, prompt_lens=None, eos_id=None, pad_id=0, capture=False, stop_every=None, return_lengths=False,
-             prefill_chunk=None):
+             prefill_chunk=None, weights=None):
     """Continue `prompt_ids` [B, P] (integers) by `max_new_tokens` tokens -> numpy int64 [B, P + N].
+
+    weights: None (the float weights, today's path launch for launch), a QuantizedWeights (quantize_weights) or "int8"
+    (quantize for this one call): the prefill and every step read the listed weights from their int8 codes (ops.dense_wq_).
 
     prompt_lens, eos_id, pad_id, capture, stop_every, return_lengths: the RAGGED path (_generate_ragged states them); with
     all of them at their defaults the path described here runs.
@@ -202,6 +270,21 @@ def generate(model_or_net, prompt_ids, max_new_tokens, temperature=1.0, top_k=No
     the ordinary prefill (the extension when L > 0), the rest through the extension at the offset of the rows already cached;
     the pieces before the last stop behind the last layer that takes the cache, so only the last piece reaches the head.
     The net runs in phase TEST; the previous phase is restored.  P + N beyond an Embedding's max_len raises before any launch."""
+    if weights is not None:
+        qw = quantize_weights(model_or_net, weights) if isinstance(weights, str) else weights
+        if not isinstance(qw, QuantizedWeights) or qw.net is not getattr(model_or_net, "net", model_or_net):
+            raise ValueError("generate: weights= takes None, \"int8\" or the QuantizedWeights of THIS model, got %r" % (weights,))
+        if ops.WQ_ACTIVE is not None:
+            raise RuntimeError("generate: another generate(weights=) is running")
+        if capture and not _lib.get().has_wq:
+            raise ValueError("generate: capture=True over int8 weights needs libtnn_hip.so: the CPU test twin dequantizes on "
+                             "the host, which a graph capture cannot do")
+        ops.WQ_ACTIVE = qw.activate()
+        try:
+            return generate(model_or_net, prompt_ids, max_new_tokens, temperature, top_k, u, seed, cache, generator, prompt_lens,
+                            eos_id, pad_id, capture, stop_every, return_lengths, prefill_chunk)
+        finally:
+            ops.WQ_ACTIVE = None
     net = getattr(model_or_net, "net", model_or_net)
     layers = net.layers
     host = np.asarray(getattr(prompt_ids, "values", prompt_ids))
