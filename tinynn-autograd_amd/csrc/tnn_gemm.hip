@@ -83,16 +83,7 @@ inline bool tn_extents_ok(const GemmArgs& g) {
 }
 
 // XCD-aware cut of a tile grid (GemmArgs::ord): the one with the smallest operand footprint per XCD, or none
-void pick_xcd_cut(GemmArgs& g) {
-    int xg_m = 0, xg_n = 0, best = 0;
-    for (int xm = 1; xm <= 8; xm *= 2) {
-        const int xn = 8 / xm;
-        if (g.tiles_m % xm || g.tiles_n % xn) continue;
-        const int cost = g.tiles_m / xm + g.tiles_n / xn;
-        if (!best || cost < best) { best = cost; xg_m = xm; xg_n = xn; }
-    }
-    g.ord = tnn::tile_order(g.tiles_m, g.tiles_n, xg_m, xg_n);
-}
+void pick_xcd_cut(GemmArgs& g) { g.ord = tnn::cut_tile_order(g.tiles_m, g.tiles_n); }
 
 // the mid-size kernel takes 16-B loads on its K-contiguous operands: alignment, ld % 4 == 0, K % 4 == 0, extents below 2 GiB
 bool mid_ok(const GemmArgs& g, int transA, int transB) {
@@ -146,6 +137,7 @@ void fill_small_fast(GemmArgs& g, bool akc, bool bkc) {
 // (the switch below, an order that does not pack, or operands the FAST form does not take), -1 = none launched yet.
 int g_small_args_form = -1;
 int g_bwd0_args_form = -1;           // the same for the last first-layer backward + Adam launch (tnn_dense_bwd_first_adam)
+int g_small_tile_rows = -1;          // rows per tile of its last SIXTEEN-WAVE launch: 16, or 8 (half-height form); tnn_small_tile_rows
 
 // TNN_STEP_ARGS=struct keeps every launch on the argument-block kernels, TNN_STEP_ARGS=struct:fwd16,bwd0 only the named parts
 // (fwd4 / fwd8 / fwd16: the FAST 16 x 16 kernel by waves per workgroup; bwd0; head: read in tnn_head.hip).  An A/B switch: read per
@@ -168,6 +160,7 @@ bool placed_at_once(int64_t workgroups) { return workgroups <= tnn::num_cus(); }
 template <int WAVES>
 int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
     small_geometry(g);
+    if (WAVES == 16) g_small_tile_rows = 16;
     dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
     hipStream_t s = tnn::stream();
     const bool fast = small_fast_ok(g, transA, transB);
@@ -197,6 +190,42 @@ int launch_small(GemmArgs& g, int transA, int transB, float* colsum) {
     return 0;
 }
 
+// The half-height form of the sixteen-wave FAST kernel (gemm_small_half_f32_kernel: 8 x 16 tiles, the same K slices, the same
+// bits).  Taken when the 16-row grid would leave at least half of the CUs without a workgroup, so the doubled grid is still
+// placed in one round: fwd0 of the MNIST step up to 128 rows.  Only the plain NN product without a head or `bump` has the body.
+// How deep K must be is gemm_small's sixteen-wave threshold (more than 48 chunks): below it a CU's L1 moves a third of the
+// bytes at most, and only K = 784 has been measured: 15.72 -> 15.545 us per step at 128 rows, 256 / 1024 rows (the 16-row grid
+// fills the CUs: today's kernel) inside the spread (profiles/fwd0_half_tiles_ab.txt).  TNN_FWD0_TILE=16 keeps the 16-row tiles (an A/B switch: read per call, not cached).
+bool half_tiles_ok(const GemmArgs& g, int transA, int transB) {
+    if (transA || transB || g.head_z != nullptr || g.bump != nullptr) return false;
+    if (const char* e = getenv("TNN_FWD0_TILE"))
+        if (atoi(e) == 16) return false;
+    const int64_t tiles16 = ((g.M + 15) / 16) * ((g.N + 15) / 16);
+    return 2 * tiles16 <= tnn::num_cus() && small_fast_ok(g, 0, 0);
+}
+
+int launch_small_half(GemmArgs& g, float* colsum) {
+    g.ord = tnn::half_tile_order(g.M, g.N, g.tiles_m, g.tiles_n);
+    g_small_tile_rows = 8;
+    g.splits = 1;
+    g.ws = nullptr;
+    fill_small_fast(g, true, false);
+    dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
+    hipStream_t s = tnn::stream();
+    tnn::PackedTileOrder po;
+    if (!step_args_struct_forced("fwd16") && tnn::pack_tile_order(g.ord, po)) {
+        const SmallFast& f = g.f;
+        hipLaunchKernelGGL(gemm_small_half_pre_f32_kernel, grid, 1024, 0, s, f.A, f.B, f.a_bytes, f.b_bytes, f.lda4, f.ldb4, f.M, f.N, f.K,
+                           po.w[0], po.w[1], po.w[2], g, colsum);
+        g_small_args_form = 1;
+    } else {
+        hipLaunchKernelGGL(gemm_small_half_f32_kernel, grid, 1024, 0, s, g, colsum);
+        g_small_args_form = 0;
+    }
+    TNN_LAUNCH_OK();
+    return 0;
+}
+
 bool use_small_path(const GemmArgs& g) {
     int64_t tiles = ((g.M + 15) / 16) * ((g.N + 15) / 16);
     // (the latency kernels' tile order divides by a 16-bit reciprocal, tnn_tile_order.h: a larger grid takes the tiled kernel)
@@ -216,6 +245,7 @@ int gemm_small(GemmArgs& g, int transA, int transB, float* colsum) {
     // — 1.5 us from the first to the last workgroup entry, profiles/r06_stepA_stamps.txt — costs less than the longer MFMA chain)
     if (nchunks <= 16) return launch_small<4>(g, transA, transB, colsum);
     if (nchunks <= 48) return launch_small<8>(g, transA, transB, colsum);
+    if (half_tiles_ok(g, transA, transB)) return launch_small_half(g, colsum);
     return launch_small<16>(g, transA, transB, colsum);
 }
 
@@ -641,6 +671,9 @@ int tnn_dense_bwd_first_adam(int64_t rows, int64_t n_in, int64_t n_out, const vo
 // How the last launch of the 16 x 16 latency kernel (which = 0) / of the first-layer backward + Adam (which = 1) got its
 // first-request arguments: 1 preloaded user SGPRs, 0 the argument block, -1 none yet.  For tests/test_gpu_step_arg_sgprs.py; not part of include/tnn_hip.h.
 __attribute__((visibility("default"))) int tnn_step_args_form(int which) { return which == 1 ? g_bwd0_args_form : g_small_args_form; }
+// Rows per tile of the last sixteen-wave launch of the 16 x 16 latency kernel (K above 768): 16, 8 (the half-height form) or -1 (none yet).
+// For tests/test_fwd_half_tiles.py; not part of include/tnn_hip.h.
+__attribute__((visibility("default"))) int tnn_small_tile_rows(void) { return g_small_tile_rows; }
 
 #ifdef TNN_STEP_TRACE
 // rows [kernel id][workgroup][4] of g_step_trace; `which` = 2 is served by tnn_head.hip's own buffer (tnn_debug_step_trace_head)
@@ -649,10 +682,11 @@ extern "C" __attribute__((visibility("default"))) int tnn_debug_step_trace(unsig
     TNN_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_trace), (size_t)std::min(n, 4 * 1024 * 4) * 8));
     return 0;
 }
-// [kernel id][workgroup]: wave 0's first chunk home (fwd0, fwd1, bwd0's tiles); its last chunk home is word [1] of the rows above
+// [kernel id][workgroup]: wave 0's first chunk home (fwd0, fwd1, bwd0's tiles); its last chunk home is word [1] of the rows above.
+// Row 4: the last chunk home of fwd0's LAST wave.
 extern "C" __attribute__((visibility("default"))) int tnn_debug_step_trace_first(unsigned long long* out, int n) {
     TNN_CHECK_HIP(hipDeviceSynchronize());
-    TNN_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_trace_first), (size_t)std::min(n, 4 * 1024) * 8));
+    TNN_CHECK_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_trace_first), (size_t)std::min(n, 5 * 1024) * 8));
     return 0;
 }
 #endif

@@ -154,5 +154,6 @@ __device__ __forceinline__ void small_tile_coords(const GemmArgs& g, const int b
 
 #ifdef TNN_STEP_TRACE
 __device__ unsigned long long g_step_trace[4 * 1024 * 4];        // tnn_internal.h: TNN_STEP_STAMP
-__device__ unsigned long long g_step_trace_first[4 * 1024];      // tnn_internal.h: TNN_STEP_STAMP_VALUE (a wave 0's first chunk home)
+// tnn_internal.h: TNN_STEP_STAMP_VALUE, rows [kernel id] (a wave 0's first chunk home); row 4: fwd0's LAST wave, its last chunk home
+__device__ unsigned long long g_step_trace_first[5 * 1024];
 #endif

@@ -409,12 +409,19 @@ __device__ __forceinline__ void dw_tile_wide(const DwFirst& q, const GemmArgs& g
 // HEAD = false: a caller that never has a head (no head_lds) gets no bodies for that role
 // q: what the first round of requests needs (FastFirst, tnn_gemm_args.h), from the argument block or from preloaded SGPRs;
 // everything else (the epilogue's operand, head_w, C, head_z) is read from g, behind the fragment requests
-template <bool AKC, bool BKC, int WAVES, bool SYS_HEADZ = false, bool HEAD = true>
+// ROWS = 8, the half-height tile (gemm_small_half_f32_kernel below): the workgroup owns rows m0 = 8 tm .. + 7 of the same 16
+// columns over the same K slices.  The MFMA is still 16 rows high: lanes whose A row is 8 .. 15 repeat the address of row - 8
+// (the same 64-byte segment of the same cache line: no byte more through the L1), so accumulator rows 8 .. 15 — lanes 32 .. 63
+// of every acc[r] — are copies that nobody reduces or stores; the epilogue runs on 128 threads.  Every output keeps its chunk
+// assignment, its MFMA chain and its sum over the WAVES partial tiles: the same bits as the 16-row form.  No head role.
+template <bool AKC, bool BKC, int WAVES, bool SYS_HEADZ = false, bool HEAD = true, int ROWS = 16>
 __device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmArgs& g, float* __restrict__ colsum, int block,
                                                 float (*red)[4][64], float (*bsum)[64], float* head_lds = nullptr) {
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     constexpr uint32_t OOB = 0xffffffffu;
     constexpr int KID = WAVES == 16 ? 0 : 1;              // (trace build: fwd0 runs 16 waves, fwd1 4 — or 8 in the data-parallel tail form)
+    static_assert(ROWS == 16 || (ROWS == 8 && !HEAD), "the half-height tile has no head role");
+    constexpr int E_LANES = ROWS * 4, E_THREADS = ROWS * 16;  // the epilogue's threads: lanes 0 .. E_LANES - 1 of acc[0 .. 3]
     TNN_STEP_STAMP(g_step_trace, KID, 0);                 // the entry stamp is the first thing: a stamp behind the prologue hides it
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int i16 = lane & 15, grp = lane >> 4;
@@ -423,8 +430,8 @@ __device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmAr
     const SmallFast& f = g.f;
     int tm, tn;
     tnn::tile_coords(q.ord, block, tm, tn);
-    const uint32_t m0 = (uint32_t)tm * 16u, n0 = (uint32_t)tn * 16u;
-    const uint32_t am = m0 + (uint32_t)i16, bn = n0 + (uint32_t)i16;
+    const uint32_t m0 = (uint32_t)tm * (uint32_t)ROWS, n0 = (uint32_t)tn * 16u;
+    const uint32_t am = m0 + (uint32_t)(i16 & (ROWS - 1)), bn = n0 + (uint32_t)i16;
     const bool a_ok = am < q.M, b_ok = bn < q.N;
     const int nchunks = q.nchunks;
     const uint32_t K = q.K, lda4 = q.lda4, ldb4 = q.ldb4;
@@ -436,9 +443,9 @@ __device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmAr
     const uint32_t a_chunk = AKC ? 64u : 16u * lda4;          // bytes per 16-deep chunk
     const uint32_t b_chunk = BKC ? 64u : 16u * ldb4;
 
-    const int e_r = tid >> 6, e_ln = tid & 63;
+    const int e_r = tid >> (ROWS == 16 ? 6 : 5), e_ln = tid & (E_LANES - 1);
     const uint32_t e_row = m0 + (uint32_t)((e_ln >> 4) * 4 + e_r), e_col = n0 + (uint32_t)(e_ln & 15);   // 16x16x4 C/D layout
-    const bool e_live = tid < 256 && e_row < q.M && e_col < q.N;
+    const bool e_live = tid < E_THREADS && e_row < q.M && e_col < q.N;
     // The epilogue's operand and wave 0's head_w fragment travel like the K loop's fragments: a buffer resource (a NULL bias /
     // no operand: 0 bytes long, every offset reads 0), a 32-bit byte offset, and 0xffffffff for a thread, row or unit that does
     // not exist.  Left to pointers, each of these loads sat under its own exec-mask branch behind a 64-bit multiply-add whose
@@ -563,7 +570,7 @@ __device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmAr
         }
     };
     if (HEAD && head_on && swid == 0) by_live(IntC<2>{});
-    else if (WAVES <= 4 || swid < 4) by_live(IntC<1>{});
+    else if ((ROWS == 16 && WAVES <= 4) || swid < E_THREADS / 64) by_live(IntC<1>{});
     else by_live(IntC<0>{});
     // later batches (more than WAVES * MAXC chunks): their waits stand on their own loads
     for (int c0 = swid + WAVES * MAXC; c0 < nchunks; c0 += WAVES * MAXC) {
@@ -589,8 +596,9 @@ __device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmAr
     TNN_STEP_STAMP(g_step_trace, KID, 2);
     TNN_STEP_STAMP_VALUE(g_step_trace_first, KID, 1, 0, t_first);
     TNN_STEP_STAMP_VALUE(g_step_trace, KID, 4, 1, t_last);
+    if constexpr (WAVES == 16) TNN_STEP_STAMP_VALUE_WAVE(g_step_trace_first, WAVES - 1, 4, t_last);
     float e_val = 0.f;
-    if (tid < 256) {
+    if (tid < E_THREADS) {
         float s = 0.f;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) s += red[w][e_r][e_ln];
@@ -605,7 +613,7 @@ __device__ __forceinline__ void small_tile_fast(const FastFirst& q, const GemmAr
         for (int w = 0; w < WAVES; ++w) s += (bsum[w][tid] + bsum[w][16 + tid]) + (bsum[w][32 + tid] + bsum[w][48 + tid]);
         colsum[n0 + tid] = s;
     }
-    if (head_lds != nullptr && g.head_z != nullptr) {
+    if (HEAD && head_lds != nullptr && g.head_z != nullptr) {
         // This tile's share of the NEXT layer's logits: head_z[tn][row][c] = sum over the tile's 16 columns of
         // out[row][col] * head_w[n0 + col][c] (a sign-encoded ReLU zero, -0.0, contributes -0 * w = 0).  The classifier
         // head then only ADDS tiles_n partials per logit instead of re-reading the whole activation and redoing the
@@ -666,4 +674,29 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_small_pre_f32_kernel(const fl
     small_tile_fast<AKC, BKC, WAVES>(fast_first_sgprs(A, B, a_bytes, b_bytes, lda4, ldb4, M, N, K, o0, o1, o2), g, colsum,
                                      (int)blockIdx.x, red, bsum, head_lds);
     if (g.bump != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *g.bump += 1u;
+}
+
+// fwd0 of the MNIST step on half-height tiles: 8 rows x 16 columns over the whole K, so a product whose 16-row grid fills at most
+// half of the CUs puts a workgroup on every one of them and each CU's vector L1 delivers 8 instead of 16 rows of A next to the same
+// 16 columns of B (784-deep: 75 KB instead of 100 KB).  NN form, sixteen waves; no head role and no `bump` (gemm_small picks the
+// launches, tnn_gemm.hip).  The two kernels differ as gemm_small_f32_kernel<.., FAST> and gemm_small_pre_f32_kernel do.
+// Compiled without the packed fp32 forms (the unit's other kernels predate that rule): the reduction's adds stay scalar.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TNN_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define TNN_NO_PACKED_F32                                    // (the host pass does not know the feature)
+#endif
+__global__ __launch_bounds__(1024) TNN_NO_PACKED_F32 void gemm_small_half_f32_kernel(GemmArgs g, float* __restrict__ colsum) {
+    __shared__ float red[16][4][64];
+    __shared__ float bsum[16][64];
+    small_tile_fast<true, false, 16, false, false, 8>(fast_first(g), g, colsum, (int)blockIdx.x, red, bsum);
+}
+__global__ __launch_bounds__(1024) TNN_NO_PACKED_F32 void gemm_small_half_pre_f32_kernel(const float* A, const float* B, uint32_t a_bytes, uint32_t b_bytes,
+                                                                       uint32_t lda4, uint32_t ldb4, uint32_t M, uint32_t N, uint32_t K,
+                                                                       uint32_t o0, uint32_t o1, uint32_t o2, GemmArgs g,
+                                                                       float* __restrict__ colsum) {
+    __shared__ float red[16][4][64];
+    __shared__ float bsum[16][64];
+    small_tile_fast<true, false, 16, false, false, 8>(fast_first_sgprs(A, B, a_bytes, b_bytes, lda4, ldb4, M, N, K, o0, o1, o2), g, colsum,
+                                                      (int)blockIdx.x, red, bsum);
 }

@@ -85,11 +85,17 @@ void set_update_guard(const int* device_word);
     do {                                                                                                                  \
         if (threadIdx.x == 0 && blockIdx.x < 1024) (buf)[((kid) * 1024 + blockIdx.x) * (stride) + (slot)] = (val);        \
     } while (0)
+// the same from the first thread of wave `wave` (fwd0: its LAST wave's last chunk home, row 4 of g_step_trace_first)
+#define TNN_STEP_STAMP_VALUE_WAVE(buf, wave, kid, val)                                                                    \
+    do {                                                                                                                  \
+        if (threadIdx.x == (wave) * 64 && blockIdx.x < 1024) (buf)[(kid) * 1024 + blockIdx.x] = (val);                    \
+    } while (0)
 #else
 #define TNN_STEP_STAMP TNN_STAMP_OFF
 #define TNN_STEP_STAMP_ACKED TNN_STAMP_OFF
 #define TNN_STEP_CLOCK_HOME TNN_STAMP_OFF
 #define TNN_STEP_STAMP_VALUE TNN_STAMP_OFF
+#define TNN_STEP_STAMP_VALUE_WAVE TNN_STAMP_OFF
 #endif
 // -DTNN_AR_TRACE: the data-parallel step's fused launches (g_fh_trace, g_ar_trace in tnn_gemm_step.h, SkipRanges::trace in
 // tnn_p2p.h; tools/probes/ar_fused_trace.py)

@@ -50,6 +50,27 @@ inline TileOrder tile_order(int tiles_m, int tiles_n, int xg_m, int xg_n) {
     return o;
 }
 
+// The order of a GEMM tile grid under the XCD cut with the smallest operand footprint per XCD (tiles_m / xg_m tile rows of A
+// plus tiles_n / xg_n tile columns of B; the first of equals), or the plain order when no power-of-two pair divides the grid
+inline TileOrder cut_tile_order(int tiles_m, int tiles_n) {
+    int xg_m = 0, xg_n = 0, best = 0;
+    for (int xm = 1; xm <= 8; xm *= 2) {
+        const int xn = 8 / xm;
+        if (tiles_m % xm || tiles_n % xn) continue;
+        const int cost = tiles_m / xm + tiles_n / xn;
+        if (!best || cost < best) { best = cost; xg_m = xm; xg_n = xn; }
+    }
+    return tile_order(tiles_m, tiles_n, xg_m, xg_n);
+}
+
+// The grid of the half-height forward tiles (tnn_gemm_small.h: 8 rows x 16 columns) of an M x N product and its order:
+// 128 x 256 is 16 x 16 tiles, cut 2 x 4 — an XCD's L2 fills 64 rows of A and 64 columns of B, as under the 16-row tiles
+inline TileOrder half_tile_order(int64_t M, int64_t N, int& tiles_m, int& tiles_n) {
+    tiles_m = (int)((M + 7) / 8);
+    tiles_n = (int)((N + 15) / 16);
+    return cut_tile_order(tiles_m, tiles_n);
+}
+
 // The two tile roles of the merged head + hidden-backward launch (tnn_head.hip: mlp_head_bwd_kernel and its row-blocked form;
 // 128 hidden units = 8 unit tiles) for `tiles_in` input tiles and `tr` row tiles; returns the number of dW tiles, the dx tiles
 // follow them.  dW1 (tiles_in x 8 tiles, tm over the inputs): XCD x takes the inputs' half x % 2 and the units' quarter x / 2

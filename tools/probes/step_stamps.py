@@ -39,14 +39,14 @@ except AttributeError:                                 # a trace library from be
     ff = lambda ptr, n: 0
 gbuf = np.zeros(4 * 1024 * 4, dtype=np.uint64)
 hbuf = np.zeros(1024 * 4, dtype=np.uint64)
-fbuf = np.zeros(4 * 1024, dtype=np.uint64)
+fbuf = np.zeros(5 * 1024, dtype=np.uint64)            # row 4: fwd0's LAST wave, its last chunk home (zeros from an older library)
 acc = []
 first = []
 for it in range(60):
     t.step(x, y)
     if it >= 20:
         assert fg(gbuf.ctypes.data, gbuf.size) == 0 and fh(hbuf.ctypes.data, hbuf.size) == 0 and ff(fbuf.ctypes.data, fbuf.size) == 0
-        first.append(fbuf.reshape(4, 1024).astype(np.int64).copy())
+        first.append(fbuf.reshape(5, 1024).astype(np.int64).copy())
         g = gbuf.reshape(4, 1024, 4).astype(np.int64).copy()
         g[2] = hbuf.reshape(1024, 4).astype(np.int64)
         acc.append(g)
@@ -56,7 +56,8 @@ names = ["fwd0  gemm_small_f32_kernel<.., 16, ..>  (784 -> 256, bias + ReLU)",
          "fwd1  gemm_small_f32_kernel<.., 4, ..>   (256 -> 128, bias + ReLU, partial logits)",
          "head  mlp_head_bwd_kernel<128, 10>       (loss, dz, dW2 / db2, dW1 / db1, dx1)",
          "bwd0  dense_bwd0_adam_kernel<4>          (dW0 / db0 + Adam over the arena)"]
-grids = [8 * 16, 8 * 8, 16 + 16 * 8 + (8 * 8 if os.environ.get("TNN_HEAD_DX_WIDE", "1") != "0" else 8 * 16),
+# fwd0: 8-row tiles at 128 rows and below (16 x 16 of them) unless TNN_FWD0_TILE=16 keeps the 16-row form (8 x 16)
+grids = [8 * 16 if os.environ.get("TNN_FWD0_TILE") == "16" else 16 * 16, 8 * 8, 16 + 16 * 8 + (8 * 8 if os.environ.get("TNN_HEAD_DX_WIDE", "1") != "0" else 8 * 16),
          49 * 8 if os.environ.get("TNN_DW0_WIDE", "1") != "0" else 49 * 16]
 print("# rows %d; us relative to the launch's first workgroup entry; min / median / max over workgroups (median over 40 steps)" % rows)
 if rows > 128:
@@ -74,9 +75,11 @@ for k in range(4):
     print("%s   workgroups %d (%.2f per CU)" % (names[k], n, n / 256.0))
     chunked = (tf[:, k, :n] > 0).any()                 # fwd0, fwd1, bwd0's tiles: [1] is the last chunk's clock read
     for s, label in ((0, "entry"), (-1, "first chunk home (wave 0)"), (1, "last chunk home (wave 0)" if chunked else "operands in registers"),
-                     (2, "last MFMA, sums read back"), (3, "last store acknowledged")):
+                     (-2, "last chunk home (last wave)"), (2, "last MFMA, sums read back"), (3, "last store acknowledged")):
+        if s == -2 and k != 0:
+            continue
         if s < 0:
-            raw = tf[:, k, :n]
+            raw = tf[:, k if s == -1 else 4, :n]
             v = (raw - t0[:, :, 0]) / 100.0
         else:
             raw = blk[:, :, s]
