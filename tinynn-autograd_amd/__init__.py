@@ -68,6 +68,7 @@ from . import extend
 from . import varlen
 from . import kvq
 from . import wq
+from . import lce
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

@@ -99,6 +99,10 @@ from ._wq_signatures import _WQ_SIGNATURES                    # noqa: E402  (inc
 
 WQ_SYMBOLS = sorted(_WQ_SIGNATURES)
 
+from ._lce_signatures import _LCE_SIGNATURES                  # noqa: E402  (include/tnn_lce.h: libtnn_hip.so only)
+
+LCE_SYMBOLS = sorted(_LCE_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -180,6 +184,8 @@ class _Lib(object):
         # with kvq.py's numpy statement of the format and runs the composed decode over the dequantized prefix
         # and the int8 weight-only linear layer (include/tnn_wq.h): under the twin device_array quantizes and dequantizes on the
         # host with wq.py's numpy statement of the format and runs the ordinary product over the dequantized weight
+        # and the fused linear + cross-entropy (include/tnn_lce.h): under the twin device_array runs the dense product and the
+        # per-row cross-entropy over whole logits (lce.py: the composed route)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -196,7 +202,8 @@ class _Lib(object):
                                     (_EXTEND_SIGNATURES, "tnn_extend.h", "cache-extending attention"),
                                     (_VARLEN_SIGNATURES, "tnn_varlen.h", "attention with per-sequence lengths"),
                                     (_KVQ_SIGNATURES, "tnn_kvq.h", "int8 key / value cache"),
-                                    (_WQ_SIGNATURES, "tnn_wq.h", "int8 weight-only linear")):
+                                    (_WQ_SIGNATURES, "tnn_wq.h", "int8 weight-only linear"),
+                                    (_LCE_SIGNATURES, "tnn_lce.h", "fused linear + cross-entropy")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -223,6 +230,7 @@ class _Lib(object):
         self.has_varlen = hasattr(self.cdll, "tnn_varlen_fwd")
         self.has_kvq = hasattr(self.cdll, "tnn_kvq_decode_attn")
         self.has_wq = hasattr(self.cdll, "tnn_wq_linear")
+        self.has_lce = hasattr(self.cdll, "tnn_lce_fwd")
 
     @staticmethod
     def _absent(name, what):

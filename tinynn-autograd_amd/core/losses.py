@@ -65,6 +65,28 @@ class CrossEntropyLoss(BaseLoss):
                                   route=None if self.fused else "composed")
 
 
+class LinearCrossEntropyLoss(BaseLoss):
+    """CrossEntropyLoss over the logits of a net's last `Dense`, computed from the activations that FEED it: the head's product,
+    the log-sum-exp and the gather run as one node (ops.linear_cross_entropy_) that never writes the logits [M, V] or their
+    gradient — at a real vocabulary those are the largest arrays of a training step.  `head` is that Dense (it stays in the
+    net: the optimizer, save / load and generation see it unchanged; its parameters must exist — Dense(vocab, num_in=width));
+    `loss(hidden, targets)` takes what Net.forward(.., hidden=True) returns.  ignore_index and reduction: CrossEntropyLoss.
+    `fused=False` runs the composed route: the head's ordinary forward and cross_entropy_ over whole logits."""
+
+    def __init__(self, head, ignore_index=None, reduction="mean", fused=True):
+        from ..tokens import REDUCTIONS
+        if reduction not in REDUCTIONS:
+            raise ValueError("LinearCrossEntropyLoss: reduction must be one of %s, got %r" % (REDUCTIONS, reduction))
+        self.head, self.ignore_index, self.reduction, self.fused = head, ignore_index, reduction, fused
+
+    def loss(self, hidden, targets):
+        params = self.head.params
+        if params.get("w") is None:
+            raise ValueError("LinearCrossEntropyLoss: the head's parameters do not exist yet (build it with num_in=)")
+        return ops.linear_cross_entropy_(hidden, params["w"], params.get("b"), targets, ignore_index=self.ignore_index,
+                                         reduction=self.reduction, route=None if self.fused else "composed")
+
+
 class SquaredErrorLoss(BaseLoss):
     """((pred - target) ** 2).sum() / m — the loss test/test_autograd.py:119-121 builds from ops and the
     one BASELINE.json's 4096-wide autoencoder config uses."""

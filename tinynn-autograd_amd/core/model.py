@@ -53,8 +53,11 @@ class Model(object):
         self._pending_first = None   # (x, dz, w, rows, n_in, n_out): the first Dense layer's backward, deferred to step()
         self._clip_rec = self._clip_ws = None    # clip_grad_norm's device record and workspace (include/tnn_ostep.h)
 
-    def forward(self, inputs, lens=None):
-        """lens: per-sequence lengths of a right-padded batch, handed to the layers that take them (Net.forward)."""
+    def forward(self, inputs, lens=None, hidden=False):
+        """lens: per-sequence lengths of a right-padded batch, handed to the layers that take them (Net.forward).
+        hidden=True: the activations that feed the net's last Dense instead of its logits (Net.forward)."""
+        if hidden:
+            return self.net.forward(inputs, lens=lens, hidden=True)
         return self.net.forward(inputs) if lens is None else self.net.forward(inputs, lens=lens)
 
     def get_phase(self):

@@ -29,19 +29,25 @@ class Net(object):
         self._phase = "TRAIN"
 
     # ------------------------------------------------------------------ reference API
-    def forward(self, inputs, lens=None):
+    def forward(self, inputs, lens=None, hidden=False):
         """lens (per-sequence lengths of a right-padded batch: MultiHeadAttention.forward) is handed to the layers whose
         `forward` declares it, as generation does for `cache`; None: nothing changes.
+        hidden=True: the last layer, which must be a `Dense`, is NOT run and the activations that feed it are returned — what
+        losses.LinearCrossEntropyLoss takes, together with that layer, instead of the logits.
         Thread the input through the layers (core/nn.py:10-13).  A fused `Dense` directly followed by a `ReLU` runs
         as ONE node (GEMM + bias + clip(., 0) epilogue, ops.dense_(relu=True); likewise a fused `Conv2D`, ops.conv2d_); the
         ReLU layer object is then skipped —
         its `inputs` attribute (cached but never read by the reference, core/layers.py:67) holds the fused output."""
         layers, i, activations = self.layers, 0, inputs
+        if hidden:
+            if not layers or type(layers[-1]) is not Dense:
+                raise ValueError("Net.forward(hidden=True): the last layer must be a Dense (the head the loss takes over)")
+            layers = layers[:-1]
         n = len(layers)
         # TRAIN mode, ... Dense -> ReLU -> Dense(classifier): the hidden layer's launch also emits the classifier's logits as
         # partial sums and the classifier's own GEMM is deferred — the loss node runs forward + loss + backward of the head
         # in one launch (ops.softmax_nll_); in TEST mode, or if anything else asks for the logits first, nothing changes
-        head = (self._phase == "TRAIN" and n >= 3 and type(layers[-1]) is Dense and layers[-1].fused
+        head = (not hidden and self._phase == "TRAIN" and n >= 3 and type(layers[-1]) is Dense and layers[-1].fused
                 and type(layers[-2]) is ReLU and type(layers[-3]) is Dense and layers[-3].fused and layers[-1].is_init)
         while i < n:
             layer = layers[i]

@@ -1119,6 +1119,73 @@ def cross_entropy_(logits, targets, ignore_index=None, reduction="mean", route=N
     return node
 
 
+class _LceVjp(object):
+    """The vjps of one ops.linear_cross_entropy_ node: `fused_vjp` for Tensor.backward (ONE chunked pass for whichever of h, w
+    and b require gradients, dw and db written into arena views when they are lent), per-edge forms for everybody else."""
+    __slots__ = ("h", "w", "b", "tg", "lse", "count", "kw", "edges")
+
+    def __init__(self, h, w, b, tg, lse, count, kw):
+        self.h, self.w, self.b, self.tg, self.lse, self.count, self.kw = h, w, b, tg, lse, count, kw
+        self.edges = ()
+
+    def _bwd(self, g, names, home=None):
+        home = home or {}
+        dh, dw, db = da.linear_cross_entropy_bwd(self.h.values, self.w.values, None if self.b is None else self.b.values, self.tg,
+                                                 self.lse, self.count, g, need_dh="h" in names, need_dw="w" in names,
+                                                 need_db="b" in names, dw_out=home.get("w"), db_out=home.get("b"), **self.kw)
+        return {"h": dh, "w": dw, "b": db}
+
+    def d_h(self, g):
+        return self._bwd(g, ("h",))["h"]
+
+    def d_w(self, g):
+        return self._bwd(g, ("w",))["w"]
+
+    def d_b(self, g):
+        return self._bwd(g, ("b",))["b"]
+
+    def fused_vjp(self, g, homes):
+        res = self._bwd(g, self.edges, dict(zip(self.edges, homes)))
+        return [res[name] for name in self.edges]
+
+
+def linear_cross_entropy_(h, w, b, targets, ignore_index=None, reduction="mean", route=None, chunk_rows=None, **unknown):
+    """The loss of a vocabulary head as ONE node: cross_entropy_(dense_(h, w, b), targets) without the logits.  h [.., K] (the
+    leading axes fold into the rows), w [K, V] and b [1, V] (or None) as Dense holds them, targets [..] as cross_entropy_ takes
+    them, with its ignore_index, reduction and range rules.  Returns the scalar loss.
+
+    Native (float32, lce.py): forward ONE tnn_lce_fwd call whose score tiles live in MFMA accumulators and are never written;
+    backward takes the rows in chunks of `chunk_rows` (None: lce.choose_chunk_rows), recomputes each chunk's scores into
+    dz [chunk_rows, V] (tnn_lce_dlogits) and feeds the library's GEMMs — dh, dw and db for whichever of h, w and b require
+    them, the upstream gradient and the row count as device scalars.  The most it ever holds of [M, V] is one chunk.
+    route="composed" (or device_array.LCE_ROUTE; float64; the CPU test twin): dense_ followed by cross_entropy_ over whole
+    logits.  Out of scope: bf16, a weight stored [V, K] or tied to an embedding, label smoothing, z-loss — unknown keyword
+    arguments raise."""
+    if unknown:
+        raise TypeError("linear_cross_entropy_: unsupported arguments %s (label smoothing, z-loss, bf16 and tied weights are out "
+                        "of scope)" % sorted(unknown))
+    from .. import lce
+    tg = _index_values(targets, int(w.shape[-1]), "linear_cross_entropy", also=ignore_index)
+    values = [t.values for t in (h, w, b) if t is not None]
+    float_ok = all(v.dtype == np.dtype(np.float32) for v in values)
+    plan = lce.plan_linear_cross_entropy(h.shape, w.shape, None if b is None else b.shape, tg.shape, ignore_index, reduction,
+                                         chunk_rows=chunk_rows, native=_lib.get().has_lce, float_ok=float_ok,
+                                         route=route or da.LCE_ROUTE)
+    if plan.route == "composed":
+        rows = reshape_(h, (plan.M, plan.K)) if h.values.ndim != 2 else h
+        logits = dot_(rows, w) if b is None else dense_(rows, w, b)
+        return cross_entropy_(logits, tg.reshape(plan.M), ignore_index=ignore_index, reduction=reduction)
+    loss, _, lse, count = da.linear_cross_entropy(h.values, w.values, None if b is None else b.values, tg,
+                                                  ignore_index=ignore_index, reduction=reduction, route="native")
+    ctx = _LceVjp(h, w, b, tg, lse, count, dict(ignore_index=ignore_index, reduction=reduction, route="native",
+                                                chunk_rows=chunk_rows))
+    named = [("h", h, ctx.d_h), ("w", w, ctx.d_w), ("b", b, ctx.d_b)]
+    node = _make_node(h.__class__, loss, [(t, fn) for _, t, fn in named if t is not None])
+    ctx.edges = [name for name, t, _ in named if t is not None and t.requires_grad]
+    node._fused_vjp = ctx.fused_vjp
+    return node
+
+
 def _softmax_head(logits, labels):
     """The classifier head as ONE launch when the logits are still pending (dense_(lazy=True)) and the shapes are the ones
     tnn_mlp_head_tick takes: last Dense forward (core/layers.py:49) + whole-batch softmax NLL (core/losses.py:24-32) + the last
@@ -1436,6 +1503,14 @@ def embedding(obj, ids, pos=None, padding_idx=None, **unknown):
     if unknown:
         raise TypeError("embedding: unsupported arguments %s" % sorted(unknown))
     return embedding_(as_tensor(obj), ids, _opt_tensor(pos), padding_idx=padding_idx)
+
+
+def linear_cross_entropy(h, w, b, targets, ignore_index=None, reduction="mean", **unknown):
+    """not in the reference: see linear_cross_entropy_ (unknown keyword arguments raise)"""
+    if unknown:
+        raise TypeError("linear_cross_entropy: unsupported arguments %s" % sorted(unknown))
+    return linear_cross_entropy_(as_tensor(h), as_tensor(w), None if b is None else as_tensor(b), targets,
+                                 ignore_index=ignore_index, reduction=reduction)
 
 
 def cross_entropy(obj, targets, ignore_index=None, reduction="mean", **unknown):

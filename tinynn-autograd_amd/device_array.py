@@ -37,6 +37,7 @@ from . import gated as _gt
 from . import gqa as _gq
 from . import indexing as _ix
 from . import kvq as _kq
+from . import lce as _lc
 from . import norm as _nm
 from . import ragged as _rg
 from . import rope as _rp
@@ -2607,6 +2608,97 @@ def wq_linear(x, codes, scales, b=None, route=None, splits=None):
         return y
     y = matmul(x, w)
     return y if b is None else y + b.astype(dt).reshape(1, N)
+
+
+# ---------------------------------------------------------------------- kernels: fused linear + cross-entropy (csrc/tnn_lce.hip)
+LCE_ROUTE = None      # tests / probes: "native" or "composed" overrides the planner's choice (lce.py)
+
+
+def _lce_operands(what, h, w, b, targets, ignore_index, reduction, route, splits=None, chunk_rows=None):
+    """(plan, dtype, h [M, K], w, b or None, targets on the device, their host copy or None) of both halves of the op."""
+    dt, (h, w, b) = _operands(h, w, b)
+    if w.ndim != 2 or h.ndim < 1:
+        raise ValueError("%s: h must be [.., K] and w [K, V], got shapes %s and %s" % (what, tuple(h.shape), tuple(w.shape)))
+    tg, host = _token_ids(targets, w.shape[1], what, also=ignore_index)
+    plan = _lc.plan_linear_cross_entropy(h.shape, w.shape, None if b is None else b.shape, tg.shape, ignore_index, reduction,
+                                         splits=splits, chunk_rows=chunk_rows, native=_lib.get().has_lce,
+                                         float_ok=dt == np.dtype(np.float32), route=route or LCE_ROUTE)
+    return plan, dt, h.reshape(plan.M, plan.K), w, b, tg, host
+
+
+def _lce_logits(plan, h, w, b):
+    """The whole logits [M, V] of the composed route."""
+    z = matmul(h, w)
+    return z if b is None else z + b.reshape(1, plan.V)
+
+
+def linear_cross_entropy(h, w, b, targets, ignore_index=None, reduction="mean", route=None, splits=None):
+    """(loss, losses, lse, count) of the per-row softmax cross-entropy of z = h w + b against integer targets, with the
+    meaning of cross_entropy's results: h [.., K] (leading axes fold into the rows), w [K, V] as Dense stores it, b [V] /
+    [1, V] or None, targets [..] as cross_entropy takes them.  Native (float32): ONE tnn_lce_fwd call — MFMA score tiles that
+    are folded into a running (max, sum) per row and never written, the vocabulary cut into `splits` runs (lce.choose_splits)
+    that a second small launch merges in split order; its arguments are fixed by the shapes, so it can be captured.
+    Composed (float64, the CPU test twin): the product, the bias sum and cross_entropy over whole logits."""
+    plan, dt, h, w, b, tg, _ = _lce_operands("linear_cross_entropy", h, w, b, targets, ignore_index, reduction, route, splits)
+    if plan.route != "native":
+        return cross_entropy(_lce_logits(plan, h, w, b).reshape(plan.rows_shape + (plan.V,)), targets, ignore_index=ignore_index,
+                             reduction=reduction)
+    losses, lse = DeviceArray._new(plan.rows_shape, dt), DeviceArray._new(plan.rows_shape, dt)
+    loss, count = DeviceArray._new((), dt), DeviceArray._new((), dt)
+    nbytes = plan.workspace_bytes()
+    ws = DeviceArray._new((nbytes // 4,), dt) if nbytes else None
+    _lib.get().lce_fwd(h._ptr, plan.K, w._ptr, plan.V, _ptr_of(b), tg._ptr, losses._ptr, lse._ptr, loss._ptr, count._ptr,
+                       _ptr_of(ws), nbytes, plan.M, plan.K, plan.V, plan.splits, plan.ignore_index,
+                       _tk.REDUCTION_CODE[reduction], _CODE[dt])
+    return loss, losses, lse, count
+
+
+def linear_cross_entropy_bwd(h, w, b, targets, lse, count, g=1.0, ignore_index=None, reduction="mean", route=None,
+                             chunk_rows=None, need_dh=True, need_dw=True, need_db=True, dh_out=None, dw_out=None, db_out=None):
+    """(dh, dw, db) of linear_cross_entropy from its saved per-row lse and count; a gradient that is not needed is None and its
+    product is skipped, and with none needed nothing is launched.  g (the gradient of the loss) and count are used as DEVICE
+    scalars: nothing is read on the host.  Native: the rows are taken in ascending chunks of chunk_rows (lce.choose_chunk_rows:
+    chunk_rows V 4 bytes stay under lce.CHUNK_BYTES); per chunk ONE tnn_lce_dlogits launch recomputes the scores and writes dz
+    into a scratch buffer [chunk_rows, V] from the array pool, and tnn_gemm makes dh[chunk] = dz w^T, dw (+)= h[chunk]^T dz and
+    db (+)= 1^T dz, with beta = 1 from the second chunk on — a pure function of the extents and chunk_rows.  Inside a graph
+    capture the scratch belongs to the graph, like wq_linear's workspace.  Composed: cross_entropy_bwd over whole logits and
+    three products."""
+    what = "linear_cross_entropy_bwd"
+    plan, dt, h, w, b, tg, host = _lce_operands(what, h, w, b, targets, ignore_index, reduction, route, chunk_rows=chunk_rows)
+    need_db = need_db and b is not None
+    if not (need_dh or need_dw or need_db):
+        return None, None, None
+    g = asarray(g)
+    if g.size != 1:
+        raise ValueError("%s: the loss is a scalar, got a gradient of shape %s" % (what, tuple(g.shape)))
+    lse = asarray(lse)._as_float(dt)._contig()
+    if lse.size != plan.M:
+        raise ValueError("%s: lse must hold M = %d elements, got shape %s" % (what, plan.M, tuple(lse.shape)))
+    h_shape = plan.rows_shape + (plan.K,)
+    if plan.route != "native":
+        z = _lce_logits(plan, h, w, b)
+        dz = cross_entropy_bwd(z, tg.reshape(plan.M) if host is None else host.reshape(plan.M), lse.reshape(plan.M), count, g,
+                               ignore_index=ignore_index, reduction=reduction)
+        return (matmul(dz, w.T).reshape(h_shape) if need_dh else None, matmul(h.T, dz) if need_dw else None,
+                dz.sum(axis=0).reshape(b.shape) if need_db else None)
+    gd, cd = g.astype(dt)._contig(), asarray(count).astype(dt)._contig()
+    dh = _dest(need_dh, dh_out, h_shape, dt)
+    dw = _dest(need_dw, dw_out, (plan.K, plan.V), dt)
+    db = _dest(need_db, db_out, b.shape if need_db else None, dt)
+    lib, code, K, V = _lib.get(), _CODE[dt], plan.K, plan.V
+    dz = DeviceArray._new((plan.chunk_elements(),), dt)
+    one = ones((min(plan.chunk_rows, plan.M),), dt) if need_db else None
+    for n, (m0, rows) in enumerate(plan.chunks()):
+        beta = 0.0 if n == 0 else 1.0
+        lib.lce_dlogits(h._ptr, K, w._ptr, V, _ptr_of(b), tg._ptr, lse._ptr, cd._ptr, gd._ptr, dz._ptr, m0, rows, plan.M, K, V,
+                        plan.ignore_index, _tk.REDUCTION_CODE[reduction], code)
+        if need_dh:           # dh[chunk] = dz w^T
+            lib.gemm(0, 1, rows, K, V, 1.0, dz._ptr, V, w._ptr, V, 0.0, dh._ptr + m0 * K * 4, K, code)
+        if need_dw:           # dw (+)= h[chunk]^T dz
+            lib.gemm(1, 0, K, V, rows, 1.0, h._ptr + m0 * K * 4, K, dz._ptr, V, beta, dw._ptr, V, code)
+        if need_db:           # db (+)= 1^T dz
+            lib.gemm(0, 0, 1, V, rows, 1.0, one._ptr, rows, dz._ptr, V, beta, db._ptr, V, code)
+    return dh, dw, db
 
 
 # ---------------------------------------------------------------------- kernels: cache-extending attention (csrc/tnn_extend.hip)

@@ -40,6 +40,12 @@ baseline, right for this causal model and wasteful.  The live tokens per second 
 clipping by the global gradient norm (--clip MAX_NORM, 0 = none) and a linear warm-up over --warmup steps followed by a cosine
 decay to zero at the last step, all resident on the device (include/tnn_ostep.h).  Without --adamw the run and its launch
 sequence are what they were.
+
+--fused-head: the head and the loss as ONE node — training runs model.forward(x, hidden=True), which stops in front of the last
+Dense, and losses.LinearCrossEntropyLoss(head), which computes the loss from those activations and the head's parameters
+without ever writing the logits [B T, vocab] or their gradient (ops.linear_cross_entropy_, csrc/tnn_lce.hip: at a real
+vocabulary they are the largest arrays of a step).  The head stays in the net: evaluation and generation use its logits as
+before.  Default off: the run is what it was.
 """
 
 import argparse
@@ -58,7 +64,7 @@ from tinynn_autograd_amd.rope import Rotary                                     
 from tinynn_autograd_amd.core import ops                                                    # noqa: E402
 from tinynn_autograd_amd.generation import KVCache, generate                                # noqa: E402
 from tinynn_autograd_amd.core.layers import Dense, Embedding, Layer, LayerNorm, TransformerBlock  # noqa: E402
-from tinynn_autograd_amd.core.losses import CrossEntropyLoss                                # noqa: E402
+from tinynn_autograd_amd.core.losses import CrossEntropyLoss, LinearCrossEntropyLoss        # noqa: E402
 from tinynn_autograd_amd.core.model import Model                                            # noqa: E402
 from tinynn_autograd_amd.core.nn import Net                                                 # noqa: E402
 from tinynn_autograd_amd.core.optimizer import Adam, AdamW                                  # noqa: E402
@@ -105,7 +111,11 @@ def build(args):
                                 rope=rotary, mlp=mlp),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     # --ragged-train: the targets at dead positions carry this index and count for nothing
-    loss_layer = CrossEntropyLoss(ignore_index=IGNORE if getattr(args, "ragged_train", False) else None, fused=fused)
+    ignore = IGNORE if getattr(args, "ragged_train", False) else None
+    if getattr(args, "fused_head", False):                # the loss takes over the last Dense: no logits in training
+        loss_layer = LinearCrossEntropyLoss(net.layers[-1], ignore_index=ignore, fused=fused)
+    else:
+        loss_layer = CrossEntropyLoss(ignore_index=ignore, fused=fused)
     return Model(net=net, loss=loss_layer, optimizer=make_optimizer(args)), loss_layer
 
 
@@ -143,7 +153,10 @@ def main(args):
                 if not getattr(args, "no_lens", False):
                     lens = da.lengths(host)                 # uploaded once per batch; every attention node reads it on the device
             model.zero_grad()
-            loss = loss_layer.loss(model.forward(x, lens=lens), y.reshape(-1))
+            if getattr(args, "fused_head", False):
+                loss = loss_layer.loss(model.forward(x, lens=lens, hidden=True), y.reshape(-1))
+            else:
+                loss = loss_layer.loss(model.forward(x, lens=lens), y.reshape(-1))
             loss.backward()
             model.step()
             losses.append(loss)
@@ -260,6 +273,9 @@ def parse(argv=None):
                              "beyond it ignored by the loss, the lengths handed to the model (model.forward(x, lens=))")
     parser.add_argument("--no-lens", dest="no_lens", action="store_true",
                         help="--ragged-train: keep the lengths from the model (the padded baseline; right for a causal model, wasteful)")
+    parser.add_argument("--fused-head", dest="fused_head", action="store_true",
+                        help="train through model.forward(x, hidden=True) and LinearCrossEntropyLoss: the head and the loss as "
+                             "one node that never writes the logits")
     parser.add_argument("--composed", action="store_true", help="fused=False: every part on its composed route")
     parser.add_argument("--adamw", action="store_true", help="AdamW on the device instead of Adam")
     parser.add_argument("--weight_decay", default=0.01, type=float, help="--adamw: decoupled weight decay")
