@@ -69,6 +69,7 @@ from . import varlen
 from . import kvq
 from . import wq
 from . import lce
+from . import swa
 from . import rope
 from .rope import Rotary
 from .fused import MLPTrainer, trainer_from_net

@@ -103,6 +103,10 @@ from ._lce_signatures import _LCE_SIGNATURES                  # noqa: E402  (inc
 
 LCE_SYMBOLS = sorted(_LCE_SIGNATURES)
 
+from ._swa_signatures import _SWA_SIGNATURES                  # noqa: E402  (include/tnn_swa.h: libtnn_hip.so only)
+
+SWA_SYMBOLS = sorted(_SWA_SIGNATURES)
+
 
 class TnnError(RuntimeError):
     """A native call returned non-zero; the message is tnn_last_error()."""
@@ -186,6 +190,8 @@ class _Lib(object):
         # host with wq.py's numpy statement of the format and runs the ordinary product over the dequantized weight
         # and the fused linear + cross-entropy (include/tnn_lce.h): under the twin device_array runs the dense product and the
         # per-row cross-entropy over whole logits (lce.py: the composed route)
+        # and sliding-window training attention (include/tnn_swa.h): under the twin device_array runs the composed attention
+        # with the band mask built on the host (swa.py)
         for table, header, what in ((_INDEX_SIGNATURES, "tnn_index.h", "advanced indexing"),
                                     (_BMM_SIGNATURES, "tnn_bmm.h", "batched matmul"),
                                     (_CONV_SIGNATURES, "tnn_conv.h", "convolution"),
@@ -203,7 +209,8 @@ class _Lib(object):
                                     (_VARLEN_SIGNATURES, "tnn_varlen.h", "attention with per-sequence lengths"),
                                     (_KVQ_SIGNATURES, "tnn_kvq.h", "int8 key / value cache"),
                                     (_WQ_SIGNATURES, "tnn_wq.h", "int8 weight-only linear"),
-                                    (_LCE_SIGNATURES, "tnn_lce.h", "fused linear + cross-entropy")):
+                                    (_LCE_SIGNATURES, "tnn_lce.h", "fused linear + cross-entropy"),
+                                    (_SWA_SIGNATURES, "tnn_swa.h", "sliding-window attention")):
             for name, argtypes in table.items():
                 fn = getattr(self.cdll, name, None)
                 if fn is None:
@@ -231,6 +238,7 @@ class _Lib(object):
         self.has_kvq = hasattr(self.cdll, "tnn_kvq_decode_attn")
         self.has_wq = hasattr(self.cdll, "tnn_wq_linear")
         self.has_lce = hasattr(self.cdll, "tnn_lce_fwd")
+        self.has_swa = hasattr(self.cdll, "tnn_swa_fwd")
 
     @staticmethod
     def _absent(name, what):

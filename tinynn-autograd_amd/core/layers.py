@@ -224,12 +224,26 @@ class MultiHeadAttention(Layer):
     projections and before the attention op; v is never rotated and the key stored in a cache is the rotated one.  Positions:
     0 .. T - 1 without a cache and in the prefill, cache.length in a uniform decoding step, cache.lens — read on the device —
     in a ragged one.  Positions beyond rope.max_len raise before any launch.  None (the default): no rotation, the layer as it
-    was, launch for launch."""
+    was, launch for launch.
+
+    window (sliding-window attention; needs causal=True): position i attends to positions i - window + 1 .. i.  Training
+    passes it to the attention op (ops.attention_ / ops.attention_gqa_ with window=: the tnn_swa_* launches, O(T window)).
+    With a cache the prefill runs the windowed op and the cache becomes a RING of R = window slots (LayerCache.set_ring, ONE
+    tnn_swa_fill launch); every later step runs ops.attention_decode_swa_ at cache.length, or at cache.lens when ragged — the
+    ring never fills, so prompt plus new tokens may exceed the window (the position limits of the Embedding and the rotary
+    tables still apply).  A window with lens=, with an int8 cache or with extend=True / prefill_chunk raises ValueError before
+    any launch.  None (the default): the layer as it was, launch for launch."""
 
     def __init__(self, num_heads, num_in=None, causal=False, w_init=XavierUniformInit(), b_init=ZerosInit(), fused=True,
-                 kv_heads=None, rope=None):
+                 kv_heads=None, rope=None, window=None):
         super().__init__("MultiHeadAttention")
         self.rope = rope
+        if window is not None:
+            from ..swa import check_window
+            window = check_window(window, "MultiHeadAttention")
+            if not causal:
+                raise ValueError("MultiHeadAttention: window= needs causal=True")
+        self.window = window
         num_heads = int(num_heads)
         if num_heads < 1:
             raise ValueError("MultiHeadAttention: num_heads must be >= 1, got %r" % (num_heads,))
@@ -280,6 +294,10 @@ class MultiHeadAttention(Layer):
         if lens is not None and cache is not None:
             raise ValueError("MultiHeadAttention: lens= (training over a padded batch) and cache= (generation) do not go "
                              "together; a ragged generation batch keeps its lengths in the cache")
+        if self.window is not None and lens is not None:
+            raise ValueError("MultiHeadAttention: window= with lens= (a padded batch) is out of scope")
+        if self.window is not None and cache is not None:
+            cache.set_ring(self.window)                  # raises for an int8 or an extending cache
         b, t, e = (int(s) for s in inputs.shape)
         if not self.is_init:
             self._init_parameters(e)
@@ -313,7 +331,10 @@ class MultiHeadAttention(Layer):
                 q, k = ops.rope_(ops.reshape(q, (b, 1, h, e // h)), ops.reshape(k, (b, 1, hk, e // h)), rotary=self.rope,
                                  route=route, **where)
                 q, k = ops.reshape(q, (b, h, e // h)), ops.reshape(k, (b, hk, e // h))
-            if getattr(cache, "quant", None) is not None:        # an int8 cache: plain, grouped, uniform and ragged in ONE op
+            if self.window is not None:                          # a ring: plain, grouped, uniform and ragged in ONE op
+                where = (dict(lens=cache.lens) if getattr(cache, "lens", None) is not None else dict(pos=cache.length))
+                att = ops.attention_decode_swa_(q, cache.k, cache.v, k, v, route=route, **where)
+            elif getattr(cache, "quant", None) is not None:      # an int8 cache: plain, grouped, uniform and ragged in ONE op
                 where = (dict(lens=cache.lens) if getattr(cache, "lens", None) is not None else dict(length=cache.length))
                 att = ops.attention_decode_kvq_(q, cache.k, cache.v, cache.k_scale, cache.v_scale, k_new=k, v_new=v,
                                                 layout="bthd", route=route, **where)
@@ -330,11 +351,11 @@ class MultiHeadAttention(Layer):
             if self.rope is not None:
                 q, k = ops.rope_(q, k, rotary=self.rope, route=route)
             if grouped:
-                att = ops.attention_gqa_(q, k, v, causal=self.causal, route=route, lens=lens)
+                att = ops.attention_gqa_(q, k, v, causal=self.causal, route=route, lens=lens, window=self.window)
             else:
-                att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route, lens=lens)
+                att = ops.attention_(q, k, v, causal=self.causal, layout="bthd", route=route, lens=lens, window=self.window)
             if cache is not None:
-                if getattr(cache, "quant", None) is not None:
+                if getattr(cache, "quant", None) is not None or self.window is not None:
                     cache.fill(k.values, v.values, route=route)
                 else:
                     cache.fill(k.values, v.values)
@@ -480,7 +501,8 @@ class TransformerBlock(Layer):
     form of ops.dropout_ — its launch REPLACES the block's residual add — drawing from `generator` (None: the default
     generator of rng.py).  With dropout == 0 (the default) and in the TEST phase the block runs exactly its launches without
     the argument.  kv_heads: handed to the attention part (grouped-query attention; None: multi-head, as it was).  rope: a
-    rope.Rotary handed to the attention part (rotary position embedding of q and k; None: no rotation, as it was).
+    rope.Rotary handed to the attention part (rotary position embedding of q and k; None: no rotation, as it was).  window:
+    handed to the attention part (sliding-window attention in training; None: as it was).
 
     mlp: "gelu" (the default) is the feed-forward above, launch for launch as it was.  "swiglu" / "geglu" is the GATED form
 
@@ -493,8 +515,14 @@ class TransformerBlock(Layer):
     for the gated forms (gated.gated_hidden), which keeps the parameter count about the same."""
 
     def __init__(self, num_heads, hidden=None, num_in=None, causal=False, eps=1e-5, fused=True, dropout=0.0, generator=None,
-                 kv_heads=None, rope=None, mlp="gelu"):
+                 kv_heads=None, rope=None, mlp="gelu", window=None):
         super().__init__("TransformerBlock")
+        if window is not None:
+            from ..swa import check_window
+            window = check_window(window, "TransformerBlock")
+            if not causal:
+                raise ValueError("TransformerBlock: window= needs causal=True")
+        self.window = window
         if mlp not in MLP_FORMS:
             raise ValueError("TransformerBlock: mlp must be one of %s, got %r" % (sorted(MLP_FORMS), mlp))
         self.mlp = mlp
@@ -526,7 +554,7 @@ class TransformerBlock(Layer):
         parts = {}
         parts["ln1"] = LayerNorm(width, eps=self.eps, fused=self.fused)
         parts["attn"] = MultiHeadAttention(self.num_heads, num_in=width, causal=self.causal, fused=self.fused,
-                                           kv_heads=self.kv_heads, rope=self.rope)
+                                           kv_heads=self.kv_heads, rope=self.rope, window=self.window)
         parts["ln2"] = LayerNorm(width, eps=self.eps, fused=self.fused)
         parts["fc1"] = Dense(2 * hidden if gate else hidden, num_in=width, fused=self.fused)
         parts["fc2"] = Dense(width, num_in=hidden, fused=self.fused)

@@ -647,6 +647,11 @@ def _lens_opt(lens):
     return {} if lens is None else {"lens": _raw_values(lens)}
 
 
+def _window_opt(window):
+    """window= as an option of the node (saved for the vjps); None: the options, and so the launches, are today's."""
+    return {} if window is None else {"window": window}
+
+
 def _attn_node(q, k, v, fwd, bwd_q, bwd_kv, **opts):
     """The node of attention_ / attention_gqa_: `fwd` with the options, and an _AttnVjp that hands them to the backward."""
     out, lse = fwd(q.values, k.values, v.values, **opts)
@@ -657,7 +662,7 @@ def _attn_node(q, k, v, fwd, bwd_q, bwd_kv, **opts):
     return node
 
 
-def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, lens=None, **unknown):
+def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, lens=None, window=None, **unknown):
     """Scaled-dot-product attention node: softmax(scale q k^T) v, softmax over the key axis, scale = 1 / sqrt(D) by default.
 
     layout "bhtd": q [..., Tq, D], k [..., Tk, D], v [..., Tk, Dv] -> [..., Tq, Dv] (identical leading dimensions, no
@@ -673,6 +678,12 @@ def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, len
     and padding is never read.  A host sequence raises TypeError; a Lengths with a value outside [0, T] raises before any
     launch.  The composed route masks on the host (varlen.py).
 
+    window (an integer >= 1; needs causal=True and Tq == Tk, and raises ValueError together with lens): sliding-window
+    attention, query i keeps key j iff i - window < j <= i.  Forward and both backward launches are then tnn_swa_*
+    (include/tnn_swa.h, float32): they walk only the 64 x 64 blocks of the band, O(T window), and for window >= T give the
+    bits of the causal launches.  float64, the CPU test twin and route="composed" (or device_array.SWA_ROUTE) run the composed
+    attention with the band mask built on the host (swa.py).  window=None is the path without it, launch for launch.
+
     Forward is ONE tnn_attn_fwd launch (online softmax on MFMA; the [Tq, Tk] scores never reach memory) that also keeps the
     per-row log-sum-exp.  Backward recomputes the probabilities from it: dq from one launch (not computed when q does not
     require a gradient), dk + dv from one launch.  Under the CPU test twin, beyond head dimension 128 and with
@@ -680,10 +691,10 @@ def attention_(q, k, v, causal=False, scale=None, layout="bhtd", route=None, len
     if unknown:
         raise TypeError("attention_: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
     return _attn_node(q, k, v, da.attention, da.attention_bwd_q, da.attention_bwd_kv, causal=causal, scale=scale, layout=layout,
-                      route=route, **_lens_opt(lens))
+                      route=route, **_lens_opt(lens), **_window_opt(window))
 
 
-def attention_gqa_(q, k, v, causal=False, scale=None, route=None, lens=None, **unknown):
+def attention_gqa_(q, k, v, causal=False, scale=None, route=None, lens=None, window=None, **unknown):
     """Grouped-query attention node, layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] -> [B, Tq, H, Dv]
     with H a multiple of Hkv; query head h attends over key / value head h // (H / Hkv).  Hkv == 1 is multi-query attention,
     Hkv == H gives attention_'s result bit for bit.  The causal rule, the scale and the dtypes are attention_'s.
@@ -693,13 +704,14 @@ def attention_gqa_(q, k, v, causal=False, scale=None, route=None, lens=None, **u
     dk and dv are written once, in the shapes of k and v), into lent arena views when there are any.  Under the CPU test
     twin, with route="composed" (or device_array.GQA_ROUTE), beyond head dimension 128 and for groups above 8, k and v are
     repeated over the group, the composed attention runs and dk / dv are summed over the group axis.  lens: per-sequence
-    lengths of a right-padded batch, as attention_ (the same tnn_varlen_* launches, with the group).  Out of scope: masks,
+    lengths of a right-padded batch, as attention_ (the same tnn_varlen_* launches, with the group).  window: a sliding
+    window, as attention_ (the same tnn_swa_* launches, with the group).  Out of scope: masks,
     dropout, bf16, other layouts — unknown keyword arguments raise."""
     if unknown:
         raise TypeError("attention_gqa_: unsupported arguments %s (masks, dropout, bf16 and other layouts than \"bthd\" are out "
                         "of scope)" % sorted(unknown))
     return _attn_node(q, k, v, da.gqa_attention, da.gqa_attention_bwd_q, da.gqa_attention_bwd_kv, causal=causal, scale=scale,
-                      route=route, **_lens_opt(lens))
+                      route=route, **_lens_opt(lens), **_window_opt(window))
 
 
 def rope_(q, k=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, route=None, **unknown):
@@ -1061,6 +1073,20 @@ def attention_decode_kvq_(q, k_codes, v_codes, k_scales, v_scales, length=None, 
                                   _raw_values(v_scales), length, None if k_new is None else k_new.values,
                                   None if v_new is None else v_new.values, None if lens is None else _raw_values(lens),
                                   scale=scale, layout=layout, route=route, splits=splits)
+    return q.__class__(out, False, [])
+
+
+def attention_decode_swa_(q, k_ring, v_ring, k_new, v_new, pos=None, lens=None, scale=None, route=None, splits=None, **unknown):
+    """One decoding step of sliding-window attention over a RING of R = window slots, INFERENCE ONLY (no vjp): q [B, H, D],
+    k_new [B, Hkv, D], v_new [B, Hkv, Dv], k_ring [B, R, Hkv, D], v_ring [B, R, Hkv, Dv] (device arrays or tensors, written in
+    place).  The step sits at position pos (a host integer) or lens[b] (a ragged.Lengths or a dense int64 device array, read on
+    the device): its row goes to slot p mod R and the query attends over the min(p + 1, R) live slots — the ring never fills
+    and a step reads a bounded number of bytes.  ONE tnn_swa_decode_attn call (float32); device_array.attention_decode_swa
+    states the composed route.  Unknown keyword arguments raise."""
+    if unknown:
+        raise TypeError("attention_decode_swa_: unsupported arguments %s" % sorted(unknown))
+    out = da.attention_decode_swa(q.values, _raw_values(k_ring), _raw_values(v_ring), k_new.values, v_new.values, pos=pos,
+                                  lens=None if lens is None else _raw_values(lens), scale=scale, route=route, splits=splits)
     return q.__class__(out, False, [])
 
 
@@ -1445,11 +1471,12 @@ def max_pool2d(obj, kernel, stride=None, padding=0):
     return max_pool2d_(as_tensor(obj), kernel, stride=stride, padding=padding)
 
 
-def attention(obj, k, v, causal=False, scale=None, layout="bhtd", lens=None, **unknown):
+def attention(obj, k, v, causal=False, scale=None, layout="bhtd", lens=None, window=None, **unknown):
     """not in the reference: see attention_ (masks, dropout and bf16 are out of scope: unknown keyword arguments raise)"""
     if unknown:
         raise TypeError("attention: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
-    return attention_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, layout=layout, lens=lens)
+    return attention_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, layout=layout, lens=lens,
+                      window=window)
 
 
 def _opt_tensor(obj):
@@ -1520,11 +1547,11 @@ def cross_entropy(obj, targets, ignore_index=None, reduction="mean", **unknown):
     return cross_entropy_(as_tensor(obj), targets, ignore_index=ignore_index, reduction=reduction)
 
 
-def attention_gqa(obj, k, v, causal=False, scale=None, lens=None, **unknown):
+def attention_gqa(obj, k, v, causal=False, scale=None, lens=None, window=None, **unknown):
     """not in the reference: see attention_gqa_ (grouped-query heads, layout "bthd"; unknown keyword arguments raise)"""
     if unknown:
         raise TypeError("attention_gqa: unsupported arguments %s (masks, dropout and bf16 are out of scope)" % sorted(unknown))
-    return attention_gqa_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, lens=lens)
+    return attention_gqa_(as_tensor(obj), as_tensor(k), as_tensor(v), causal=causal, scale=scale, lens=lens, window=window)
 
 
 def rope(obj, k=None, rotary=None, offset=0, positions=None, layout="bthd", inverse=False, **unknown):

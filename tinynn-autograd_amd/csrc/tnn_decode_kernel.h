@@ -76,6 +76,14 @@ struct GroupedRaggedArgs : RaggedArgs {
     int nq;
 };
 
+// a record that declares RING = true (csrc/tnn_swa.hip: a ring of Tmax slots) takes its position p from lens[b], or from the
+// host field `pos` when lens is NULL, writes the step's row to slot p mod Tmax and attends over the min(p + 1, Tmax) live
+// slots; every other record compiles the test away
+template <typename A, typename = void>
+struct is_ring { static constexpr bool value = false; };
+template <typename A>
+struct is_ring<A, decltype((void)A::RING)> { static constexpr bool value = A::RING; };
+
 template <typename A>
 __device__ __forceinline__ int live_queries(const A& a) {
     if constexpr (A::GROUPED) return a.nq;
@@ -109,8 +117,9 @@ __device__ __forceinline__ void decode_body(const A& a) {
 
     int64_t nkeys, len, chunks;
     if constexpr (A::RAGGED) {
-        len = a.lens[b];                                       // the ONE load that the ragged form adds
-        if (len < 0 || len >= a.Tmax) {                        // (workgroup-uniform) no such row: zeros, the caches untouched
+        if constexpr (is_ring<A>::value) len = a.lens != nullptr ? a.lens[b] : a.pos;
+        else len = a.lens[b];                                  // the ONE load that the ragged form adds
+        if (len < 0 || (!is_ring<A>::value && len >= a.Tmax)) {        // (workgroup-uniform) no such row: zeros, the caches untouched
 #pragma unroll
             for (int x = 0; x < Q; ++x) {
                 if (x >= nq) break;
@@ -123,6 +132,10 @@ __device__ __forceinline__ void decode_body(const A& a) {
             return;
         }
         nkeys = len + 1;
+        if constexpr (is_ring<A>::value) {                     // the ring has wrapped: every slot is live, the row goes to p mod Tmax
+            if (nkeys > a.Tmax) nkeys = a.Tmax;
+            len %= a.Tmax;
+        }
         chunks = (nkeys + CHUNK - 1) / CHUNK;
     } else {
         nkeys = a.nkeys; len = a.len; chunks = a.chunks;

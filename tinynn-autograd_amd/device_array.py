@@ -41,6 +41,7 @@ from . import lce as _lc
 from . import norm as _nm
 from . import ragged as _rg
 from . import rope as _rp
+from . import swa as _sw
 from . import tokens as _tk
 from . import varlen as _vl
 from . import wq as _wq
@@ -1489,12 +1490,42 @@ class _Varlen(object):
         return (asarray(_vl.key_mask(host, plan.T, plan.H, dt), dtype=dt), asarray(_vl.row_mask(host, plan.T, plan.H, dt), dtype=dt))
 
 
-def _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens):
-    """(plan, varlen state or None) of one call."""
+SWA_ROUTE = None      # tests / probes: "native" or "composed" overrides the planner's choice when window= is given (swa.py)
+
+
+class _Swa(object):
+    """What window= adds to one call of _attn_fwd / _attn_bwd_q / _attn_bwd_kv: the plan of swa.py and, on the composed route,
+    the additive band mask built on the host."""
+    __slots__ = ("plan",)
+
+    def __init__(self, form, q, k, v, window, causal, scale, layout, route, dt):
+        self.plan = _sw.plan_swa(q.shape, k.shape, v.shape, window, causal, scale, layout, grouped=form.fold,
+                                 native=_lib.get().has_swa, float_ok=dt == np.float32, route=route or SWA_ROUTE)
+
+    def native(self, entry, ptrs, strides):
+        """ONE call of a tnn_swa_* entry point."""
+        plan = self.plan
+        getattr(_lib.get(), entry)(*(ptrs + plan.geometry() + (_i64arr(strides), plan.scale, plan.window, plan.group)))
+
+    def mask(self, dt):
+        """[T, T] additive mask of the composed route: 0 inside the band, -inf outside."""
+        if _lib.capturing:
+            raise RuntimeError("%s (composed route): the band mask of window= is built on the host and uploaded, which a "
+                               "graph capture cannot do" % (self.plan.grouped and "gqa_attention" or "attention"))
+        return asarray(np.where(_sw.band_mask(self.plan.T, self.plan.window), 0.0, -np.inf).astype(dt), dtype=dt)
+
+
+def _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens, window=None, dt=None):
+    """(plan, varlen state or None, window state or None) of one call."""
+    if window is not None:
+        if lens is not None:
+            raise ValueError("%s: window= together with lens= is out of scope (a padded batch with a window)" % form.what)
+        sw = _Swa(form, q, k, v, window, causal, scale, layout, route, dt)
+        return sw.plan, None, sw
     if lens is None:
-        return form.plan(q, k, v, causal, scale, layout, route), None
+        return form.plan(q, k, v, causal, scale, layout, route), None, None
     vl = _Varlen(form, q, k, v, lens, causal, scale, layout, route)
-    return vl.plan, vl
+    return vl.plan, vl, None
 
 
 def _zeroed(x3, rows):
@@ -1502,18 +1533,23 @@ def _zeroed(x3, rows):
     return x3 * rows + 0.0
 
 
-def _attn_fwd(form, q, k, v, causal, scale, layout, route, lens=None):
-    """attention / gqa_attention.  Native: ONE call of the form's forward entry point (with lens=: of tnn_varlen_fwd).
-    Composed: k and v repeated over the plan's group (1 for the plain form: nothing is repeated), two batched products,
-    max-subtract, exp, sum, divide; with lens= the key mask joins the scores and the row mask zeroes the dead rows."""
+def _attn_fwd(form, q, k, v, causal, scale, layout, route, lens=None, window=None):
+    """attention / gqa_attention.  Native: ONE call of the form's forward entry point (with lens=: of tnn_varlen_fwd; with
+    window=: of tnn_swa_fwd).  Composed: k and v repeated over the plan's group (1 for the plain form: nothing is repeated),
+    two batched products, max-subtract, exp, sum, divide; with lens= the key mask joins the scores and the row mask zeroes the
+    dead rows; with window= the band mask joins the scores."""
     dt, (q, k, v) = _operands(q, k, v)
-    plan, vl = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens)
+    plan, vl, sw = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens, window, dt)
     if plan.empty():
         return zeros(plan.out_shape, dt), zeros(plan.lse_shape, dt)
     if plan.route == "native":
         out = DeviceArray._new(plan.out_shape, dt)
         lse = DeviceArray._new(plan.lse_shape, dt)
-        args = (q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr) + tuple(plan.geometry()) + (
+        ptrs = (q._ptr, k._ptr, v._ptr, out._ptr, lse._ptr)
+        if sw is not None:
+            sw.native("swa_fwd", ptrs, plan.strides("q", "k", "v", "o"))
+            return out, lse
+        args = ptrs + tuple(plan.geometry()) + (
             _i64arr(plan.strides("q", "k", "v", "o")), plan.scale, int(plan.causal), out._code())
         if vl is None:
             getattr(_lib.get(), form.fwd)(*args)
@@ -1522,6 +1558,8 @@ def _attn_fwd(form, q, k, v, causal, scale, layout, route, lens=None):
         return out, lse
     k, v = _gqa_expand(k, plan.group), _gqa_expand(v, plan.group)
     s = _attn_scores(q, k, plan)
+    if sw is not None:
+        s = s + sw.mask(s.dtype)
     if vl is not None:
         keys, rows = vl.masks(s.dtype)
         s = s + keys
@@ -1535,11 +1573,11 @@ def _attn_fwd(form, q, k, v, causal, scale, layout, route, lens=None):
     return _attn_from3(o3, plan, plan.Tq, plan.Dv), lse.reshape(plan.lse_shape)
 
 
-def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out, lens=None):
+def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out, lens=None, window=None):
     """attention_bwd_q / gqa_attention_bwd_q.  Native: ONE call of the form's backward-q entry point; dq_out is used when it
     has exactly q's shape.  Composed: as _attn_fwd, on the repeated k and v."""
     dt, (q, k, v, o, do, lse) = _operands(q, k, v, o, do, lse)
-    plan, vl = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens)
+    plan, vl, sw = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens, window, dt)
     if tuple(o.shape) != plan.out_shape or tuple(lse.shape) != plan.lse_shape:
         raise ValueError("%s_bwd_q: do / o %s and lse %s do not match the output %s and row statistics %s of this attention"
                          % (form.what, tuple(o.shape), tuple(lse.shape), plan.out_shape, plan.lse_shape))
@@ -1550,7 +1588,11 @@ def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq
     if plan.route == "native":
         dq = _dest(need_dq, dq_out, q.shape, dt, exact=True)
         delta = DeviceArray._new(plan.lse_shape, dt)
-        args = (q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, _ptr_of(dq), delta._ptr) + tuple(plan.geometry()) + (
+        ptrs = (q._ptr, k._ptr, v._ptr, o._ptr, do._ptr, lse._ptr, _ptr_of(dq), delta._ptr)
+        if sw is not None:
+            sw.native("swa_bwd_q", ptrs, plan.strides("q", "k", "v", "o", "o", "q"))
+            return dq, delta
+        args = ptrs + tuple(plan.geometry()) + (
             _i64arr(plan.strides("q", "k", "v", "o", "o", "q")), plan.scale, int(plan.causal), delta._code())
         if vl is None:
             getattr(_lib.get(), form.bwd_q)(*args)
@@ -1566,6 +1608,8 @@ def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq
     dq = None
     if need_dq:
         s = _attn_scores(q, k, plan)
+        if sw is not None:
+            s = s + sw.mask(s.dtype)
         if vl is not None:
             s = s + keys
         p = exp(s - lse.reshape(plan.B * plan.H, plan.Tq, 1))
@@ -1577,12 +1621,13 @@ def _attn_bwd_q(form, q, k, v, o, do, lse, causal, scale, layout, route, need_dq
     return dq, delta3.reshape(plan.lse_shape)
 
 
-def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out, lens=None):
+def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out, lens=None,
+                 window=None):
     """attention_bwd_kv / gqa_attention_bwd_kv.  Native: ONE call of the form's backward-kv entry point; dk_out / dv_out are
     used when they have exactly k's / v's shape.  Composed: as _attn_fwd, on the repeated k and v; the grouped form then sums
     dk and dv over the group axis (also for a group of one)."""
     dt, (q, k, v, do, lse, delta) = _operands(q, k, v, do, lse, delta)
-    plan, vl = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens)
+    plan, vl, sw = _attn_call_plan(form, q, k, v, causal, scale, layout, route, lens, window, dt)
     if tuple(lse.shape) != plan.lse_shape or tuple(delta.shape) != plan.lse_shape:
         raise ValueError("%s_bwd_kv: lse %s / delta %s do not match the row statistics %s of this attention"
                          % (form.what, tuple(lse.shape), tuple(delta.shape), plan.lse_shape))
@@ -1594,7 +1639,11 @@ def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, ne
         return (zeros(k.shape, dt) if need_dk else None), (zeros(v.shape, dt) if need_dv else None)
     if plan.route == "native":
         dk, dv = _dest(need_dk, dk_out, k.shape, dt, exact=True), _dest(need_dv, dv_out, v.shape, dt, exact=True)
-        args = (q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, _ptr_of(dk), _ptr_of(dv)) + tuple(plan.geometry()) + (
+        ptrs = (q._ptr, k._ptr, v._ptr, do._ptr, lse._ptr, delta._ptr, _ptr_of(dk), _ptr_of(dv))
+        if sw is not None:
+            sw.native("swa_bwd_kv", ptrs, plan.strides("q", "k", "v", "o", "k", "v"))
+            return dk, dv
+        args = ptrs + tuple(plan.geometry()) + (
             _i64arr(plan.strides("q", "k", "v", "o", "k", "v")), plan.scale, int(plan.causal), lse._code())
         if vl is None:
             getattr(_lib.get(), form.bwd_kv)(*args)
@@ -1605,6 +1654,8 @@ def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, ne
     rows = plan.B * plan.H
     do3 = _attn3(do, plan, plan.Tq, plan.Dv)
     s = _attn_scores(q, k, plan)
+    if sw is not None:
+        s = s + sw.mask(s.dtype)
     if vl is not None:
         keys, live = vl.masks(s.dtype)
         s = s + keys
@@ -1625,32 +1676,35 @@ def _attn_bwd_kv(form, q, k, v, do, lse, delta, causal, scale, layout, route, ne
     return dk, dv
 
 
-def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None, lens=None):
+def attention(q, k, v, causal=False, scale=None, layout="bhtd", route=None, lens=None, window=None):
     """(o, lse): o = softmax(scale q k^T) v over the key axis and the per-row log-sum-exp of the scaled scores (what the
     backward recomputes the probabilities from).  Layouts, the causal rule and the routes: attention.py.  Native: ONE
     tnn_attn_fwd launch, the scores never reach memory; composed: two batched products, max-subtract, exp, sum, divide.
     lens= (a ragged.Lengths or a dense int64 device array [B]; Tq == Tk, layout "bthd" or three-axis "bhtd"): sequence b of a
     right-padded batch has lens[b] live tokens — live rows attend over live keys only, dead rows get o = +0 and lse = 0
-    (varlen.py: the rule, the routes).  Native: ONE tnn_varlen_fwd launch that reads the lengths on the device."""
-    return _attn_fwd(_PLAIN, q, k, v, causal, scale, layout, route, lens)
+    (varlen.py: the rule, the routes).  Native: ONE tnn_varlen_fwd launch that reads the lengths on the device.
+    window= (an integer >= 1; causal=True, Tq == Tk, no lens=): query i keeps key j iff i - window < j <= i (swa.py: the rule,
+    the walk, the routes).  Native (float32): ONE tnn_swa_fwd launch whose work follows the band."""
+    return _attn_fwd(_PLAIN, q, k, v, causal, scale, layout, route, lens, window)
 
 
 def attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, layout="bhtd", route=None, need_dq=True, dq_out=None,
-                    lens=None):
+                    lens=None, window=None):
     """(dq, delta) for the gradient `do` of attention's output: delta[i] = sum_c do[i, c] o[i, c] (what attention_bwd_kv
     reads) and dq = scale dS k with dS = p (dP - delta), dP = do v^T, p recomputed from lse.  need_dq=False: dq is None and
     only delta is produced (native: the key loop is skipped).  dq_out: a dense array the result is written into.  lens=: as
-    attention; dead rows get delta = 0 and dq = +0."""
-    return _attn_bwd_q(_PLAIN, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out, lens)
+    attention; dead rows get delta = 0 and dq = +0.  window=: as attention (tnn_swa_bwd_q)."""
+    return _attn_bwd_q(_PLAIN, q, k, v, o, do, lse, causal, scale, layout, route, need_dq, dq_out, lens, window)
 
 
 def attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, layout="bhtd", route=None, need_dk=True,
-                     need_dv=True, dk_out=None, dv_out=None, lens=None):
+                     need_dv=True, dk_out=None, dv_out=None, lens=None, window=None):
     """(dk, dv): dv = p^T do and dk = scale dS^T q from ONE launch, with the delta attention_bwd_q produced (on the native
     route the launch must follow that call).  need_dk / need_dv = False: that product is skipped and None returned.  A key
     that no query sees (causal, Tk > Tq) gets exact zeros.  dk_out / dv_out: dense arrays the results are written into.
-    lens=: as attention; dead keys get dk = dv = +0."""
-    return _attn_bwd_kv(_PLAIN, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out, lens)
+    lens=: as attention; dead keys get dk = dv = +0.  window=: as attention (tnn_swa_bwd_kv)."""
+    return _attn_bwd_kv(_PLAIN, q, k, v, do, lse, delta, causal, scale, layout, route, need_dk, need_dv, dk_out, dv_out, lens,
+                        window)
 
 
 # ---------------------------------------------------------------------- kernels: layer norm, RMS norm, GELU (csrc/tnn_norm.hip)
@@ -2346,27 +2400,154 @@ _GROUPED = _AttnForm(lambda q, k, v, causal, scale, layout, route: _gqa_plan(q, 
                      "gqa_fwd", "gqa_bwd_q", "gqa_bwd_kv", "gqa_attention", True)
 
 
-def gqa_attention(q, k, v, causal=False, scale=None, route=None, lens=None):
+def gqa_attention(q, k, v, causal=False, scale=None, route=None, lens=None, window=None):
     """(o, lse) of grouped-query attention in layout "bthd": q [B, Tq, H, D], k [B, Tk, Hkv, D], v [B, Tk, Hkv, Dv] ->
     o [B, Tq, H, Dv], lse [B, H, Tq]; query head h reads key / value head h // (H / Hkv) (gqa.py: the checks, the routes).
     Native: ONE tnn_gqa_fwd launch, k and v are never expanded; composed: k and v repeated over the group, then attention()
-    on its composed route.  lens=: per-sequence lengths of a right-padded batch, as attention (ONE tnn_varlen_fwd launch)."""
-    return _attn_fwd(_GROUPED, q, k, v, causal, scale, "bthd", route, lens)
+    on its composed route.  lens=: per-sequence lengths of a right-padded batch, as attention (ONE tnn_varlen_fwd launch).
+    window=: a sliding window, as attention (ONE tnn_swa_fwd launch with the group)."""
+    return _attn_fwd(_GROUPED, q, k, v, causal, scale, "bthd", route, lens, window)
 
 
-def gqa_attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, route=None, need_dq=True, dq_out=None, lens=None):
+def gqa_attention_bwd_q(q, k, v, o, do, lse, causal=False, scale=None, route=None, need_dq=True, dq_out=None, lens=None,
+                        window=None):
     """(dq, delta) of gqa_attention, as attention_bwd_q: delta [B, H, Tq] is what gqa_attention_bwd_kv reads; need_dq=False:
-    only delta.  Native: ONE tnn_gqa_bwd_q launch (lens=: tnn_varlen_bwd_q)."""
-    return _attn_bwd_q(_GROUPED, q, k, v, o, do, lse, causal, scale, "bthd", route, need_dq, dq_out, lens)
+    only delta.  Native: ONE tnn_gqa_bwd_q launch (lens=: tnn_varlen_bwd_q; window=: tnn_swa_bwd_q)."""
+    return _attn_bwd_q(_GROUPED, q, k, v, o, do, lse, causal, scale, "bthd", route, need_dq, dq_out, lens, window)
 
 
 def gqa_attention_bwd_kv(q, k, v, do, lse, delta, causal=False, scale=None, route=None, need_dk=True, need_dv=True,
-                         dk_out=None, dv_out=None, lens=None):
+                         dk_out=None, dv_out=None, lens=None, window=None):
     """(dk, dv) of gqa_attention with the shapes of k and v: the sums over every key / value head's group of query heads.
     Native: ONE tnn_gqa_bwd_kv launch (it must follow gqa_attention_bwd_q on the stream: it reads that call's delta) — one
     workgroup per (b, key / value head, key block) adds the group's heads in ascending order and writes once.  Composed:
-    attention_bwd_kv on k and v repeated over the group, then a sum over the group axis.  lens=: tnn_varlen_bwd_kv."""
-    return _attn_bwd_kv(_GROUPED, q, k, v, do, lse, delta, causal, scale, "bthd", route, need_dk, need_dv, dk_out, dv_out, lens)
+    attention_bwd_kv on k and v repeated over the group, then a sum over the group axis.  lens=: tnn_varlen_bwd_kv;
+    window=: tnn_swa_bwd_kv."""
+    return _attn_bwd_kv(_GROUPED, q, k, v, do, lse, delta, causal, scale, "bthd", route, need_dk, need_dv, dk_out, dv_out, lens,
+                        window)
+
+
+
+# ---------------------------------------------------------------------- kernels: sliding-window attention (csrc/tnn_swa.hip)
+def _swa_form(q, k, layout):
+    """The grouped form when k holds fewer heads than q (layout "bthd"), else the plain one."""
+    grouped = layout == "bthd" and len(q.shape) == 4 and len(k.shape) == 4 and q.shape[2] != k.shape[2]
+    return _GROUPED if grouped else _PLAIN
+
+
+def attention_swa(q, k, v, window, scale=None, layout="bthd", route=None):
+    """(o, lse) of causal self-attention in which query i keeps key j iff i - window < j <= i (swa.py).  Plain heads in either
+    layout; grouped-query heads (k and v with H / group heads) in layout "bthd".  Native (float32): ONE tnn_swa_fwd launch
+    over the band's 64 x 64 blocks; otherwise the composed attention with the band mask built on the host."""
+    q, k = asarray(q), asarray(k)
+    return _attn_fwd(_swa_form(q, k, layout), q, k, v, True, scale, layout, route, None, window)
+
+
+def attention_swa_bwd(q, k, v, o, do, lse, window, scale=None, layout="bthd", route=None, need=(True, True, True)):
+    """(dq, dk, dv) of attention_swa for the gradient `do` of its output (need: which of the three; the others are None):
+    tnn_swa_bwd_q (delta, and dq when needed), then tnn_swa_bwd_kv when dk or dv is needed."""
+    q, k = asarray(q), asarray(k)
+    form = _swa_form(q, k, layout)
+    dq, delta = _attn_bwd_q(form, q, k, v, o, do, lse, True, scale, layout, route, bool(need[0]), None, None, window)
+    dk, dv = _attn_bwd_kv(form, q, k, v, do, lse, delta, True, scale, layout, route, bool(need[1]), bool(need[2]), None, None,
+                          None, window)
+    return dq, dk, dv
+
+
+def swa_fill(k, v, R, lens=None, route=None):
+    """(k_ring, v_ring) [B, R, Hkv, .] of a prefill's k [B, T, Hkv, D] and v [B, T, Hkv, Dv] (layout "bthd"): row t of
+    sequence b goes to slot t mod R for the last R of its n_b live rows (n_b = T, or lens[b] of a ragged.Lengths / dense int64
+    device array); the other slots hold zeros.  Native (float32): ONE tnn_swa_fill launch that reads the lengths on the
+    device.  Composed: slice assignments with host arithmetic."""
+    dt, (k, v) = _operands(k, v)
+    if len(k.shape) != 4 or k.shape[:3] != v.shape[:3]:
+        raise ValueError("swa_fill: k [B, T, Hkv, D] and v [B, T, Hkv, Dv] expected, got %s and %s" % (k.shape, v.shape))
+    R = _sw.check_window(R, "swa_fill")
+    (b, t, h, d), dv = k.shape, v.shape[3]
+    ld = None if lens is None else _ragged_state(lens, "swa_fill", "lens")
+    if ld is not None and tuple(ld.shape) != (b,):
+        raise ValueError("swa_fill: lens must have shape (%d,), got %s" % (b, tuple(ld.shape)))
+    kr, vr = zeros((b, R, h, d), dt), zeros((b, R, h, dv), dt)
+    native = _lib.get().has_swa and dt == np.float32 and max(d, dv) <= _sw.MAX_HEAD_DIM
+    if route == "native" and not native:
+        raise ValueError("the native swa_fill route needs libtnn_hip.so, float32 operands and head dimensions <= %d" % _sw.MAX_HEAD_DIM)
+    if b * t * h == 0:
+        return kr, vr
+    if native and route != "composed":
+        st = lambda T, W: _at._strides("bthd", h, T, W)
+        _lib.get().swa_fill(k._ptr, v._ptr, kr._ptr, vr._ptr, b, h, t, R, d, dv,
+                            _i64arr(st(t, d) + st(t, dv) + st(R, d) + st(R, dv)), _ptr_of(ld))
+        return kr, vr
+    host = None if lens is None else _ragged_mirror(lens, "swa_fill")
+    for i in range(b):
+        rows, slots = _sw.ring_rows(t if host is None else host[i], t, R)
+        for a, e in _runs(rows, slots):
+            kr[i, slots[a]:slots[e - 1] + 1] = k[i, rows[a]:rows[e - 1] + 1]
+            vr[i, slots[a]:slots[e - 1] + 1] = v[i, rows[a]:rows[e - 1] + 1]
+    return kr, vr
+
+
+def _runs(rows, slots):
+    """[(first, end)] index runs of `rows` over which the slots ascend by one (at most two: the ring wraps once)."""
+    cuts = [0] + [i for i in range(1, len(slots)) if slots[i] != slots[i - 1] + 1] + [len(slots)]
+    return [(a, e) for a, e in zip(cuts[:-1], cuts[1:]) if e > a]
+
+
+def attention_decode_swa(q, k_ring, v_ring, k_new, v_new, pos=None, lens=None, scale=None, route=None, splits=None):
+    """o [B, H, Dv] of ONE decoding step over a ring of R slots (layout "bthd": k_ring [B, R, Hkv, D], v_ring [B, R, Hkv, Dv];
+    q [B, H, D], k_new [B, Hkv, D], v_new [B, Hkv, Dv]).  The step sits at position `pos` (a host integer) or lens[b] (a
+    ragged.Lengths or dense int64 device array, read ON THE DEVICE): its row is written to slot p mod R IN PLACE and the query
+    attends over the min(p + 1, R) live slots.  Native (float32): ONE tnn_swa_decode_attn call whose arguments, with lens=, do
+    not depend on the lengths — splits come from R alone (swa.choose_splits).  Composed: a slice assignment and the composed
+    attention over the live slots with host arithmetic; with lens= a loop over the sequences."""
+    what = "attention_decode_swa"
+    if (pos is None) == (lens is None):
+        raise ValueError("%s: give pos= (a host integer shared by the batch) or lens= (one per sequence), not both" % what)
+    if k_new is None or v_new is None:
+        raise ValueError("%s: k_new and v_new are required (the step writes its row into the ring)" % what)
+    dt, q, k_ring, v_ring, k_new, v_new, ld = _decode_operands(what, q, k_ring, v_ring, k_new, v_new, lens)
+    if pos is not None and int(pos) < 0:
+        raise ValueError("%s: pos must be >= 0, got %r" % (what, pos))
+    lib = _lib.get()
+    R = int(k_ring.shape[1]) if len(k_ring.shape) == 4 else 0
+    native = lib.has_swa and dt == np.float32
+    plan = _gq.plan_gqa_decode(q.shape, k_ring.shape, v_ring.shape, max(R - 1, 0), True, k_new.shape, v_new.shape, scale, "bthd",
+                               splits, native=native, float_ok=native, route=route or SWA_ROUTE)
+    if ld is not None and tuple(ld.shape) != (plan.B,):
+        raise ValueError("%s: lens must have shape (%d,), got %s" % (what, plan.B, tuple(ld.shape)))
+    if plan.empty():
+        return zeros(plan.out_shape, dt)
+    if plan.route == "native":
+        out = DeviceArray._new(plan.out_shape, dt)
+        nbytes = plan.workspace_bytes(dt.itemsize)
+        ws = DeviceArray._new((nbytes // dt.itemsize,), dt) if nbytes else None
+        lib.swa_decode_attn(q._ptr, k_new._ptr, v_new._ptr, k_ring._ptr, v_ring._ptr, out._ptr, _ptr_of(ws), nbytes, plan.B, plan.H,
+                            0 if pos is None else int(pos), _ptr_of(ld), R, plan.D, plan.Dv, _i64arr(plan.strides()), plan.scale,
+                            plan.splits, plan.group)
+        return out
+    if ld is None:
+        return _swa_decode_composed(plan, q, k_ring, v_ring, k_new, v_new, int(pos), R)
+    if _lib.capturing:
+        raise RuntimeError("%s (composed route) loops over the sequences with host lengths, which a graph capture cannot do" % what)
+    host = _ragged_mirror(lens, what)
+    out = zeros(plan.out_shape, dt)
+    for b in range(plan.B):
+        if int(host[b]) >= 0:
+            one = slice(b, b + 1)
+            sub = _gq.plan_gqa_decode(q[one].shape, k_ring[one].shape, v_ring[one].shape, R - 1, True, k_new[one].shape,
+                                      v_new[one].shape, plan.scale, "bthd", route="composed")
+            out[one] = _swa_decode_composed(sub, q[one], k_ring[one], v_ring[one], k_new[one], v_new[one], int(host[b]), R)
+    return out
+
+
+def _swa_decode_composed(plan, q, k_ring, v_ring, k_new, v_new, pos, R):
+    """The ring with host arithmetic: the row into slot pos mod R, then the composed attention over the live slots."""
+    slot, live = _sw.ring_slot(pos, R), _sw.ring_live(pos, R)
+    k_ring[:, slot] = k_new
+    v_ring[:, slot] = v_new
+    o, _ = attention(q.reshape(plan.B, 1, plan.H, plan.D), _gqa_expand(k_ring[:, :live], plan.group, 2),
+                     _gqa_expand(v_ring[:, :live], plan.group, 2), False, plan.scale, "bthd", "composed")
+    return o.reshape(plan.out_shape)
 
 
 def gqa_decode(q, k_cache, v_cache, length=None, k_new=None, v_new=None, lens=None, scale=None, layout="bthd", route=None,

@@ -104,11 +104,17 @@ def build(args):
     drop = args.dropout
     rotary = Rotary(args.seq) if getattr(args, "rope", False) else None      # shared by the blocks; then no "pos" table
     mlp = getattr(args, "mlp", "gelu")
+    window = getattr(args, "window", None)                # --window W: every position attends to its last W (swa.py)
+    if window is not None:
+        for flag in ("ragged_train", "kv_quant", "prefill_chunk", "second_turn"):
+            if getattr(args, flag, None):
+                raise ValueError("--window excludes --%s (a window over a padded batch, an int8 cache or a chunked prefill is "
+                                 "out of scope)" % flag.replace("_", "-"))
     net = Net([Embedding(args.vocab, args.width, max_len=None if rotary else args.seq, fused=fused, dropout=drop),
                TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
-                                rope=rotary, mlp=mlp),
+                                rope=rotary, mlp=mlp, window=window),
                TransformerBlock(args.heads, num_in=args.width, causal=True, fused=fused, dropout=drop, kv_heads=args.kv_heads,
-                                rope=rotary, mlp=mlp),
+                                rope=rotary, mlp=mlp, window=window),
                LayerNorm(args.width, fused=fused), Rows(), Dense(args.vocab, num_in=args.width, fused=fused)])
     # --ragged-train: the targets at dead positions carry this index and count for nothing
     ignore = IGNORE if getattr(args, "ragged_train", False) else None
@@ -252,6 +258,10 @@ def parse(argv=None):
                         help="rotary position embeddings (one Rotary shared by the blocks) instead of learned positions")
     parser.add_argument("--mlp", default="gelu", choices=("gelu", "swiglu", "geglu"),
                         help="feed-forward of the blocks: gelu (default), or the gated forms swiglu / geglu (one packed fc1)")
+    parser.add_argument("--window", default=None, type=int, metavar="W",
+                        help="sliding-window attention in training: every position attends to its last W positions "
+                             "; --generate then keeps a ring of W rows per layer (combines with --rope, --kv-heads, --mlp, "
+                             "--generate, --ragged and --capture; not with --kv-quant, --prefill-chunk or --ragged-train)")
     parser.add_argument("--period", default=4, type=int)
     parser.add_argument("--seed", default=0, type=int)
     parser.add_argument("--dropout", default=0.0, type=float, help="dropout rate of the embedding and the blocks (0: none)")

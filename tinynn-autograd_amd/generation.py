@@ -74,6 +74,18 @@ class LayerCache(object):
         self.extend = bool(extend)     # a filled cache also takes T > 1 new rows (ops.attention_extend_); False: ONE per step
         self.lens = lens     # a ragged.Lengths: every sequence's own live rows, read on the device; `length` is then the
                              # host's upper bound (what check() uses)
+        self.ring = None     # a windowed layer's cache (set_ring): k and v are rings of R = window slots, token t in slot
+                             # t mod R; `length` keeps counting positions and the cache never fills
+        self.prompt_lens = None    # ragged + ring: the prompts' lengths [B] on the device, which the ring's fill reads (during
+                                   # the prefill `lens` holds the position of every sequence's LAST token, one less)
+
+    def set_ring(self, window):
+        """What a MultiHeadAttention(window=) asks of its cache BEFORE any launch: a ring of `window` slots."""
+        if self.quant is not None:
+            raise ValueError("KVCache: a window with quant=%r (a window over an int8 cache is out of scope)" % self.quant)
+        if self.extend:
+            raise ValueError("KVCache: a window with extend=True / prefill_chunk (chunked prefill into a ring is out of scope)")
+        self.ring = int(window)
 
     def check(self, b, t, h, d):
         """What MultiHeadAttention.forward asks BEFORE any launch."""
@@ -89,9 +101,9 @@ class LayerCache(object):
         elif t != 1:
             raise ValueError("KVCache: the cache holds %d tokens — a step takes ONE new token per sequence, got T = %d "
                              "(chunked prefill is out of scope)" % (self.length, t))
-        elif self.length >= self.max_len:
+        elif self.ring is None and self.length >= self.max_len:
             raise ValueError("KVCache: the cache is full (%d of %d rows)" % (self.length, self.max_len))
-        if tuple(self.k.shape) != (b, self.max_len, h, d):
+        if tuple(self.k.shape) != (b, self.ring or self.max_len, h, d):
             raise ValueError("KVCache: the cache was allocated for [B, H, D] = %s, got %s"
                              % ((self.k.shape[0],) + tuple(self.k.shape[2:]), (b, h, d)))
 
@@ -99,6 +111,12 @@ class LayerCache(object):
         """The prefill's k and v [B, T, H, D] (device arrays) become rows [0, T) — quantized by ONE launch when the cache is
         an int8 one (`route`: that launch's, None picks)."""
         b, t, h, d = (int(s) for s in k.shape)
+        if self.ring is not None:                    # ONE launch: the last `ring` live rows of every sequence, row t to slot t mod ring
+            if self.lens is not None and self.prompt_lens is None:
+                raise ValueError("KVCache: a ragged batch into a ring needs the prompts' lengths (KVCache.set_lens(lens, prompt_lens))")
+            self.k, self.v = da.swa_fill(k, v, self.ring, lens=self.prompt_lens if self.lens is not None else None, route=route)
+            self.length = t
+            return
         if self.quant is not None:
             self.k, self.v = da.zeros((b, self.max_len, h, d), np.uint8), da.zeros((b, self.max_len, h, int(v.shape[3])), np.uint8)
             self.k_scale, self.v_scale = (da.zeros((b, self.max_len, h), np.float32) for _ in range(2))
@@ -134,13 +152,16 @@ class KVCache(object):
     def layer(self, index):
         if index not in self.layers:
             self.layers[index] = LayerCache(self.max_len, self.lens, self.extend, self.quant)
+            self.layers[index].prompt_lens = getattr(self, "prompt_lens", None)
         return self.layers[index]
 
-    def set_lens(self, lens):
-        """A ragged batch: every layer's decode step reads the sequences' lengths from `lens` (a ragged.Lengths) on the device."""
-        self.lens = lens
+    def set_lens(self, lens, prompt_lens=None):
+        """A ragged batch: every layer's decode step reads the sequences' lengths from `lens` (a ragged.Lengths) on the device;
+        prompt_lens: the prompts' lengths (dense int64 device array [B]), which a windowed layer's ring fill reads."""
+        self.lens = self.lens if lens is None else lens
+        self.prompt_lens = prompt_lens
         for c in self.layers.values():
-            c.lens = lens
+            c.lens, c.prompt_lens = self.lens, prompt_lens
 
     def set_length(self, length):
         """The host's upper bound of the live rows of every layer that has been filled (generate's captured steps: a replay
@@ -451,6 +472,8 @@ def _generate_ragged(model_or_net, layers, host, N, temperature, top_k, u, cache
             kv.set_lens(lens)
         elif cache:
             kv = KVCache(Tout, lens)
+        if kv is not None:
+            kv.set_lens(lens, start_d)
         arange = np.arange(B, dtype=np.int64)
 
         def last_rows(logits, t):
